@@ -21,6 +21,10 @@ the same stream; its hit list is also compared with the GPU's (field "parity").
 5 -- the known-LAP full chain over 79 hop-channel streams (scan -> sort -> gather -> header +
 payload decode) and the 64-seed CLK1-6 brute force over a stream of 2^20 detected packets -- each
 with its own roofline figure and the reference's CPU loop on a bounded sample beside it.
+
+A plain run measures the headline only: `cpu_baseline` (with "parity") and `secondary` are measured
+with --full alone and are null / absent otherwise.  --dump-outputs DIR writes the hit list of the
+last timed step as .npy files (see dump_outputs), so that two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -42,6 +46,7 @@ HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8
 VALU_MIN_PER_WORD = 124        # fewest vector instructions per 64 offsets of an exact LAP_ANY filter of this shape (NOTEBOOK.md 6.4 for the derivation: 30 + 30 + 8 x 8)
 SEED = 20260926
 STRIDE = 4096
+DUMP_SAMPLE = 1 << 20          # hits --dump-outputs writes at most (four float64 fields: 32 MiB)
 
 
 def csrc_fingerprint(csrc_dir=None):
@@ -255,6 +260,19 @@ def payload_hash(res):
     h = ((res["payload"] & mask) * (2 * k + 1).astype(np.uint64)[None, :]).sum(axis=1, dtype=np.uint64)
     wrote = (res["header_rv"] == 1) & np.isin(res["payload_rv"], (2, 10, 1000))
     return np.where(wrote, h, np.uint64(0))
+
+
+def dump_outputs(out_dir, hits):
+    """--dump-outputs: the hit records of the last timed step, as a caller of btbbx_scan_device receives them, one .npy per
+    field (float64: offsets stay exact below 2^53) plus the hit count.  The kernel appends hits in no fixed order, so they
+    are put in (stream, offset, lap) order first; of a longer list a fixed, seeded sample of DUMP_SAMPLE records is kept."""
+    os.makedirs(out_dir, exist_ok=True)
+    hits = hits[np.lexsort((hits["lap"], hits["offset"], hits["stream"]))]
+    np.save(os.path.join(out_dir, "hit_count.npy"), np.array([len(hits)], np.float64))
+    if len(hits) > DUMP_SAMPLE:
+        hits = hits[np.sort(np.random.default_rng(SEED).choice(len(hits), DUMP_SAMPLE, replace=False))]
+    for f in ("stream", "offset", "lap", "ac_errors"):
+        np.save(os.path.join(out_dir, "hit_%s.npy" % f), hits[f].astype(np.float64))
 
 
 class Timer:
@@ -670,6 +688,8 @@ def channels79(args, bt, lib, shard, dev, rank, world, red_dev):
         mine_h = hits_t.cpu().numpy().view(bt.HIT_DTYPE)[:nhits].copy()
         mine_h["offset"] += np.uint64(plan["first_offset"])         # offset inside the channel (stream = channel number)
         np.save("%s.rank%d.npy" % (args.dump_hits, rank), mine_h)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, hits_t.cpu().numpy().view(bt.HIT_DTYPE)[:nhits])
 
     # ground truth: injected sync words with <= 2 bit errors whose window starts inside this rank's range of a channel
     from libbtbb_amd import synth
@@ -844,9 +864,11 @@ def main():
     ap.add_argument("--gib", type=float, default=None, help="packed stream size in GiB: per GPU for --layout single (default 4), "
                     "in total for --layout channels79 (default 64)")
     ap.add_argument("--cpu-symbols", type=int, default=0, help="size of the CPU-baseline sample (0 = 2^33 symbols when the host has >= 64 CPUs and the RAM for it, else 2^30)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the config 3 / config 5 block")
-    ap.add_argument("--only-secondary", default=None, metavar="NAME", help="run one line of the secondary block only (with the input it "
+    ap.add_argument("--full", action="store_true", help="besides the headline, measure the CPU baseline (with its parity check) "
+                    "and the secondary block; a plain run measures the headline only")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the config 3 / config 5 block")
+    ap.add_argument("--only-secondary", default=None, metavar="NAME", help="with --full: run one line of the secondary block only (with the input it "
                     "needs): lap_any_4gib_ordered, lap_any_4gib_init4, known_lap_79ch_chain_full_payloads, known_lap_79ch_chain, clk6_bruteforce, clk6_bruteforce_all_types")
     ap.add_argument("--layout", default="single", choices=["single", "channels79"],
                     help="single: one stream of --gib GiB per GPU (weak scaling, BASELINE configs[1], the default line); "
@@ -857,7 +879,14 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for "
                     "exercising the N>1 path where ranks share one GPU)")
     ap.add_argument("--share-gpu", action="store_true", help="testing: every rank uses cuda:0")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write the hit list of the last one "
+                    "to DIR/hit_<field>.npy (float64; a fixed, seeded sample of %d hits when there are more) and DIR/hit_count.npy; "
+                    "--gpus 1 only" % DUMP_SAMPLE)
     args = ap.parse_args()
+    if args.only_secondary and not args.full:
+        ap.error("--only-secondary is part of --full")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
 
     if args.gib is None:
         args.gib = 4.0 if args.layout == "single" else 64.0
@@ -937,6 +966,8 @@ def main():
         mine_h = hits_t.cpu().numpy().view(bt.HIT_DTYPE)[:nhits].copy()
         mine_h["offset"] += np.uint64(plan["first_offset"])
         np.save("%s.rank%d.npy" % (args.dump_hits, rank), mine_h)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, hits_t.cpu().numpy().view(bt.HIT_DTYPE)[:nhits])
     t_el = torch.tensor([elapsed, kern_ms], dtype=torch.float64, device=red_dev)
     if world > 1:
         dist.all_reduce(t_el, op=dist.ReduceOp.MAX)
@@ -998,7 +1029,7 @@ def main():
             "csrc_sha16": fp,
         }
         cpu = host_cpu()
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             cpu_symbols = args.cpu_symbols
             if cpu_symbols <= 0:                     # >= 0.5 s per thread on a 256-thread host needs ~2^33 symbols (8 GiB of bytes)
                 import psutil
@@ -1012,7 +1043,7 @@ def main():
             result["parity"] = bool(parity)
         else:
             result["cpu_baseline"] = None
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             ordered = four = None
             if args.only_secondary in (None, "lap_any_4gib_init4"):
                 four = four_error_headline(bt, lib, dev, cur, hs, stream, nwords, nbits, hits_t, cnt_t, cap)

@@ -2,10 +2,11 @@
 # A/B of library builds on the GPU box: rocprofv3 kernel averages of the secondary block's kernels matching a pattern
 #   tools/ab_decode.sh [pattern]
 export TMPDIR=/tmp
+root=$PWD
 for so in libbtbb_amd/libbtbb_amd.so libbtbb_amd/variants/*.so; do
   [ -f "$so" ] || continue
   d=/tmp/abd_$(basename $so .so); rm -rf $d
-  ( cd /tmp && LIBBTBB_AMD_SO=$GRAFT_REPO_ROOT/$so rocprofv3 --kernel-trace --stats --output-format csv -d $d -- python $GRAFT_REPO_ROOT/bench.py --steps 4 --warmup 1 --no-cpu > /dev/null 2>&1 )
+  ( cd /tmp && LIBBTBB_AMD_SO=$root/$so rocprofv3 --kernel-trace --stats --output-format csv -d $d -- python $root/bench.py --full --steps 4 --warmup 1 --no-cpu > /dev/null 2>&1 )
   f=$(find $d -name "*kernel_stats.csv" | head -1)
   python - <<PY
 import csv

@@ -9,7 +9,7 @@ done
 for rep in 1 2; do
   for so in libbtbb_amd/libbtbb_amd.so libbtbb_amd/variants/*.so; do
     for line in clk6_bruteforce clk6_bruteforce_all_types; do
-      LIBBTBB_AMD_SO=$PWD/$so timeout 600 python bench.py --steps 5 --warmup 1 --no-cpu --only-secondary $line 2>/dev/null | tail -1 | python -c "
+      LIBBTBB_AMD_SO=$PWD/$so timeout 600 python bench.py --full --steps 5 --warmup 1 --no-cpu --only-secondary $line 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 for k,v in d['secondary'].items(): print('$so', k, v['value'], 'kernel_ms', v['roofline']['kernel_ms'], 'parity', v.get('parity'))" >> $out/ab.txt

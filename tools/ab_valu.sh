@@ -2,7 +2,7 @@
 # per-variant instruction counts of one kernel: tools/ab_valu.sh <kernel-substring>
 for so in libbtbb_amd/libbtbb_amd.so libbtbb_amd/variants/*.so; do
   [ -f "$so" ] || continue
-  LIBBTBB_AMD_SO=$PWD/$so python tools/pmc_collect.py --out /tmp/abv_$(basename $so .so) --kernel ${1:-decode_hits} --groups SQ_INSTS_VALU,SQ_INSTS_SALU,SQ_INSTS_LDS,SQ_WAVES -- python bench.py --steps 1 --warmup 1 --no-cpu 2>/dev/null | python -c "
+  LIBBTBB_AMD_SO=$PWD/$so python tools/pmc_collect.py --out /tmp/abv_$(basename $so .so) --kernel ${1:-decode_hits} --groups SQ_INSTS_VALU,SQ_INSTS_SALU,SQ_INSTS_LDS,SQ_WAVES -- python bench.py --full --steps 1 --warmup 1 --no-cpu 2>/dev/null | python -c "
 import sys,json
 d=json.load(sys.stdin)
 for k,v in d.items():

@@ -1,8 +1,8 @@
 #!/bin/bash
-# full GPU check of the current build: pytest -m gpu, default bench line, soak
+# full GPU check of the current build: pytest -m gpu, the --full bench line, soak
 out=gpurun_out/$1; mkdir -p $out
 timeout 1500 python -m pytest tests -x -q -m gpu 2>&1 | grep -E "passed|failed|error|Error|assert" | tail -15 > $out/pytest_gpu.txt
-python bench.py 2> $out/bench.err | tail -1 > $out/bench.json
+python bench.py --full 2> $out/bench.err | tail -1 > $out/bench.json
 [ "${2:-0}" != "0" ] && timeout 400 python tools/soak.py --seconds $2 --seed ${3:-5} 2>&1 | tail -3 > $out/soak.txt
 cat $out/pytest_gpu.txt $out/soak.txt 2>/dev/null; python - <<PY
 import json

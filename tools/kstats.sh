@@ -1,9 +1,10 @@
 #!/bin/bash
-# rocprofv3 --kernel-trace --stats over the default bench (no CPU baselines): per-kernel average durations
+# rocprofv3 --kernel-trace --stats over the --full bench (no CPU baselines): per-kernel average durations
 #   tools/kstats.sh <out-dir-name> [pattern]
 out=gpurun_out/$1; mkdir -p $out
 export TMPDIR=/tmp
-( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$out/stats -- python $GRAFT_REPO_ROOT/bench.py --steps 6 --warmup 2 --no-cpu > /dev/null 2>&1 )
+root=$PWD
+( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/stats -- python $root/bench.py --full --steps 6 --warmup 2 --no-cpu > /dev/null 2>&1 )
 find $out/stats -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $out/kernel_stats.csv
 rm -rf $out/stats
 python - <<PY

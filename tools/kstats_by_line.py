@@ -5,7 +5,7 @@
     python tools/kstats_by_line.py <out-dir>        (on the GPU box, from the repo root)
 
 For the headline (`bench.py --steps 10 --warmup 2 --no-cpu --no-secondary`) and for every line of the secondary block
-(`--only-secondary <line>`) the command runs under `rocprofv3 --kernel-trace` (no counters, no other trace domains), and
+(`--full --only-secondary <line>`) the command runs under `rocprofv3 --kernel-trace` (no counters, no other trace domains), and
 <out-dir>/kernel_stats_<line>.csv gets one row per kernel: calls counted, average / min / max / standard deviation in
 microseconds over the dispatches that are left when the first DROP dispatches of that kernel are dropped -- the warm-up
 steps of the line (the headline's two warm-up launches; one warm call of every secondary line) plus the cold first launch."""
@@ -20,12 +20,12 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LINES = [("headline", ["--steps", "10", "--warmup", "2", "--no-cpu", "--no-secondary"], 2),
-         ("lap_any_4gib_ordered", ["--steps", "2", "--warmup", "1", "--no-cpu", "--only-secondary", "lap_any_4gib_ordered"], 1),
-         ("lap_any_4gib_init4", ["--steps", "2", "--warmup", "1", "--no-cpu", "--only-secondary", "lap_any_4gib_init4"], 1),
-         ("known_lap_79ch_chain_full_payloads", ["--steps", "2", "--warmup", "1", "--no-cpu", "--only-secondary", "known_lap_79ch_chain_full_payloads"], 1),
-         ("known_lap_79ch_chain", ["--steps", "2", "--warmup", "1", "--no-cpu", "--only-secondary", "known_lap_79ch_chain"], 1),
-         ("clk6_bruteforce", ["--steps", "2", "--warmup", "1", "--no-cpu", "--only-secondary", "clk6_bruteforce"], 1),
-         ("clk6_bruteforce_all_types", ["--steps", "2", "--warmup", "1", "--no-cpu", "--only-secondary", "clk6_bruteforce_all_types"], 1)]
+         ("lap_any_4gib_ordered", ["--full", "--steps", "2", "--warmup", "1", "--no-cpu", "--only-secondary", "lap_any_4gib_ordered"], 1),
+         ("lap_any_4gib_init4", ["--full", "--steps", "2", "--warmup", "1", "--no-cpu", "--only-secondary", "lap_any_4gib_init4"], 1),
+         ("known_lap_79ch_chain_full_payloads", ["--full", "--steps", "2", "--warmup", "1", "--no-cpu", "--only-secondary", "known_lap_79ch_chain_full_payloads"], 1),
+         ("known_lap_79ch_chain", ["--full", "--steps", "2", "--warmup", "1", "--no-cpu", "--only-secondary", "known_lap_79ch_chain"], 1),
+         ("clk6_bruteforce", ["--full", "--steps", "2", "--warmup", "1", "--no-cpu", "--only-secondary", "clk6_bruteforce"], 1),
+         ("clk6_bruteforce_all_types", ["--full", "--steps", "2", "--warmup", "1", "--no-cpu", "--only-secondary", "clk6_bruteforce_all_types"], 1)]
 
 
 def main():

@@ -63,7 +63,7 @@ json.dump({
 print("traffic.json: %.3f GB per launch = %.3f x algorithmic" % (b / 1e9, b / alg))
 
 out = {"csrc_sha16": fp, "source": "%s/pmc_sec_<line>.json: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over "
-       "`python bench.py --steps 2 --warmup 1 --no-cpu --only-secondary <line>` (one line of the block at a time: a kernel's mean "
+       "`python bench.py --full --steps 2 --warmup 1 --no-cpu --only-secondary <line>` (one line of the block at a time: a kernel's mean "
        "per launch then belongs to one workload); (2 x FETCH_SIZE + WRITE_SIZE) KB x 1024 per launch, as in traffic.json" % rel}
 # (round 6: the ordered lines run the scan kernels' slot form -- "..., true>" -- and the compaction; the plain forms also appear in those
 # runs, as the lines' own unordered timing and as the gated fallback's launches that return at once: not part of the step)

@@ -9,7 +9,7 @@ timeout 300 python tools/pmc_collect.py --out $out/pmcp --kernel scan_ --groups 
 rm -rf $out/pmcp
 for line in lap_any_4gib_ordered lap_any_4gib_init4 known_lap_79ch_chain_full_payloads known_lap_79ch_chain clk6_bruteforce clk6_bruteforce_all_types; do
   timeout 300 python tools/pmc_collect.py --out $out/pmcp --kernel "" --groups SQ_THREAD_CYCLES_VALU,SQ_CYCLES,SQ_INSTS_VALU \
-    -- python bench.py --steps 2 --warmup 1 --no-cpu --only-secondary $line > $out/pmc_pipe_$line.json 2> $out/pmcp.err
+    -- python bench.py --full --steps 2 --warmup 1 --no-cpu --only-secondary $line > $out/pmc_pipe_$line.json 2> $out/pmcp.err
   rm -rf $out/pmcp
 done
 rm -f $out/pmcp.err
