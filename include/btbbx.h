@@ -22,6 +22,8 @@
  *                        lib/src/bluetooth_packet.c:1198-1297, 1371-1408
  *   btbbx_hop_*       <- gen_hops / hop / init_candidates / channel_winnow / btbb_winnow,
  *                        lib/src/bluetooth_piconet.c:311-362, 443-446, 455-498, 575-645
+ *   btbbx_le_*        <- the LE search in front of lell_allocate_and_decode (the reference
+ *                        expects found, dewhitened bytes), lib/src/bluetooth_le_packet.c:282-312
  */
 #ifndef INCLUDED_BTBBX_H
 #define INCLUDED_BTBBX_H
@@ -318,6 +320,65 @@ int btbbx_decode_hits_piconet_phase_device(const uint64_t *d_words, uint64_t n_w
 					   const btbbx_hit *d_hits, const uint32_t *d_count, uint32_t cap,
 					   const btbbx_pkt_in *entry, uint32_t clk_div, uint32_t clk_phase, uint32_t max_length,
 					   btbbx_pkt_out *d_out, uint32_t *d_lengths, void *hip_stream);
+
+/* ---- Bluetooth LE 1M scan (Core v5.x Vol 6 Part B 2.1, 3.1.1, 3.2) ------------------------- */
+/* Finds preamble + access address (AA) in demodulated LE captures (packed streams as above, one per RF channel),
+ * dewhitens with the channel's LFSR, reads the PDU length from the header, checks the CRC-24 and derives what
+ * lell_allocate_and_decode (lib/src/bluetooth_le_packet.c:282-312) derives from the dewhitened bytes.  The lell_*
+ * entry points themselves still abort: this is the batch path in front of them. */
+#define BTBBX_LE_ADV_AA       0x8e89bed6u
+#define BTBBX_LE_ADV_CRC_INIT 0x555555u
+#define BTBBX_LE_MAX_BYTES    64          /* lell_packet.symbols, bluetooth_le_packet.h:30 */
+#define BTBBX_LE_MAX_ERRORS   4
+
+/* Stage 1: the pattern search.  Arguments as btbbx_scan_device, except:
+ *   - offsets [0, search_bits) are tested for the first PREAMBLE bit, which needs search_bits + 39 <= 64 * n_words;
+ *   - a match is <= max_errors (0..4) mismatches over the 40 bits preamble + AA;
+ *   - the records are btbbx_hit with offset = first preamble bit, lap = the 32 AA bits AS RECEIVED,
+ *     ac_errors = mismatches over the 40 bits, stream = stream index.
+ * btbbx_order_hits_device / btbbx_sort_hits order them unchanged. */
+int btbbx_le_scan_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			 uint64_t search_bits, uint32_t aa, int max_errors,
+			 btbbx_hit *d_hits, uint32_t hit_cap, uint32_t *d_hit_count, void *hip_stream);
+
+/* one decoded LE packet (104 bytes) */
+typedef struct btbbx_le_pkt {
+	uint64_t offset;            /* first preamble bit in its stream */
+	uint16_t stream;
+	uint8_t  aa_errors;         /* mismatches over preamble + AA */
+	uint8_t  crc_ok;            /* 1 iff complete and crc_calc == crc_rx */
+	uint32_t crc_rx;            /* the 24 CRC bits as received: bit i = the i-th CRC bit on air (register position 23 - i) */
+	uint32_t crc_calc;          /* the CRC over the PDU in the same orientation */
+	uint16_t pdu_bytes;         /* 2 + L: the octets the CRC covered (L = header octet 1, all 8 bits) */
+	uint8_t  truncated;         /* the stream ended before the last CRC bit (bits past it read as 0); crc_ok = 0 */
+	/* what lell_allocate_and_decode(bytes, phys_channel, 0, &p) derives (bluetooth_le_packet.c:282-312) */
+	uint8_t  channel_idx;
+	uint8_t  channel_k;
+	uint8_t  is_data;
+	uint8_t  length;            /* header octet 1 masked as the reference does: 0x3f advertising, 0x1f data */
+	uint8_t  adv_type;
+	uint8_t  adv_tx_add;
+	uint8_t  adv_rx_add;
+	uint8_t  access_address_ok;
+	uint8_t  access_address_offenses;
+	uint32_t access_address;    /* as received */
+	uint8_t  bytes[BTBBX_LE_MAX_BYTES]; /* the received AA (4 octets), then the dewhitened header, payload and CRC; zero past the end */
+} btbbx_le_pkt;
+
+/* Stage 2: dewhiten + CRC + decode the first min(*d_count, cap) hits; the count stays in device memory.
+ * d_phys_channel: one uint16 per stream, the RF frequency in MHz (lell_allocate_and_decode's phys_channel).
+ * crc_init: CRCInit, 24 bits (BTBBX_LE_ADV_CRC_INIT on the advertising channels). */
+int btbbx_le_decode_hits_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words,
+				const btbbx_hit *d_hits, const uint32_t *d_count, uint32_t cap,
+				const uint16_t *d_phys_channel, uint32_t crc_init,
+				btbbx_le_pkt *d_out, void *hip_stream);
+
+/* Host wrapper: copy in, scan, order by (stream, offset), decode, copy out.  Returns the number of matches found
+ * or a negative BTBBX_E_*.  When that exceeds cap, the cap SMALLEST (stream, offset) records are returned, as
+ * btbbx_scan_host does.  Safe to call from several host threads at once. */
+int64_t btbbx_le_scan_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			   uint64_t search_bits, const uint16_t *phys_channel, uint32_t aa, uint32_t crc_init,
+			   int max_errors, btbbx_le_pkt *pkts, uint64_t cap);
 
 /* ---- hop selection and CLK1-27 reversal ------------------------- */
 #define BTBBX_SEQUENCE_LENGTH 134217728u   /* values of CLK1-27, bluetooth_piconet.h:102 */

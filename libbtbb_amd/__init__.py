@@ -77,6 +77,18 @@ assert TRIAL_DTYPE.itemsize == C.sizeof(Trial) == 4
 assert PKTIN_DTYPE.itemsize == C.sizeof(PktIn) == 16
 assert PKTOUT_DTYPE.itemsize == C.sizeof(PktOut)
 
+# Bluetooth LE (include/btbbx.h btbbx_le_*; le.hip checks the C layout with static_asserts)
+LE_ADV_AA = 0x8E89BED6
+LE_ADV_CRC_INIT = 0x555555
+LE_MAX_BYTES = 64
+LE_PKT_DTYPE = np.dtype([("offset", "<u8"), ("stream", "<u2"), ("aa_errors", "u1"), ("crc_ok", "u1"),
+                         ("crc_rx", "<u4"), ("crc_calc", "<u4"), ("pdu_bytes", "<u2"), ("truncated", "u1"),
+                         ("channel_idx", "u1"), ("channel_k", "u1"), ("is_data", "u1"), ("length", "u1"),
+                         ("adv_type", "u1"), ("adv_tx_add", "u1"), ("adv_rx_add", "u1"), ("access_address_ok", "u1"),
+                         ("access_address_offenses", "u1"), ("access_address", "<u4"), ("bytes", "u1", (LE_MAX_BYTES,)),
+                         ("pad", "u1", (4,))])
+assert LE_PKT_DTYPE.itemsize == 104 and LE_PKT_DTYPE.fields["bytes"][1] == 36
+
 _vp, _u64, _u32 = C.c_void_p, C.c_uint64, C.c_uint32
 
 # every symbol include/btbbx.h and include/btbb.h declare: (restype, argtypes)
@@ -139,6 +151,9 @@ SIGNATURES = {
     "btbbx_hop_reversal_close": (None, [_vp]),
     "btbbx_piconet_state": (C.c_int64, [_vp, C.c_int]),
     "btbbx_piconet_candidates": (C.c_int64, [_vp, _vp, _u64]),
+    "btbbx_le_scan_device": (C.c_int, [_vp, _u64, _u64, _u32, _u64, _u32, C.c_int, _vp, _u32, _vp, _vp]),
+    "btbbx_le_decode_hits_device": (C.c_int, [_vp, _u64, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp]),
+    "btbbx_le_scan_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, C.c_int, _vp, _u64]),
     # ---- btbb.h
     "btbb_init": (C.c_int, [C.c_int]),
     "btbb_get_release": (C.c_char_p, []),
@@ -307,6 +322,27 @@ def scan_symbols(symbols, search_length, lap=LAP_ANY, max_ac_errors=2, cap=1 << 
     if n > cap:
         raise BtbbError("hit buffer too small: %d > %d" % (n, cap))
     return hits[:n]
+
+
+def le_scan(words, search_bits, phys_channels, aa=LE_ADV_AA, crc_init=LE_ADV_CRC_INIT, max_errors=2, n_streams=1,
+            pitch_words=None, n_words=None, cap=1 << 20, truncate=False):
+    """Bluetooth LE packets (preamble + access address within max_errors bit errors, dewhitened, CRC checked) in
+    n_streams packed streams held in host memory: words is (n_streams, pitch_words) or flat, each stream's first n_words
+    words (default: all pitch_words) are its bits; phys_channels = the RF MHz of every stream.  Returns LE_PKT_DTYPE records in (stream, offset) order.  With truncate=True the `cap` smallest
+    (stream, offset) records are returned when more were found."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if pitch_words is None:
+        pitch_words = len(words) // n_streams
+    if n_words is None:
+        n_words = pitch_words
+    assert n_words <= pitch_words and (n_streams - 1) * pitch_words + n_words <= len(words)
+    phys = np.ascontiguousarray(np.broadcast_to(np.asarray(phys_channels, dtype=np.uint16), (n_streams,)))
+    pkts = np.zeros(max(cap, 1), dtype=LE_PKT_DTYPE)
+    n = check(lib().btbbx_le_scan_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, _ptr(phys), aa, crc_init,
+                                       max_errors, _ptr(pkts), cap), "btbbx_le_scan_host")
+    if n > cap and not truncate:
+        raise BtbbError("packet buffer too small: %d > %d" % (n, cap))
+    return pkts[:min(n, cap)]
 
 
 class DeviceBuffer:

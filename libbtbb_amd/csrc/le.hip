@@ -1,0 +1,646 @@
+// le.hip -- Bluetooth LE 1M uncoded PHY: access-address search, dewhitening, CRC-24 and the fields
+// lell_allocate_and_decode derives (lib/src/bluetooth_le_packet.c:282-312), over whole captures.
+//
+// Air format (Core v5.x Vol 6 Part B): preamble (8 alternating bits, the first equal to AA bit 0), access address
+// (32 bits), PDU = 16-bit header + L octets (L = header octet 1, all 8 bits), CRC-24.  Every octet LSB first, so
+// stream bit offset + i is bit i of the 40-bit pattern preamble | AA << 8.  Header, payload and CRC are whitened
+// (3.2: x^7 + x^4 + 1, position 0 = 1, positions 1..6 = channel index MSB first); the CRC (3.1.1:
+// x^24 + x^10 + x^9 + x^6 + x^4 + x^3 + x + 1, preset with CRCInit) covers the 2 + L PDU octets and is sent from
+// register position 23 down to 0.  Both registers run here in their reflected software form: whitening state bit j
+// = position 6 - j, CRC state bit j = position 23 - j; tests/_le.py shifts the spec's positions literally.
+#include "common.h"
+#include <algorithm>
+#include <stddef.h>
+
+#define LE_THREADS 256
+#define LE_WORDS 2                               // consecutive stream words per lane and tile (tile = 512 words)
+#define LE_TILE_WORDS (LE_THREADS * LE_WORDS)
+#define LE_RING 128                              // per-wave hit ring (entries)
+
+typedef uint32_t le_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t le_u32x2 __attribute__((ext_vector_type(2)));
+
+struct LeScanArgs {
+	const uint64_t *words;
+	uint64_t n_words;
+	uint64_t pitch_words;
+	uint64_t search_bits;
+	uint32_t tiles_per_stream;
+	uint32_t full_tiles;         // leading tiles of a stream whose words, halo word and offsets are all in range
+	uint32_t n_streams;
+	uint32_t pat_lo;             // window bits 0..31 = preamble | AA << 8
+	uint32_t pat_hi;             // window bits 32..39 = AA >> 24
+	int max_err;
+	btbbx_hit *hits;
+	uint32_t hit_cap;
+	uint32_t *hit_count;
+};
+
+__device__ __forceinline__ uint32_t le_alignbit(uint32_t hi, uint32_t lo, uint32_t sh) { return __builtin_amdgcn_alignbit(hi, lo, sh); }
+
+// truth table of f(a ^ ia, b ^ ib, c ^ ic) for the table `base` of f(a, b, c): a pattern bit of 1 folds into the
+// adder's immediate instead of costing an XOR per plane
+constexpr uint32_t le_tt3(uint32_t base, bool ia, bool ib, bool ic)
+{
+	uint32_t t = 0;
+	for (uint32_t idx = 0; idx < 8; idx++) {
+		const uint32_t a = ((idx >> 2) & 1) ^ (ia ? 1u : 0u), b = ((idx >> 1) & 1) ^ (ib ? 1u : 0u), c = (idx & 1) ^ (ic ? 1u : 0u);
+		t |= ((base >> (a * 4 + b * 2 + c)) & 1) << idx;
+	}
+	return t;
+}
+template <uint32_t TT>
+__device__ __forceinline__ uint32_t le_op3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, TT); }
+
+// Bit-sliced pre-filter over sixteen of the forty pattern bits: window bits 0..7 (the preamble) and 32..39 (the AA's
+// last octet) of 32 offsets.  r[0..7] = window bits 0..7, r[8..15] = bits 32..39.  PAT >= 0: the sixteen pattern bits
+// (bit k = plane k) are folded into the first adder level; PAT < 0: flip[k] (all ones where the pattern has a 1) is
+// XORed into each plane.  Returns the offsets with at most `limit` mismatches among the sixteen -- the count itself is
+// never formed: weight-1 sums s*, weight-2 carries c*; count = ones + 2 T with T = the number of set weight-2 bits, and
+// "<= limit" is decided from whether T is 0, <= 1 or <= 2.
+template <int PAT, int LIMIT>
+__device__ __forceinline__ uint32_t le_filter16(const uint32_t *r, const uint32_t *flip)
+{
+	uint32_t m[16];
+#pragma unroll
+	for (int k = 0; k < 16; k++)
+		m[k] = PAT < 0 ? (r[k] ^ flip[k]) : r[k];
+#define INV(k) (PAT >= 0 && ((PAT >> (k)) & 1))
+#define G3(base, i) le_op3<le_tt3(base, INV(i), INV(i + 1), INV(i + 2))>(m[i], m[i + 1], m[i + 2])
+	const uint32_t m15 = INV(15) ? ~m[15] : m[15];
+	if (LIMIT == 0) {                                   // no mismatch: the NOR of the sixteen planes
+		const uint32_t x0 = G3(0xfe, 0), x1 = G3(0xfe, 3), x2 = G3(0xfe, 6), x3 = G3(0xfe, 9), x4 = G3(0xfe, 12);
+		return ~(le_op3<0xfe>(x0, x1, x2) | le_op3<0xfe>(x3, x4, m15));
+	}
+	const uint32_t s0 = G3(0x96, 0), c0 = G3(0xe8, 0);
+	const uint32_t s1 = G3(0x96, 3), c1 = G3(0xe8, 3);
+	const uint32_t s2 = G3(0x96, 6), c2 = G3(0xe8, 6);
+	const uint32_t s3 = G3(0x96, 9), c3 = G3(0xe8, 9);
+	const uint32_t s4 = G3(0x96, 12), c4 = G3(0xe8, 12);
+#undef G3
+#undef INV
+	const uint32_t o1 = le_op3<0x96>(s0, s1, s2), k0 = le_op3<0xe8>(s0, s1, s2);
+	const uint32_t o2 = le_op3<0x96>(s3, s4, m15), k1 = le_op3<0xe8>(s3, s4, m15);
+	const uint32_t ones = o1 ^ o2, k2 = o1 & o2;
+	// the eight weight-2 bits c0..c4, k0, k1, k2 in three groups: a* = sums, b* = carries (weight 4 in the count)
+	if (LIMIT == 1)                                     // T == 0
+		return ~(le_op3<0xfe>(le_op3<0xfe>(c0, c1, c2), le_op3<0xfe>(c3, c4, k0), k1) | k2);
+	const uint32_t a0 = le_op3<0x96>(c0, c1, c2), b0 = le_op3<0xe8>(c0, c1, c2);
+	const uint32_t a1 = le_op3<0x96>(c3, c4, k0), b1 = le_op3<0xe8>(c3, c4, k0);
+	const uint32_t a2 = k1 ^ k2, b2 = k1 & k2;
+	const uint32_t b_any = le_op3<0xfe>(b0, b1, b2);
+	const uint32_t le1 = ~(b_any | le_op3<0xe8>(a0, a1, a2));                          // T <= 1
+	if (LIMIT == 3)
+		return le1;
+	if (LIMIT == 2) {                                   // T == 0, or T == 1 and no weight-1 mismatch
+		const uint32_t z = ~(b_any | le_op3<0xfe>(a0, a1, a2));
+		return z | (le1 & ~ones);
+	}
+	// LIMIT 4: T <= 1, or T == 2 and no weight-1 mismatch.  T <= 2 <=> (no b and not all three a) or (exactly one b and no a)
+	const uint32_t b_one = le_op3<0x96>(b0, b1, b2) & ~le_op3<0xe8>(b0, b1, b2);
+	const uint32_t le2 = (~b_any & ~le_op3<0x80>(a0, a1, a2)) | (b_one & ~le_op3<0xfe>(a0, a1, a2));
+	return le1 | (le2 & ~ones);
+}
+
+// One workgroup of 256 lanes works on a tile of 512 words of one stream at a time; a lane owns two consecutive words
+// (four dwords D[0..3]) and reads the next word as its halo (D[4..5]): chain c = the 32 offsets starting at dword c,
+// whose 40-bit windows lie in D[c .. c + 2].  Window bit j of chain c's offsets is alignbit(D[c + 1], D[c], j) and window
+// bit 32 + j is alignbit(D[c + 2], D[c + 1], j) -- the lower planes of chain c + 1 --, so the filter's sixteen planes of
+// the four chains take 5 x 7 funnel shifts (the shift by zero is the dword itself).  Survivors get the exact check
+// popcount((window ^ pattern) & mask40) <= limit; hits are ranked with a ballot and mbcnt into a per-wave ring and leave it
+// 64 at a time, with one counter atomic per 64 hits.
+template <int PAT, int LIMIT>
+__global__ __launch_bounds__(LE_THREADS) void le_scan_kernel(LeScanArgs a)
+{
+	__shared__ uint4 ring_mem[LE_THREADS / 64][LE_RING];
+	const uint32_t tid = threadIdx.x, lane = tid & 63;
+	uint32_t pat_lo = a.pat_lo, pat_hi = a.pat_hi;
+	asm volatile("" : "+v"(pat_lo), "+v"(pat_hi));     // (VGPR copies: a VALU op with an SGPR source issues at half rate)
+	uint32_t flip[16];
+#pragma unroll
+	for (int k = 0; k < 16; k++) {
+		flip[k] = (((k < 8 ? pat_lo : pat_hi) >> (k & 7)) & 1) ? 0xffffffffu : 0u;
+		if (PAT < 0)
+			asm volatile("" : "+v"(flip[k]));
+	}
+	const uint32_t tiles_per_stream = a.tiles_per_stream;
+	uint32_t stream = 0, t = blockIdx.x;
+	while (t >= tiles_per_stream && stream < a.n_streams) {
+		t -= tiles_per_stream;
+		stream++;
+	}
+	const uint32_t lw = tid * LE_WORDS;
+	uint64_t nw[LE_WORDS + 1];
+	auto fetch = [&](uint32_t ft, uint32_t fstream) {
+		// a buffer descriptor over the tile: the hardware's range check returns zero for words behind the stream's end
+		uint32_t bytes = 0;
+		const uint64_t *tp = a.words;
+		if (fstream < a.n_streams) {
+			tp = a.words + (uint64_t)fstream * a.pitch_words + (uint64_t)ft * LE_TILE_WORDS;
+			bytes = (LE_TILE_WORDS + 1u) * 8u;
+			if (ft >= a.full_tiles) {
+				asm volatile("" ::: "memory");
+				const uint64_t first = (uint64_t)ft * LE_TILE_WORDS;
+				const uint64_t left = first < a.n_words ? a.n_words - first : 0;
+				bytes = (uint32_t)(left < LE_TILE_WORDS + 1u ? left : LE_TILE_WORDS + 1u) * 8u;
+			}
+		}
+		const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint64_t *>(tp), 0, (int)bytes, 0x00020000);
+		const le_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(lw * 8u), 0, 0);
+		const le_u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)(lw * 8u), 16, 0);
+		nw[0] = ((uint64_t)v.y << 32) | v.x;
+		nw[1] = ((uint64_t)v.w << 32) | v.z;
+		nw[2] = ((uint64_t)w.y << 32) | w.x;
+	};
+	// Hits wait in a per-wave LDS ring and leave 64 at a time: one counter atomic per 64 hits (a single counter word saturates
+	// near 88 M atomics/s, which one atomic per wave and pass ran into at one packet per 4096 bits: 0.46 Tbit/s)
+	uint4 *ring = ring_mem[tid >> 6];
+	uint32_t q_head = 0, q_tail = 0;                // wave-uniform, free running
+	auto flush = [&](uint32_t n) {                  // the n <= 64 oldest entries -> the global hit list
+		uint32_t base = 0;
+		if (lane == 0)
+			base = atomicAdd(a.hit_count, n);
+		base = __builtin_amdgcn_readfirstlane(base);
+		if (lane < n && base + lane < a.hit_cap)
+			reinterpret_cast<uint4 *>(a.hits)[base + lane] = ring[(q_head + lane) & (LE_RING - 1)];
+		q_head += n;
+	};
+	auto stage = [&](bool hit, uint32_t s, uint64_t offset, uint32_t aa_rx, uint32_t nerr) {
+		const uint64_t mask = __ballot(hit);
+		if (!mask)
+			return;
+		if (q_tail - q_head + 64 > LE_RING)
+			flush(64);
+		if (hit) {
+			const uint32_t slot = q_tail + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
+			uint4 rec;
+			rec.x = (uint32_t)offset;
+			rec.y = (uint32_t)(offset >> 32);
+			rec.z = aa_rx;
+			rec.w = nerr | (s << 16);
+			ring[slot & (LE_RING - 1)] = rec;
+		}
+		q_tail += (uint32_t)__popcll(mask);
+	};
+	fetch(t, stream);
+	constexpr int NCH = 2 * LE_WORDS;
+	while (stream < a.n_streams) {
+		const uint64_t word0 = (uint64_t)t * LE_TILE_WORDS + lw;
+		uint32_t D[NCH + 2], m[NCH];
+#pragma unroll
+		for (int u = 0; u <= LE_WORDS; u++) {
+			D[2 * u] = (uint32_t)nw[u];
+			D[2 * u + 1] = (uint32_t)(nw[u] >> 32);
+		}
+		const bool ragged = t >= a.full_tiles;
+		const uint32_t this_stream = stream;
+		t += gridDim.x;
+		while (t >= tiles_per_stream && stream < a.n_streams) {
+			t -= tiles_per_stream;
+			stream++;
+		}
+		fetch(t, stream);                               // the next tile's words are loaded while this one is worked on
+		{
+			uint32_t P[2][8];
+			P[0][0] = D[0];
+#pragma unroll
+			for (int j = 1; j < 8; j++)
+				P[0][j] = le_alignbit(D[1], D[0], j);
+#pragma unroll
+			for (int c = 0; c < NCH; c++) {
+				uint32_t *up = P[(c + 1) & 1];
+				up[0] = D[c + 1];
+#pragma unroll
+				for (int j = 1; j < 8; j++)
+					up[j] = le_alignbit(D[c + 2], D[c + 1], j);
+				uint32_t r[16];
+#pragma unroll
+				for (int j = 0; j < 8; j++) {
+					r[j] = P[c & 1][j];
+					r[8 + j] = up[j];
+				}
+				m[c] = le_filter16<PAT, LIMIT>(r, flip);
+			}
+		}
+		if (ragged) {
+			asm volatile("" ::: "memory");
+#pragma unroll
+			for (int c = 0; c < NCH; c++) {
+				const uint64_t first_off = word0 * 64 + 32u * c;
+				m[c] &= first_off >= a.search_bits ? 0u
+					: (a.search_bits - first_off >= 32 ? 0xffffffffu : ((1u << (uint32_t)(a.search_bits - first_off)) - 1u));
+			}
+		}
+		// survivors: one offset of every chain per pass, passes until no lane of the wave has one left
+		for (;;) {
+			uint32_t any = 0;
+#pragma unroll
+			for (int c = 0; c < NCH; c++)
+				any |= m[c];
+			if (!__ballot(any != 0))
+				break;
+#pragma unroll
+			for (int c = 0; c < NCH; c++) {
+				if (!__ballot(m[c] != 0))
+					continue;
+				const uint32_t p = (uint32_t)__builtin_ctz(m[c] | 0x80000000u);
+				const uint32_t lo = le_alignbit(D[c + 1], D[c], p), hi = le_alignbit(D[c + 2], D[c + 1], p);
+				const uint32_t e = (uint32_t)__popc(lo ^ pat_lo) + (uint32_t)__popc((hi ^ pat_hi) & 0xffu);
+				const bool hit = m[c] != 0 && e <= (uint32_t)LIMIT;
+				m[c] &= m[c] - 1;
+				stage(hit, this_stream, word0 * 64 + 32u * c + p, (lo >> 8) | (hi << 24), e);
+			}
+		}
+		while (q_tail - q_head >= 64)
+			flush(64);
+	}
+	if (q_tail != q_head)
+		flush(q_tail - q_head);
+}
+
+// ---- stage 2: dewhitening, CRC-24, the lell fields ----------------------------------------------------------------
+
+// le_channel_index of the reference (bluetooth_le_packet.c:266-280), its integer arithmetic included: an odd or
+// out-of-range MHz value gives what the reference's unsigned-char conversion gives
+__host__ __device__ inline uint8_t le_channel_index(uint16_t mhz)
+{
+	const int f = mhz;
+	if (f == 2402)
+		return 37;
+	if (f < 2426)
+		return (uint8_t)((f - 2404) / 2);
+	if (f == 2426)
+		return 38;
+	if (f < 2480)
+		return (uint8_t)(11 + (f - 2428) / 2);
+	return 39;
+}
+
+// a 12-bit window of the AA with a run of seven or more equal bits, as the reference's enumeration counts such windows
+// (bluetooth_le_packet.c:184-238): its case list leaves out 38 of the 224 windows that hold such a run -- seven ones at
+// bits 0..6 or 5..11 unless the rest of the window is zero, seven ones at 4..10 with bit 2 clear, nine zeros at 0..8
+// unless bits 9..11 are all ones, and 0x401 -- and the offense count follows the reference, not the rule
+__host__ __device__ inline bool le_run_window(uint32_t v)
+{
+	uint32_t ones = v, zeros = ~v & 0xfffu;
+	for (int k = 0; k < 6; k++) {                       // x & x >> 1 ... six times: bit i survives iff bits i..i+6 are all set
+		ones &= ones >> 1;
+		zeros &= zeros >> 1;
+	}
+	if (!(ones | zeros))
+		return false;
+	if ((v & 0xffu) == 0x7fu && (v >> 8) != 0)
+		return false;
+	if ((v & 0xff0u) == 0xfe0u && (v & 0xfu) != 0)
+		return false;
+	if ((v & 0xffcu) == 0x7f0u)
+		return false;
+	if ((v & 0x3ffu) == 0x200u && (v >> 10) != 3)
+		return false;
+	return v != 0x401u;
+}
+
+// aa_data_channel_offenses (bluetooth_le_packet.c:100-242), restated: transitions beyond 24, fewer than two transitions
+// in the six most significant bits, four equal octets, the advertising AA or one of its one-bit neighbours, and one
+// per nibble-aligned 12-bit window with a long run (le_run_window)
+__host__ __device__ inline uint32_t le_data_offenses(uint32_t aa)
+{
+	uint32_t n = 0;
+	const uint32_t transitions = (uint32_t)__builtin_popcount((aa ^ (aa >> 1)) & 0x7fffffffu);
+	if (transitions > 24)
+		n += transitions - 24;
+	const uint32_t top6 = aa >> 26;
+	if (__builtin_popcount((top6 ^ (top6 >> 1)) & 0x1fu) < 2)
+		n++;
+	const uint32_t b0 = aa & 0xff;
+	if (b0 == ((aa >> 8) & 0xff) && b0 == ((aa >> 16) & 0xff) && b0 == (aa >> 24))
+		n++;
+	if (aa == BTBBX_LE_ADV_AA)
+		n++;
+	if (__builtin_popcount(aa ^ BTBBX_LE_ADV_AA) == 1)
+		n++;
+	for (int shift = 0; shift <= 20; shift += 4)
+		n += le_run_window((aa >> shift) & 0xfffu) ? 1u : 0u;
+	return n;
+}
+
+__host__ __device__ inline uint32_t le_reverse24(uint32_t x)
+{
+	uint32_t r = 0;
+	for (int i = 0; i < 24; i++)
+		r |= ((x >> i) & 1u) << (23 - i);
+	return r;
+}
+
+// one thread per hit (hits are rare next to the offsets scanned).  LDS: the byte-wise CRC table of the reflected register
+// (state >>= 8 ^ T[(state ^ octet) & 0xff]) and the whitening register advanced eight bits at a time (127-state LFSR:
+// the eight output bits and the next state of every state).
+__global__ __launch_bounds__(256) void le_decode_kernel(const uint64_t *words, uint64_t n_words, uint64_t pitch_words,
+							const btbbx_hit *hits, const uint32_t *d_count, uint32_t cap,
+							const uint16_t *phys, uint32_t crc_init_reflected, btbbx_le_pkt *out)
+{
+	__shared__ uint32_t crc_tab[256];
+	__shared__ uint16_t wh_tab[128];                    // low byte: eight whitening bits; high byte: the next state
+	const uint32_t tid = threadIdx.x;
+	{
+		uint32_t s = tid;
+		for (int k = 0; k < 8; k++)
+			s = (s >> 1) ^ ((s & 1u) ? 0xda6000u : 0u);   // x^24 + x^10 + x^9 + x^6 + x^4 + x^3 + x + 1, reflected
+		crc_tab[tid] = s;
+		if (tid < 128) {
+			uint32_t w = tid, o = 0;
+			for (int k = 0; k < 8; k++) {
+				o |= (w & 1u) << k;
+				if (w & 1u)
+					w ^= 0x88u;
+				w >>= 1;
+			}
+			wh_tab[tid] = (uint16_t)(o | (w << 8));
+		}
+	}
+	__syncthreads();
+	const uint32_t n = min(*d_count, cap);
+	const uint32_t i = blockIdx.x * 256u + tid;
+	if (i >= n)
+		return;
+	const btbbx_hit h = hits[i];
+	const uint64_t *w = words + (uint64_t)h.stream * pitch_words;
+	auto octet = [&](uint64_t bit) -> uint32_t {       // eight stream bits from `bit`, zeros past the stream's end
+		const uint64_t wi = bit >> 6;
+		const uint32_t sh = (uint32_t)(bit & 63);
+		const uint64_t lo = wi < n_words ? w[wi] : 0;
+		const uint64_t hi = sh > 56 && wi + 1 < n_words ? w[wi + 1] : 0;
+		return (uint32_t)(((lo >> sh) | (sh ? hi << (64 - sh) : 0)) & 0xffu);
+	};
+	const uint16_t mhz = phys[h.stream];
+	const uint8_t ch_idx = le_channel_index(mhz);
+	const uint8_t ch_k = (uint8_t)(((int)mhz - 2402) / 2);
+	uint32_t ws = (ch_idx & 0x3fu) | 0x40u;            // whitening register: position 0 = 1, positions 1..6 = channel index
+	uint32_t crc = crc_init_reflected;
+	const uint64_t pdu_bit = h.offset + 40;
+	uint32_t *ob = reinterpret_cast<uint32_t *>(out[i].bytes);
+	ob[0] = h.lap;
+	// header
+	uint32_t wt = wh_tab[ws];
+	const uint32_t h0 = octet(pdu_bit) ^ (wt & 0xffu);
+	ws = wt >> 8;
+	wt = wh_tab[ws];
+	const uint32_t h1 = octet(pdu_bit + 8) ^ (wt & 0xffu);
+	ws = wt >> 8;
+	const uint32_t pdu = 2 + h1;
+	crc = (crc >> 8) ^ crc_tab[(crc ^ h0) & 0xffu];
+	crc = (crc >> 8) ^ crc_tab[(crc ^ h1) & 0xffu];
+	uint32_t acc = h0 | (h1 << 8), crc_rx = 0;
+	uint32_t dw = 1;                                    // next dword of `bytes` to store
+	for (uint32_t k = 2; k < pdu + 3; k++) {
+		wt = wh_tab[ws];
+		const uint32_t d = octet(pdu_bit + 8ull * k) ^ (wt & 0xffu);
+		ws = wt >> 8;
+		if (k < pdu)
+			crc = (crc >> 8) ^ crc_tab[(crc ^ d) & 0xffu];
+		else
+			crc_rx |= d << (8 * (k - pdu));
+		if (dw < 16) {
+			acc |= d << (8 * (k & 3));
+			if ((k & 3) == 3) {
+				ob[dw++] = acc;
+				acc = 0;
+			}
+		}
+	}
+	if (dw < 16 && ((pdu + 3) & 3))
+		ob[dw++] = acc;
+	while (dw < 16)
+		ob[dw++] = 0;
+	ob[16] = 0;                                         // (the record's tail padding: records are compared as bytes)
+	const uint64_t end_bit = pdu_bit + 8ull * (pdu + 3);
+	const bool truncated = end_bit > n_words * 64;
+	btbbx_le_pkt &o = out[i];
+	o.offset = h.offset;
+	o.stream = h.stream;
+	o.aa_errors = h.ac_errors;
+	o.crc_rx = crc_rx;
+	o.crc_calc = crc;
+	o.crc_ok = (!truncated && crc == crc_rx) ? 1 : 0;
+	o.pdu_bytes = (uint16_t)pdu;
+	o.truncated = truncated ? 1 : 0;
+	o.channel_idx = ch_idx;
+	o.channel_k = ch_k;
+	const bool data = ch_idx < 37;
+	o.is_data = data ? 1 : 0;
+	o.access_address = h.lap;
+	if (data) {
+		o.length = (uint8_t)(h1 & 0x1f);
+		o.adv_type = o.adv_tx_add = o.adv_rx_add = 0;
+		const uint32_t off = le_data_offenses(h.lap);
+		o.access_address_offenses = (uint8_t)off;
+		o.access_address_ok = off ? 0 : 1;
+	} else {
+		o.length = (uint8_t)(h1 & 0x3f);
+		o.adv_type = (uint8_t)(h0 & 0xf);
+		o.adv_tx_add = (h0 & 0x40) ? 1 : 0;
+		o.adv_rx_add = (h0 & 0x80) ? 1 : 0;
+		const bool ok = h.lap == BTBBX_LE_ADV_AA;
+		o.access_address_ok = ok ? 1 : 0;
+		o.access_address_offenses = ok ? 0 : (__builtin_popcount(h.lap ^ BTBBX_LE_ADV_AA) == 1 ? 1 : 32);
+	}
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------
+
+static_assert(sizeof(btbbx_le_pkt) == 104, "btbbx_le_pkt: 104 bytes (libbtbb_amd LE_PKT_DTYPE)");
+static_assert(offsetof(btbbx_le_pkt, stream) == 8 && offsetof(btbbx_le_pkt, aa_errors) == 10 && offsetof(btbbx_le_pkt, crc_ok) == 11,
+	      "btbbx_le_pkt layout");
+static_assert(offsetof(btbbx_le_pkt, crc_rx) == 12 && offsetof(btbbx_le_pkt, crc_calc) == 16 && offsetof(btbbx_le_pkt, pdu_bytes) == 20 &&
+	      offsetof(btbbx_le_pkt, truncated) == 22 && offsetof(btbbx_le_pkt, channel_idx) == 23, "btbbx_le_pkt layout");
+static_assert(offsetof(btbbx_le_pkt, access_address_offenses) == 31 && offsetof(btbbx_le_pkt, access_address) == 32 &&
+	      offsetof(btbbx_le_pkt, bytes) == 36, "btbbx_le_pkt layout");
+
+static int le_check_args(const char *who, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, uint64_t search_bits,
+			 int max_errors)
+{
+	if (max_errors < 0 || max_errors > BTBBX_LE_MAX_ERRORS) {
+		set_error("%s: max_errors must be 0..%d", who, BTBBX_LE_MAX_ERRORS);
+		return BTBBX_E_ARG;
+	}
+	if (n_streams == 0 || n_streams > 65535) {
+		set_error("%s: n_streams must be 1..65535", who);
+		return BTBBX_E_ARG;
+	}
+	if (n_streams > 1 && pitch_words < n_words) {
+		set_error("%s: pitch_words < n_words", who);
+		return BTBBX_E_ARG;
+	}
+	if (n_words > (1ull << 40) || search_bits + 39 > n_words * 64) {
+		set_error("%s: search_bits + 39 exceeds the stream (%llu bits)", who, (unsigned long long)(n_words * 64));
+		return BTBBX_E_ARG;
+	}
+	return BTBBX_OK;
+}
+
+static int le_launch_scan(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, uint64_t search_bits,
+			  uint32_t aa, int max_errors, btbbx_hit *d_hits, uint32_t hit_cap, uint32_t *d_hit_count, hipStream_t q)
+{
+	if (search_bits == 0)
+		return BTBBX_OK;
+	if ((uintptr_t)d_hits & 15) {
+		set_error("btbbx_le_scan_device: the hit buffer must be 16-byte aligned");
+		return BTBBX_E_ARG;
+	}
+	LeScanArgs a;
+	a.words = d_words;
+	a.n_words = n_words;
+	a.pitch_words = n_streams > 1 ? pitch_words : n_words;
+	a.search_bits = search_bits;
+	a.n_streams = n_streams;
+	a.pat_lo = ((aa & 1u) ? 0x55u : 0xaau) | (aa << 8);
+	a.pat_hi = aa >> 24;
+	a.max_err = max_errors;
+	a.hits = d_hits;
+	a.hit_cap = hit_cap;
+	a.hit_count = d_hit_count;
+	const uint64_t search_words = (search_bits + 63) / 64;
+	const uint64_t tps = (search_words + LE_TILE_WORDS - 1) / LE_TILE_WORDS;
+	const uint64_t n_tiles = tps * n_streams;
+	{	// tile t is full iff (t + 1) * 512 + 1 <= n_words and (t + 1) * 512 * 64 <= search_bits
+		const uint64_t by_words = n_words ? (n_words - 1) / LE_TILE_WORDS : 0, by_bits = search_bits / (LE_TILE_WORDS * 64ull);
+		const uint64_t full = std::min(by_words, by_bits);
+		a.full_tiles = full > 0xffffffffull ? 0xffffffffu : (uint32_t)full;
+	}
+	const uint64_t grid = std::min<uint64_t>(n_tiles, (uint64_t)ctx().num_cus * 8);
+	if (tps + grid >= (1ull << 32)) {
+		set_error("btbbx_le_scan_device: stream too long for one launch (split it)");
+		return BTBBX_E_ARG;
+	}
+	a.tiles_per_stream = (uint32_t)tps;
+	const bool adv = aa == BTBBX_LE_ADV_AA;
+	// the advertising AA's sixteen filter bits (preamble 0xaa, AA octet 0x8e) folded into the adders; any other AA: XORs
+	constexpr int ADV_PAT = 0xaa | (0x8e << 8);
+#define LE_LAUNCH(P, L) hipLaunchKernelGGL((le_scan_kernel<P, L>), dim3((uint32_t)grid), dim3(LE_THREADS), 0, q, a)
+#define LE_LAUNCH_L(L) do { if (adv) LE_LAUNCH(ADV_PAT, L); else LE_LAUNCH(-1, L); } while (0)
+	switch (max_errors) {
+	case 0: LE_LAUNCH_L(0); break;
+	case 1: LE_LAUNCH_L(1); break;
+	case 2: LE_LAUNCH_L(2); break;
+	case 3: LE_LAUNCH_L(3); break;
+	default: LE_LAUNCH_L(4); break;
+	}
+#undef LE_LAUNCH_L
+#undef LE_LAUNCH
+	HIP_TRY(hipGetLastError());
+	return BTBBX_OK;
+}
+
+extern "C" int btbbx_le_scan_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				    uint64_t search_bits, uint32_t aa, int max_errors,
+				    btbbx_hit *d_hits, uint32_t hit_cap, uint32_t *d_hit_count, void *hip_stream)
+{
+	int rc = le_check_args("btbbx_le_scan_device", n_words, pitch_words, n_streams, search_bits, max_errors);
+	if (rc)
+		return rc;
+	if (!d_words || !d_hit_count || (!d_hits && hit_cap)) {
+		set_error("btbbx_le_scan_device: null pointer");
+		return BTBBX_E_ARG;
+	}
+	rc = ctx_require();
+	if (rc)
+		return rc;
+	return le_launch_scan(d_words, n_words, pitch_words, n_streams, search_bits, aa, max_errors, d_hits, hit_cap, d_hit_count,
+			      (hipStream_t)hip_stream);
+}
+
+extern "C" int btbbx_le_decode_hits_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words,
+					   const btbbx_hit *d_hits, const uint32_t *d_count, uint32_t cap,
+					   const uint16_t *d_phys_channel, uint32_t crc_init,
+					   btbbx_le_pkt *d_out, void *hip_stream)
+{
+	if (cap && (!d_words || !d_hits || !d_count || !d_phys_channel || !d_out)) {
+		set_error("btbbx_le_decode_hits_device: null pointer");
+		return BTBBX_E_ARG;
+	}
+	int rc = ctx_require();
+	if (rc)
+		return rc;
+	if (cap == 0)
+		return BTBBX_OK;
+	hipLaunchKernelGGL(le_decode_kernel, dim3((cap + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream, d_words, n_words, pitch_words,
+			   d_hits, d_count, cap, d_phys_channel, le_reverse24(crc_init & 0xffffffu), d_out);
+	HIP_TRY(hipGetLastError());
+	return BTBBX_OK;
+}
+
+extern "C" int64_t btbbx_le_scan_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				      uint64_t search_bits, const uint16_t *phys_channel, uint32_t aa, uint32_t crc_init,
+				      int max_errors, btbbx_le_pkt *pkts, uint64_t cap)
+{
+	int rc = le_check_args("btbbx_le_scan_host", n_words, pitch_words, n_streams, search_bits, max_errors);
+	if (rc)
+		return rc;
+	if (!words || !phys_channel || (!pkts && cap)) {
+		set_error("btbbx_le_scan_host: null pointer");
+		return BTBBX_E_ARG;
+	}
+	rc = ctx_require();
+	if (rc)
+		return rc;
+	if (n_streams == 1)
+		pitch_words = n_words;
+	CallScope scope;
+	hipStream_t q = scope_stream();
+	// the capture (+ one word of slack) and the channel list in one block of the call's device scratch
+	const uint64_t cap_words = (uint64_t)(n_streams - 1) * pitch_words + n_words;
+	const size_t words_bytes = ((size_t)(cap_words + 1) * 8 + 255) & ~(size_t)255;
+	char *dblock = (char *)scope_device(words_bytes + 2 * (size_t)n_streams);
+	if (!dblock)
+		return BTBBX_E_NOMEM;
+	const uint64_t *d_words = (const uint64_t *)dblock;
+	uint16_t *d_phys = (uint16_t *)(dblock + words_bytes);
+	HIP_TRY(hipMemcpyAsync(dblock, words, (size_t)cap_words * 8, hipMemcpyHostToDevice, q));
+	HIP_TRY(hipMemcpyAsync(d_phys, phys_channel, 2 * (size_t)n_streams, hipMemcpyHostToDevice, q));
+	// first guess: what the caller can take, but no more than one hit per 1024 offsets + slack; repeated with room for
+	// every match when more were found (the records kept by a full buffer are whichever waves came first)
+	uint64_t guess = search_bits / 1024 * n_streams + 4096;
+	if (guess > cap)
+		guess = cap;
+	uint32_t dev_cap = guess > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)guess;
+	uint32_t count = 0;
+	char *block = nullptr;
+	size_t rec_bytes = 0, order_bytes = 0;
+	for (int pass = 0; pass < 2; pass++) {
+		rec_bytes = ((size_t)dev_cap * sizeof(btbbx_hit) + 255) & ~(size_t)255;
+		order_bytes = dev_cap >= 2 ? (btbbx_order_hits_scratch_bytes(dev_cap) + 255) & ~(size_t)255 : 0;
+		const size_t pkt_bytes = (size_t)dev_cap * sizeof(btbbx_le_pkt);
+		block = (char *)scope_hits(256 + rec_bytes + order_bytes + pkt_bytes);
+		if (!block)
+			return BTBBX_E_NOMEM;
+		uint32_t *d_count = (uint32_t *)block;
+		HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(uint32_t), q));
+		rc = le_launch_scan(d_words, n_words, pitch_words, n_streams, search_bits, aa, max_errors, (btbbx_hit *)(block + 256), dev_cap,
+				    d_count, q);
+		if (rc)
+			return rc;
+		HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, q));
+		HIP_TRY(hipStreamSynchronize(q));
+		if (count <= dev_cap || cap == 0)
+			break;
+		dev_cap = count;
+	}
+	const uint32_t have = std::min(count, dev_cap);
+	if (have) {
+		uint32_t *d_count = (uint32_t *)block;
+		btbbx_hit *d_hits = (btbbx_hit *)(block + 256);
+		btbbx_le_pkt *d_pkts = (btbbx_le_pkt *)(block + 256 + rec_bytes + order_bytes);
+		if (have >= 2) {
+			rc = btbbx_order_hits_device(d_hits, d_count, dev_cap, block + 256 + rec_bytes, order_bytes, q);
+			if (rc)
+				return rc;
+		}
+		const uint32_t n = (uint32_t)std::min<uint64_t>(have, cap);
+		rc = btbbx_le_decode_hits_device(d_words, n_words, pitch_words, d_hits, d_count, n, d_phys, crc_init, d_pkts, q);
+		if (rc)
+			return rc;
+		HIP_TRY(hipMemcpyAsync(pkts, d_pkts, (size_t)n * sizeof(btbbx_le_pkt), hipMemcpyDeviceToHost, q));
+		HIP_TRY(hipStreamSynchronize(q));
+	}
+	return (int64_t)count;
+}
