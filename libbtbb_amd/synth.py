@@ -162,10 +162,10 @@ def access_code(lap, trailer=True):
     return bits
 
 
-def header_bits(lt_addr, ptype, flags, uap, clk6):
+def header_bits(lt_addr, ptype, flags, uap, clk6, whitened=True):
     data = (lt_addr & 7) | (ptype & 0xF) << 3 | (flags & 7) << 7
     h = np.concatenate([bits_lsb(data, 10), bits_lsb(hec(data, uap), 8)])
-    return fec13(h ^ whitening(clk6, 0, 18))
+    return fec13(h ^ whitening(clk6, 0, 18) if whitened else h)
 
 
 def fhs_payload(lap, uap, nap, clk27_2, rng=None):
@@ -181,16 +181,19 @@ def fhs_payload(lap, uap, nap, clk27_2, rng=None):
 
 
 def build_packet(lap, uap=0, clk6=0, ptype=None, lt_addr=1, flags=0, body=b"", llid=2, flow=1,
-                 voice=None, fhs_bits=None):
+                 voice=None, fhs_bits=None, whitened=True):
     """Air-order symbols (one 0/1 byte each), index 0 = first sync-word bit.
 
     ptype None -> ID packet (64 symbols).  `body` = user payload bytes (no payload header,
     no CRC).  For HV1/2/3 `body` is the 10/20/30 voice bytes; for DV `voice` is the 10 voice
-    bytes and `body` the data field; for EV3/4/5 body is payload, CRC appended.
+    bytes and `body` the data field; for EV4/5 body is payload, CRC appended (type 7 is
+    built as HV3: `body` goes on air as it is).  whitened=False sends header and payload
+    without the whitening sequence (a receiver then clears the packet's WHITENED flag).
     """
     if ptype is None:
         return access_code(lap, trailer=False)
-    parts = [access_code(lap), header_bits(lt_addr, ptype, flags, uap, clk6)]
+    wh = (lambda skip, n: whitening(clk6, skip, n)) if whitened else (lambda skip, n: np.zeros(n, np.uint8))
+    parts = [access_code(lap), header_bits(lt_addr, ptype, flags, uap, clk6, whitened)]
     skip = 18
     pl = None
     if ptype in (TYPE_NULL, TYPE_POLL):
@@ -222,9 +225,9 @@ def build_packet(lap, uap=0, clk6=0, ptype=None, lt_addr=1, flags=0, body=b"", l
         assert len(v) == 80
         # the reference decodes the data field with whitening index 18 straight after the
         # header (bluetooth_packet.c:913-916, 937): the voice field is whitened separately
-        parts.append(v ^ whitening(clk6, skip, 80))
+        parts.append(v ^ wh(skip, 80))
     if pl is not None:
-        w = pl ^ whitening(clk6, skip, len(pl))
+        w = pl ^ wh(skip, len(pl))
         if ptype in _FEC23_TYPES:
             w = fec23(w)
         elif ptype == TYPE_HV1:

@@ -890,6 +890,28 @@ int orc_decode(orc_packet *p)
 	return rv;
 }
 
+void orc_trial_table(const char *syms, int length, uint32_t flags, uint8_t uap, uint8_t type,
+		     uint8_t llid, uint8_t flow, uint32_t *out)
+{
+	orc_packet *p = orc_packet_new();
+	int clock;
+	orc_packet_init_found(p, 0, 0);
+	orc_packet_set_data(p, syms, length, 0, 0);
+	p->flags = flags;
+	p->payload_llid = llid;
+	p->payload_flow = flow;
+	for (clock = 0; clock < 64; clock++) {
+		uint8_t u;
+		int rv;
+		p->packet_type = type;
+		p->UAP = uap;
+		u = orc_try_clock(clock, p);
+		rv = orc_crc_check(clock, p);
+		out[clock] = (uint32_t)u | (uint32_t)p->packet_type << 8 | (uint32_t)(uint16_t)rv << 16;
+	}
+	orc_packet_free(p);
+}
+
 /* bluetooth_packet.c:1411-1441 */
 uint32_t orc_lap_from_fhs(const orc_packet *p) { return (uint32_t)air_bits(p->payload + 34, 24); }
 uint8_t orc_uap_from_fhs(const orc_packet *p) { return (uint8_t)air_bits(p->payload + 64, 8); }

@@ -140,6 +140,12 @@ int orc_crc_check(int clock, orc_packet *p);      /* :708 */
 int orc_decode_header(orc_packet *p);             /* :1198 */
 int orc_decode_payload(orc_packet *p);            /* :1223 */
 int orc_decode(orc_packet *p);                    /* :1300 (silent) */
+/* The 64-clock brute force of one packet from one entry state: for clock 0..63 the entry's
+ * packet_type / UAP are put back, then try_clock and crc_check run on the same packet object
+ * (whatever else a trial writes stays for the next, as in the reference's own loops).
+ * out[c] = try_clock's return | packet_type << 8 | (uint16_t)crc_check's return << 16. */
+void orc_trial_table(const char *syms, int length, uint32_t flags, uint8_t uap, uint8_t type,
+		     uint8_t llid, uint8_t flow, uint32_t *out);
 int orc_fhs(int clock, orc_packet *p);
 int orc_DM(int clock, orc_packet *p);
 int orc_DH(int clock, orc_packet *p);

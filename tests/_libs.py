@@ -102,6 +102,8 @@ def oracle():
         "orc_decode_header": (C.c_int, [P]),
         "orc_decode_payload": (C.c_int, [P]),
         "orc_decode": (C.c_int, [P]),
+        "orc_trial_table": (None, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint8, C.c_uint8, C.c_uint8, C.c_uint8,
+                                C.c_void_p]),
         "orc_piconet_new": (N, []),
         "orc_piconet_free": (None, [N]),
         "orc_init_piconet": (None, [N, C.c_uint32]),
