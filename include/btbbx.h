@@ -24,6 +24,8 @@
  *                        lib/src/bluetooth_piconet.c:311-362, 443-446, 455-498, 575-645
  *   btbbx_le_*        <- the LE search in front of lell_allocate_and_decode (the reference
  *                        expects found, dewhitened bytes), lib/src/bluetooth_le_packet.c:282-312
+ *   btbbx_survey_*    <- btbb_uap_from_header under the survey mode of btbb_process_packet,
+ *                        lib/src/bluetooth_piconet.c:648-750, 807-858
  */
 #ifndef INCLUDED_BTBBX_H
 #define INCLUDED_BTBBX_H
@@ -320,6 +322,67 @@ int btbbx_decode_hits_piconet_phase_device(const uint64_t *d_words, uint64_t n_w
 					   const btbbx_hit *d_hits, const uint32_t *d_count, uint32_t cap,
 					   const btbbx_pkt_in *entry, uint32_t clk_div, uint32_t clk_phase, uint32_t max_length,
 					   btbbx_pkt_out *d_out, uint32_t *d_lengths, void *hip_stream);
+
+/* ---- piconet survey: UAP and CLK1-6 for every LAP of a hit list -------------------------------- */
+/* What the reference's survey mode (btbb_init_survey / btbb_process_packet / btbb_next_survey_result,
+ * bluetooth_piconet.c:807-858) leaves in one piconet after it has seen every packet of a list.  The packets of a LAP
+ * are taken in ascending (offset, stream), whatever the order of the list; for each one, on a piconet that starts as
+ * btbb_piconet_new + btbb_init_piconet(lap) leave it,
+ *     btbb_piconet_set_channel_seen(pn, channel);
+ *     if (btbb_header_present(pkt) && !flag(pn, BTBB_UAP_VALID)) btbb_uap_from_header(pkt, pn);
+ * with every branch of btbb_uap_from_header (:648-750): the walk over 64 or the live candidates, the first CRC success
+ * ending it (candidates above it keep their value), settling by elimination, the reset when none is left and the reset
+ * after MAX_PATTERN_LENGTH packets.  What the reference prints is in the record instead. */
+typedef struct btbbx_survey_rec {      /* 64 bytes */
+	uint32_t lap;
+	uint32_t flags;                  /* piconet flags as the reference leaves them (LAP_VALID, GOT_FIRST_PACKET, UAP_VALID, CLK6_VALID) */
+	uint8_t  uap, clk_offset, used_channels;
+	uint8_t  settled_by;             /* 0 not settled, 1 elimination ("UAP = ..."), 2 CRC ("Correct CRC! ...") */
+	uint8_t  afh_map[10];            /* channels seen, over ALL packets of the LAP */
+	uint16_t first_stream;           /* first packet of the LAP in time order: its stream ... */
+	uint32_t n_packets;              /* hits with this LAP */
+	uint32_t n_walked;               /* calls of btbb_uap_from_header the loop above makes */
+	uint32_t n_resets;               /* remaining == 0 resets + "Oops" resets */
+	uint32_t settled_after;          /* total_packets_observed as the reference prints it, 0 if not settled */
+	uint32_t settled_hit;            /* index into d_hits of the settling packet, UINT32_MAX if none */
+	int32_t  packets_observed, total_packets_observed;
+	uint32_t first_pkt_time;
+	uint64_t first_offset;           /* ... and its offset */
+} btbbx_survey_rec;
+
+/* Device scratch the survey of a list of up to cap hits needs (about 760 bytes per hit: sort keys, the gathered packets and
+ * their 64-clock trial tables).  Host only, no device needed. */
+size_t btbbx_survey_scratch_bytes(uint32_t cap);
+/* Surveys the first min(*d_count, cap) records of d_hits (d_count may be NULL: then cap records), in any order.  A packet is a
+ * hit: LAP = hit.lap (24 bits), channel = channels[hit.stream] (the stream index when channels is NULL), clock
+ * entry->clkn + (offset + clk_phase) / clk_div as in btbbx_decode_hits_piconet_phase_device (uint32_t arithmetic), symbols and
+ * captured length as btbbx_gather_packets_device cuts them out with the same max_length, entry state *entry.  channels and entry
+ * are HOST pointers; a channel table covers at most 256 streams.  The list must come from a scan of the same geometry:
+ * offsets below 64 * n_words <= 2^40, streams below n_streams.  (A hit outside it is not a fault -- it is surveyed as an empty
+ * packet that marks no channel -- but where it falls among the packets of its LAP, and so first_offset / first_stream of that
+ * record, is unspecified.)  The gather, trial and walk stages work on the list's length, not on cap; scratch and launch sizes
+ * follow cap.
+ * Records come in ASCENDING LAP order -- btbb_next_survey_result hands piconets out in order of first appearance; sort by
+ * (first_offset, first_stream) to restore that.  *d_rec_count counts all piconets; when it exceeds rec_cap the rec_cap smallest
+ * LAPs are stored.  d_candidates (may be NULL) receives the 64 clock6_candidates of every stored record.  d_scratch:
+ * btbbx_survey_scratch_bytes(cap) bytes, 16-byte aligned, owned by the caller.  Asynchronous on hip_stream, no host round trip.
+ * BTBBX_E_ARG before any launch for: a channel above 78, more than 79 streams without a channel table, clk_div = 0,
+ * clk_phase >= clk_div, scratch too small, misaligned pointers. */
+int btbbx_survey_hits_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			     const btbbx_hit *d_hits, const uint32_t *d_count, uint32_t cap,
+			     const uint8_t *channels, const btbbx_pkt_in *entry, uint32_t clk_div, uint32_t clk_phase, uint32_t max_length,
+			     btbbx_survey_rec *d_recs, uint32_t rec_cap, uint32_t *d_rec_count, int16_t *d_candidates,
+			     void *d_scratch, size_t scratch_bytes, void *hip_stream);
+/* Host wrapper: copy in, btbbx_scan_ordered_device with LAP_ANY (repeated with room for every match when its first buffer was
+ * too small, as btbbx_scan_host does), survey with scratch sized from the number of hits found, copy out.  Every packet enters as btbb_find_ac +
+ * btbb_packet_set_data leave it (BTBB_WHITENED set, nothing else known), with the stored clock (CLK1-27, what
+ * btbb_packet_set_data keeps of its clkn argument) clkn0 + (offset + clk_phase) / clk_div.  Returns the number of piconets
+ * or a negative BTBBX_E_*; when that exceeds rec_cap the rec_cap smallest LAPs are returned.  candidates may be NULL.
+ * Safe to call from several host threads at once. */
+int64_t btbbx_survey_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			  uint64_t search_bits, int max_ac_errors, const uint8_t *channels,
+			  uint32_t clkn0, uint32_t clk_div, uint32_t clk_phase,
+			  btbbx_survey_rec *recs, uint64_t rec_cap, int16_t *candidates);
 
 /* ---- Bluetooth LE 1M scan (Core v5.x Vol 6 Part B 2.1, 3.1.1, 3.2) ------------------------- */
 /* Finds preamble + access address (AA) in demodulated LE captures (packed streams as above, one per RF channel),

@@ -89,6 +89,14 @@ LE_PKT_DTYPE = np.dtype([("offset", "<u8"), ("stream", "<u2"), ("aa_errors", "u1
                          ("pad", "u1", (4,))])
 assert LE_PKT_DTYPE.itemsize == 104 and LE_PKT_DTYPE.fields["bytes"][1] == 36
 
+# one surveyed piconet (include/btbbx.h btbbx_survey_rec; survey.hip checks the C layout with static_asserts)
+SURVEY_DTYPE = np.dtype([("lap", "<u4"), ("flags", "<u4"), ("uap", "u1"), ("clk_offset", "u1"), ("used_channels", "u1"),
+                         ("settled_by", "u1"), ("afh_map", "u1", (10,)), ("first_stream", "<u2"), ("n_packets", "<u4"),
+                         ("n_walked", "<u4"), ("n_resets", "<u4"), ("settled_after", "<u4"), ("settled_hit", "<u4"),
+                         ("packets_observed", "<i4"), ("total_packets_observed", "<i4"), ("first_pkt_time", "<u4"),
+                         ("first_offset", "<u8")])
+assert SURVEY_DTYPE.itemsize == 64 and SURVEY_DTYPE.fields["first_offset"][1] == 56
+
 _vp, _u64, _u32 = C.c_void_p, C.c_uint64, C.c_uint32
 
 # every symbol include/btbbx.h and include/btbb.h declare: (restype, argtypes)
@@ -154,6 +162,10 @@ SIGNATURES = {
     "btbbx_le_scan_device": (C.c_int, [_vp, _u64, _u64, _u32, _u64, _u32, C.c_int, _vp, _u32, _vp, _vp]),
     "btbbx_le_decode_hits_device": (C.c_int, [_vp, _u64, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp]),
     "btbbx_le_scan_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, C.c_int, _vp, _u64]),
+    "btbbx_survey_scratch_bytes": (C.c_size_t, [_u32]),
+    "btbbx_survey_hits_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp,
+                                           _vp, C.c_size_t, _vp]),
+    "btbbx_survey_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, C.c_int, _vp, _u32, _u32, _u32, _vp, _u64, _vp]),
     # ---- btbb.h
     "btbb_init": (C.c_int, [C.c_int]),
     "btbb_get_release": (C.c_char_p, []),
@@ -483,6 +495,78 @@ def run_decode_hits(stream_words, hits, pkt_in, max_length=MAX_SYMBOLS, via_gath
         for b in (d_w, d_h, d_out, d_len, d_in, d_pk):
             if b is not None:
                 b.free()
+
+
+def _channel_table(channels, n_streams):
+    if channels is None:
+        return None
+    t = np.ascontiguousarray(channels, dtype=np.uint8)
+    assert len(t) == n_streams
+    return t
+
+
+def survey(words, search_bits, n_streams=1, pitch_words=None, channels=None, clkn0=0, clk_div=625, clk_phase=0,
+           max_ac_errors=2, rec_cap=1 << 20, candidates=False, n_words=None):
+    """Every piconet of a capture held in host memory (btbbx_survey_host): scan with LAP_ANY, then UAP / CLK1-6 discovery per
+    LAP as the reference's survey mode runs it.  words is (n_streams, pitch_words) or flat; channels = the BR/EDR channel of
+    every stream (the stream index when None).  Returns SURVEY_DTYPE records in ascending LAP order -- and, with
+    candidates=True, the (n, 64) int16 clock6_candidates as well."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if pitch_words is None:
+        pitch_words = len(words) // n_streams
+    if n_words is None:
+        n_words = pitch_words
+    assert n_words <= pitch_words and (n_streams - 1) * pitch_words + n_words <= len(words)
+    table = _channel_table(channels, n_streams)
+    recs = np.zeros(max(rec_cap, 1), dtype=SURVEY_DTYPE)
+    cand = np.zeros((max(rec_cap, 1), 64), dtype=np.int16) if candidates else None
+    n = check(lib().btbbx_survey_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, max_ac_errors,
+                                      None if table is None else _ptr(table), clkn0, clk_div, clk_phase, _ptr(recs), rec_cap,
+                                      None if cand is None else _ptr(cand)), "btbbx_survey_host")
+    k = min(n, rec_cap)
+    return (recs[:k], cand[:k]) if candidates else recs[:k]
+
+
+def run_survey_hits(stream_words, hits, entry, channels=None, clk_div=625, clk_phase=0, max_length=MAX_SYMBOLS, count=None,
+                    cap=None, rec_cap=None, candidates=True, pitch_words=None, n_words=None):
+    """btbbx_survey_hits_device over `hits` (HIT_DTYPE, any order) of the packed streams stream_words[n_streams, pitch_words]
+    -> (piconet count, SURVEY_DTYPE records, (n, 64) int16 candidates or None).  entry: one PKTIN_DTYPE record; count: the
+    list's length as a word in HBM (None: a NULL d_count); cap / rec_cap default to len(hits)."""
+    stream_words = np.ascontiguousarray(stream_words, dtype=np.uint64)
+    n_streams, pitch = stream_words.shape
+    pitch_words = pitch if pitch_words is None else pitch_words
+    n_words = pitch_words if n_words is None else n_words
+    cap = len(hits) if cap is None else cap
+    rec_cap = cap if rec_cap is None else rec_cap
+    table = _channel_table(channels, n_streams)
+    entry = np.ascontiguousarray(np.asarray(entry, dtype=PKTIN_DTYPE).reshape(1))
+    scratch_bytes = lib().btbbx_survey_scratch_bytes(cap)
+    bufs = []
+
+    def dev(nbytes):
+        bufs.append(DeviceBuffer(nbytes))
+        return bufs[-1]
+    try:
+        d_w = dev(stream_words.nbytes + 16).upload(stream_words)
+        d_h = dev(max(hits.nbytes, 16)).upload(np.ascontiguousarray(hits))
+        d_cnt = dev(8).upload(np.array([0 if count is None else count, 0], dtype=np.uint32))
+        d_recs = dev(max(rec_cap, 1) * SURVEY_DTYPE.itemsize).zero()
+        d_cand = dev(max(rec_cap, 1) * 128).zero() if candidates else None
+        d_nrec = dev(8).zero()
+        d_scr = dev(scratch_bytes)
+        check(lib().btbbx_survey_hits_device(d_w.ptr, n_words, pitch_words, n_streams, d_h.ptr, None if count is None else d_cnt.ptr,
+                                             cap, None if table is None else _ptr(table), _ptr(entry), clk_div, clk_phase,
+                                             max_length, d_recs.ptr, rec_cap, d_nrec.ptr, d_cand.ptr if candidates else None,
+                                             d_scr.ptr, scratch_bytes, None), "btbbx_survey_hits_device")
+        check(lib().btbbx_sync(None), "sync")
+        n = int(d_nrec.download(np.uint32, 2)[0])
+        k = min(n, rec_cap)
+        recs = d_recs.download(SURVEY_DTYPE, max(rec_cap, 1))[:k]
+        cand = d_cand.download(np.int16, max(rec_cap, 1) * 64).reshape(-1, 64)[:k] if candidates else None
+        return n, recs, cand
+    finally:
+        for b in bufs:
+            b.free()
 
 
 # ---- hop selection / CLK1-27 reversal -------------------------------------------------------

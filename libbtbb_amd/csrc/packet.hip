@@ -1070,8 +1070,10 @@ __device__ unsigned long long g_tl_prof[16];
 #endif
 #define TL_AFAIL(p) lds_now(&a_fail[p])
 __global__ __launch_bounds__(TL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void trials_linear_kernel(const uint64_t *packets, const btbbx_pkt_in *in,
-							     uint32_t n_packets, btbbx_trial *trials)
+							     uint32_t n_packets, btbbx_trial *trials, const uint32_t *d_count)
 {
+	if (d_count)                                        // the list's length lives in HBM: n_packets is its capacity
+		n_packets = min(n_packets, *d_count);
 	__shared__ uint64_t pk[TL_PACKETS][BTBBX_PKT_WORDS + 1];
 	__shared__ __attribute__((aligned(8))) btbbx_pkt_in pin[TL_PACKETS];
 	__shared__ uint32_t hdr_ut[TL_PACKETS];
@@ -1592,9 +1594,11 @@ __global__ __launch_bounds__(TL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
 // types, so the call takes as long as the longest single trial -- the lane-per-clock kernel above is
 // the throughput shape, this one the latency shape.
 __global__ __launch_bounds__(64) void trials_wide_kernel(const uint64_t *packets, const btbbx_pkt_in *in,
-							  uint32_t n_packets, btbbx_trial *trials)
+							  uint32_t n_packets, btbbx_trial *trials, const uint32_t *d_count)
 {
 	chain_lds_init();
+	if (d_count)
+		n_packets = min(n_packets, *d_count);
 	const uint32_t pkt = blockIdx.x >> 6, clock = blockIdx.x & 63;
 	if (threadIdx.x || pkt >= n_packets)
 		return;
@@ -3122,8 +3126,10 @@ size_t trials_state_bytes() { return 64 * sizeof(TrialState); }
 #define GATHER_PACKETS (256 / BTBBX_PKT_WORDS)
 __global__ __launch_bounds__(256) void gather_kernel(const uint64_t *words, uint64_t n_words, uint64_t pitch_words,
 						      const btbbx_hit *hits, uint32_t n_packets, uint32_t max_length,
-						      uint64_t *packets, uint32_t *lengths)
+						      uint64_t *packets, uint32_t *lengths, const uint32_t *d_count)
 {
+	if (d_count)
+		n_packets = min(n_packets, *d_count);
 	uint32_t pkt = blockIdx.x * GATHER_PACKETS + threadIdx.x / BTBBX_PKT_WORDS;
 	uint32_t i = threadIdx.x % BTBBX_PKT_WORDS;          // output word
 	if (pkt >= n_packets || threadIdx.x >= GATHER_PACKETS * BTBBX_PKT_WORDS)
@@ -3151,11 +3157,26 @@ __global__ __launch_bounds__(256) void gather_kernel(const uint64_t *words, uint
 		lengths[pkt] = len;
 }
 
-// ---- launchers --------------------------------------------------------------------------------
+// btbb_header_present of gathered packets, one byte each (the survey walks only packets that carry a header)
+__global__ __launch_bounds__(256) void header_flags_kernel(const uint64_t *packets, const uint32_t *lengths, uint32_t n_packets,
+							    uint8_t *present, const uint32_t *d_count)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n_packets || (d_count && i >= *d_count))
+		return;
+	PState s;
+	s.w = packets + (uint64_t)i * BTBBX_PKT_WORDS;
+	s.length = (int)lengths[i];
+	present[i] = (uint8_t)do_header_present(s);
+}
 
-extern "C" int btbbx_gather_packets_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words,
-					   const btbbx_hit *d_hits, uint32_t n_packets, uint32_t max_length,
-					   uint64_t *d_packets, uint32_t *d_lengths, void *hip_stream)
+// ---- launchers --------------------------------------------------------------------------------
+int launch_trials(const uint64_t *d_packets, const btbbx_pkt_in *d_in, uint32_t n_packets, const uint32_t *d_count,
+		  btbbx_trial *d_trials, hipStream_t hip_stream);
+
+// d_count (may be null): the number of packets as a word in HBM, n_packets then being the capacity the launch is sized for
+int launch_gather(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, const btbbx_hit *d_hits, uint32_t n_packets,
+		  const uint32_t *d_count, uint32_t max_length, uint64_t *d_packets, uint32_t *d_lengths, hipStream_t hip_stream)
 {
 	int rc = ctx_require();
 	if (rc)
@@ -3163,13 +3184,26 @@ extern "C" int btbbx_gather_packets_device(const uint64_t *d_words, uint64_t n_w
 	if (!n_packets)
 		return BTBBX_OK;
 	hipLaunchKernelGGL(gather_kernel, dim3((n_packets + GATHER_PACKETS - 1) / GATHER_PACKETS), dim3(256), 0,
-			   (hipStream_t)hip_stream, d_words, n_words, pitch_words, d_hits, n_packets, max_length, d_packets, d_lengths);
+			   hip_stream, d_words, n_words, pitch_words, d_hits, n_packets, max_length, d_packets, d_lengths, d_count);
 	HIP_TRY(hipGetLastError());
 	return BTBBX_OK;
 }
 
+extern "C" int btbbx_gather_packets_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words,
+					   const btbbx_hit *d_hits, uint32_t n_packets, uint32_t max_length,
+					   uint64_t *d_packets, uint32_t *d_lengths, void *hip_stream)
+{
+	return launch_gather(d_words, n_words, pitch_words, d_hits, n_packets, nullptr, max_length, d_packets, d_lengths, (hipStream_t)hip_stream);
+}
+
 extern "C" int btbbx_trials_device(const uint64_t *d_packets, const btbbx_pkt_in *d_in, uint32_t n_packets,
 				   btbbx_trial *d_trials, void *hip_stream)
+{
+	return launch_trials(d_packets, d_in, n_packets, nullptr, d_trials, (hipStream_t)hip_stream);
+}
+
+int launch_trials(const uint64_t *d_packets, const btbbx_pkt_in *d_in, uint32_t n_packets, const uint32_t *d_count,
+		  btbbx_trial *d_trials, hipStream_t hip_stream)
 {
 	int rc = ctx_require();
 	if (rc)
@@ -3178,12 +3212,12 @@ extern "C" int btbbx_trials_device(const uint64_t *d_packets, const btbbx_pkt_in
 		return BTBBX_OK;
 	if (n_packets <= 256) {      // latency shape while 64 n waves are only a few rounds over the chip
 		hipLaunchKernelGGL(trials_wide_kernel, dim3(n_packets * 64), dim3(64), 0, (hipStream_t)hip_stream,
-				   d_packets, d_in, n_packets, d_trials);
+				   d_packets, d_in, n_packets, d_trials, d_count);
 	} else {                     // per-packet FEC / CRC prefix work once, O(1) per DM / DH / FHS trial
 		const uint32_t batches = (n_packets + TL_PACKETS - 1) / TL_PACKETS;
 		const uint32_t resident = (uint32_t)ctx().num_cus * TL_WGS_PER_CU;
 		hipLaunchKernelGGL(trials_linear_kernel, dim3(batches < resident ? batches : resident), dim3(TL_THREADS), 0,
-				   (hipStream_t)hip_stream, d_packets, d_in, n_packets, d_trials);
+				   (hipStream_t)hip_stream, d_packets, d_in, n_packets, d_trials, d_count);
 	}
 #ifdef TL_PROFILE
 	if (n_packets > 256) {
@@ -3216,6 +3250,16 @@ extern "C" int btbbx_uap_table_device(const uint64_t *d_packets, const btbbx_pkt
 	}
 	hipLaunchKernelGGL(uap_table_kernel, dim3((n_packets + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream,
 			   d_packets, d_in, n_packets, (uint4 *)d_table);
+	HIP_TRY(hipGetLastError());
+	return BTBBX_OK;
+}
+
+int launch_header_flags(const uint64_t *d_packets, const uint32_t *d_lengths, uint32_t n_packets, const uint32_t *d_count,
+			uint8_t *d_present, hipStream_t stream)
+{
+	if (!n_packets)
+		return BTBBX_OK;
+	hipLaunchKernelGGL(header_flags_kernel, dim3((n_packets + 255) / 256), dim3(256), 0, stream, d_packets, d_lengths, n_packets, d_present, d_count);
 	HIP_TRY(hipGetLastError());
 	return BTBBX_OK;
 }

@@ -1,0 +1,801 @@
+// survey.hip -- batch piconet survey: UAP and CLK1-6 for every LAP of a hit list, on the device.
+//
+// What the reference's survey mode does one packet at a time (bluetooth_piconet.c:851-858 around
+// btbb_uap_from_header, :648-750) is done here for a whole ordered or unordered hit list:
+//
+//   1. survey_key_kernel .. survey_scatter_kernel   stable LSD radix sort of (LAP << 40 | offset, hit index), eight bits
+//      per pass, with the stream number as the least significant digit: the packets of a LAP end up in (offset, stream) order
+//   2. survey_mark_kernel / survey_tiles_kernel / survey_group_kernel   boundary flags and their compaction: one group per
+//      LAP with first index and count; the same pass lays out the sorted hit records and one btbbx_pkt_in per packet and ORs
+//      every packet's channel into its group's map (in parallel over the list, not by the group's wave)
+//   3. gather_kernel + trials kernels + header_flags_kernel (packet.hip)   the 64 {uap, type, rv} of every packet of the
+//      list (the kernels read the list's length on the device); survey_wmark / wtiles / wlist_kernel compact the indices of
+//      the header-bearing packets, so a walk never visits a packet it would skip
+//   4. survey_walk_kernel   one wave per piconet, lane c = candidate c: the elimination of classify_candidates
+//      (piconet.cpp) as ballots, candidates in a register for the life of the group
+//
+// Nothing here synchronises or reads back: the list's length stays in device memory.
+#include "common.h"
+#include <algorithm>
+#include <string.h>
+
+#define SV_THREADS     256
+#define SV_WAVES       (SV_THREADS / 64)
+#define SV_SORT_TILE   4096u               // keys a workgroup ranks per pass (16 rounds of 256)
+#define SV_GRP_TILE    2048u               // records a workgroup flags and lays out (8 rounds of 256)
+#define SV_BATCH       16                  // trial rows a walking wave keeps in flight
+#define SV_MAX_PATTERN 1000                // MAX_PATTERN_LENGTH, bluetooth_piconet.h
+#define SV_PAD_OFFSET  (1ULL << 62)        // a hit beyond every stream: gathers as an empty packet
+#define SV_CHAN_STREAMS 256u
+
+// piconet flags (include/btbb.h)
+#define SVF_UAP_VALID  (1u << 2)
+#define SVF_LAP_VALID  (1u << 3)
+#define SVF_CLK6_VALID (1u << 4)
+#define SVF_GOT_FIRST  (1u << 10)
+
+static_assert(sizeof(btbbx_survey_rec) == 64, "btbbx_survey_rec is 64 bytes");
+static_assert(offsetof(btbbx_survey_rec, afh_map) == 12 && offsetof(btbbx_survey_rec, first_stream) == 22 &&
+	      offsetof(btbbx_survey_rec, first_offset) == 56, "btbbx_survey_rec layout (libbtbb_amd.SURVEY_DTYPE)");
+
+// launchers of the packet chain's kernels (packet.hip)
+int launch_gather(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, const btbbx_hit *d_hits, uint32_t n_packets,
+		  const uint32_t *d_count, uint32_t max_length, uint64_t *d_packets, uint32_t *d_lengths, hipStream_t hip_stream);
+int launch_trials(const uint64_t *d_packets, const btbbx_pkt_in *d_in, uint32_t n_packets, const uint32_t *d_count,
+		  btbbx_trial *d_trials, hipStream_t hip_stream);
+int launch_header_flags(const uint64_t *d_packets, const uint32_t *d_lengths, uint32_t n_packets, const uint32_t *d_count,
+			uint8_t *d_present, hipStream_t stream);
+
+struct SurveyChannels {
+	uint8_t ch[SV_CHAN_STREAMS];           // channel of every stream
+};
+
+struct SurveyLayout {
+	size_t params, keys[2], vals[2], hist, tot, tiles, wtiles, gstart, wpos, widx, chan, hits, pin, packets, lengths, trials, present, total;
+	uint32_t sort_blocks, grp_tiles;
+};
+
+static size_t sv_up(size_t x) { return (x + 255) & ~(size_t)255; }
+
+static SurveyLayout survey_layout(uint32_t cap)
+{
+	SurveyLayout L;
+	const size_t c = cap ? cap : 1;
+	L.sort_blocks = (uint32_t)((c + SV_SORT_TILE - 1) / SV_SORT_TILE);
+	L.grp_tiles = (uint32_t)((c + SV_GRP_TILE - 1) / SV_GRP_TILE);
+	size_t at = 0;
+	auto take = [&](size_t bytes) { const size_t here = at; at += sv_up(bytes); return here; };
+	L.params = take(256);
+	L.keys[0] = take(c * 8);
+	L.keys[1] = take(c * 8);
+	L.vals[0] = take(c * 4);
+	L.vals[1] = take(c * 4);
+	L.hist = take((size_t)L.sort_blocks * 256 * 4);
+	L.tot = take(256 * 4);
+	L.tiles = take(((size_t)L.grp_tiles + 1) * 4);
+	L.wtiles = take(((size_t)L.grp_tiles + 1) * 4);
+	L.gstart = take((c + 1) * 4);
+	L.wpos = take((c + 1) * 4);
+	L.widx = take(c * 4);
+	L.chan = take(c * 16);
+	L.hits = take(c * sizeof(btbbx_hit));
+	L.pin = take(c * sizeof(btbbx_pkt_in));
+	L.packets = take(c * BTBBX_PKT_WORDS * 8);
+	L.lengths = take(c * 4);
+	L.trials = take(c * 64 * sizeof(btbbx_trial));
+	L.present = take(c);
+	L.total = at;
+	return L;
+}
+
+// ---- workgroup helpers ------------------------------------------------------------------------------
+
+// exclusive prefix sum over the 256 threads of a workgroup; lds: SV_WAVES words; ends with a barrier
+__device__ __forceinline__ uint32_t sv_block_scan(uint32_t v, uint32_t *lds, uint32_t &total)
+{
+	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	uint32_t inc = v;
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) {
+		const uint32_t up = __shfl_up(inc, d, 64);
+		if (lane >= (uint32_t)d)
+			inc += up;
+	}
+	if (lane == 63)
+		lds[wave] = inc;
+	__syncthreads();
+	uint32_t before = 0, sum = 0;
+#pragma unroll
+	for (uint32_t w = 0; w < SV_WAVES; w++) {
+		const uint32_t t = lds[w];
+		if (w < wave)
+			before += t;
+		sum += t;
+	}
+	total = sum;
+	__syncthreads();
+	return before + inc - v;
+}
+
+__device__ __forceinline__ uint32_t sv_lap_of(uint64_t key) { return (uint32_t)(key >> 40); }
+
+// ---- 1. ordering ------------------------------------------------------------------------------------
+
+// params[0] = records to process, keys and hit indices of the unsorted list
+__global__ __launch_bounds__(SV_THREADS) void survey_key_kernel(const btbbx_hit *hits, const uint32_t *d_count, uint32_t cap,
+								  uint32_t *params, uint64_t *keys, uint32_t *vals)
+{
+	uint32_t n = cap;
+	if (d_count) {
+		const uint32_t have = *d_count;
+		n = have < cap ? have : cap;
+	}
+	const uint32_t i = blockIdx.x * SV_THREADS + threadIdx.x;
+	if (i == 0)
+		params[0] = n;
+	if (i >= n)
+		return;
+	const btbbx_hit h = hits[i];
+	keys[i] = ((uint64_t)(h.lap & 0xffffffu) << 40) | (h.offset & 0xffffffffffULL);
+	vals[i] = i;
+}
+
+// digit of record i in this pass: eight bits of the key, or of the hit's stream number
+__device__ __forceinline__ uint32_t sv_digit(const uint64_t *keys, const uint32_t *vals, const btbbx_hit *hits, uint32_t i,
+					     int by_stream, uint32_t shift)
+{
+	if (by_stream)
+		return ((uint32_t)hits[vals[i]].stream >> shift) & 0xff;
+	return (uint32_t)(keys[i] >> shift) & 0xff;
+}
+
+// hist[d * n_blocks + b] = records of tile b with digit d
+__global__ __launch_bounds__(SV_THREADS) void survey_hist_kernel(const uint64_t *keys, const uint32_t *vals, const btbbx_hit *hits,
+								   const uint32_t *params, uint32_t n_blocks, int by_stream, uint32_t shift,
+								   uint32_t *hist)
+{
+	__shared__ uint32_t h[256];
+	const uint32_t tid = threadIdx.x, n = params[0];
+	h[tid] = 0;
+	__syncthreads();
+	const uint32_t base = blockIdx.x * SV_SORT_TILE;
+	for (uint32_t k = 0; k < SV_SORT_TILE / SV_THREADS; k++) {
+		const uint32_t i = base + k * SV_THREADS + tid;
+		if (i < n)
+			atomicAdd(&h[sv_digit(keys, vals, hits, i, by_stream, shift)], 1u);
+	}
+	__syncthreads();
+	hist[(size_t)tid * n_blocks + blockIdx.x] = h[tid];
+}
+
+// one workgroup per digit: its row of tile counts becomes exclusive prefix sums, tot[d] the row's sum
+__global__ __launch_bounds__(SV_THREADS) void survey_rows_kernel(uint32_t *hist, uint32_t n_blocks, uint32_t *tot)
+{
+	__shared__ uint32_t lds[SV_WAVES];
+	uint32_t *row = hist + (size_t)blockIdx.x * n_blocks;
+	uint32_t carry = 0;
+	for (uint32_t base = 0; base < n_blocks; base += SV_THREADS) {
+		const uint32_t i = base + threadIdx.x;
+		const uint32_t v = i < n_blocks ? row[i] : 0;
+		uint32_t sum;
+		const uint32_t ex = sv_block_scan(v, lds, sum);
+		if (i < n_blocks)
+			row[i] = carry + ex;
+		carry += sum;
+	}
+	if (threadIdx.x == 0)
+		tot[blockIdx.x] = carry;
+}
+
+// stable scatter of one tile: 256 records per round, ranked by ballots within a wave and by counters between waves
+__global__ __launch_bounds__(SV_THREADS) void survey_scatter_kernel(const uint64_t *keys, const uint32_t *vals, const btbbx_hit *hits,
+								      const uint32_t *params, uint32_t cap, uint32_t n_blocks, int by_stream,
+								      uint32_t shift, const uint32_t *hist, const uint32_t *tot,
+								      uint64_t *keys_out, uint32_t *vals_out)
+{
+	__shared__ uint32_t lds[SV_WAVES];
+	__shared__ uint32_t run[256];
+	__shared__ uint32_t wcnt[SV_WAVES][256];
+	const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = params[0];
+	uint32_t all;
+	const uint32_t digit_base = sv_block_scan(tot[tid], lds, all);
+	run[tid] = digit_base + hist[(size_t)tid * n_blocks + blockIdx.x];
+#pragma unroll
+	for (uint32_t w = 0; w < SV_WAVES; w++)
+		wcnt[w][tid] = 0;
+	__syncthreads();
+	const uint32_t base = blockIdx.x * SV_SORT_TILE;
+	for (uint32_t k = 0; k < SV_SORT_TILE / SV_THREADS; k++) {
+		if (base + k * SV_THREADS >= n)
+			break;                                          // (uniform over the workgroup)
+		const uint32_t i = base + k * SV_THREADS + tid;
+		const bool valid = i < n;
+		uint64_t key = 0;
+		uint32_t val = 0, d = 0;
+		if (valid) {
+			key = keys[i];
+			val = vals[i];
+			d = by_stream ? ((uint32_t)hits[val].stream >> shift) & 0xff : (uint32_t)(key >> shift) & 0xff;
+		}
+		uint64_t peers = __ballot(valid);
+#pragma unroll
+		for (int b = 0; b < 8; b++) {
+			const bool bit = (d >> b) & 1;
+			const uint64_t m = __ballot(valid && bit);
+			peers &= bit ? m : ~m;
+		}
+		const uint32_t rank = __popcll(peers & ((1ULL << lane) - 1));
+		if (valid && rank == 0)
+			wcnt[wave][d] = __popcll(peers);
+		__syncthreads();
+		if (valid) {
+			uint32_t pos = run[d] + rank;
+			for (uint32_t w = 0; w < wave; w++)
+				pos += wcnt[w][d];
+			if (pos < cap) {
+				keys_out[pos] = key;
+				vals_out[pos] = val;
+			}
+		}
+		__syncthreads();
+		uint32_t s = 0;
+#pragma unroll
+		for (uint32_t w = 0; w < SV_WAVES; w++) {
+			s += wcnt[w][tid];
+			wcnt[w][tid] = 0;
+		}
+		run[tid] += s;
+		__syncthreads();
+	}
+}
+
+// ---- 2. group table, sorted records, channel maps ------------------------------------------------------
+
+__device__ __forceinline__ bool sv_first_of_lap(const uint64_t *keys, uint32_t i, uint32_t n)
+{
+	return i < n && (i == 0 || sv_lap_of(keys[i]) != sv_lap_of(keys[i - 1]));
+}
+
+__global__ __launch_bounds__(SV_THREADS) void survey_mark_kernel(const uint64_t *keys, const uint32_t *params, uint32_t *tiles)
+{
+	__shared__ uint32_t count;
+	const uint32_t tid = threadIdx.x, n = params[0];
+	if (tid == 0)
+		count = 0;
+	__syncthreads();
+	uint32_t mine = 0;
+	for (uint32_t k = 0; k < SV_GRP_TILE / SV_THREADS; k++)
+		mine += sv_first_of_lap(keys, blockIdx.x * SV_GRP_TILE + k * SV_THREADS + tid, n) ? 1u : 0u;
+	if (mine)
+		atomicAdd(&count, mine);
+	__syncthreads();
+	if (tid == 0)
+		tiles[blockIdx.x] = count;
+}
+
+// one workgroup: tile counts -> exclusive prefix sums; the number of groups goes to params[1], *rec_count and,
+// as the end of the last group, gstart[groups] = n
+__global__ __launch_bounds__(SV_THREADS) void survey_tiles_kernel(uint32_t *tiles, uint32_t n_tiles, uint32_t *params, uint32_t *gstart,
+								    uint32_t *rec_count)
+{
+	__shared__ uint32_t lds[SV_WAVES];
+	uint32_t carry = 0;
+	for (uint32_t base = 0; base < n_tiles; base += SV_THREADS) {
+		const uint32_t i = base + threadIdx.x;
+		const uint32_t v = i < n_tiles ? tiles[i] : 0;
+		uint32_t sum;
+		const uint32_t ex = sv_block_scan(v, lds, sum);
+		if (i < n_tiles)
+			tiles[i] = carry + ex;
+		carry += sum;
+	}
+	if (threadIdx.x == 0) {
+		params[1] = carry;
+		gstart[carry] = params[0];
+		if (rec_count)
+			*rec_count = carry;
+	}
+}
+
+__global__ __launch_bounds__(SV_THREADS) void survey_group_kernel(const uint64_t *keys, const uint32_t *vals, const btbbx_hit *hits,
+								    const uint32_t *params, uint32_t cap, const uint32_t *tiles,
+								    uint64_t total_bits, uint32_t n_streams, uint32_t max_length,
+								    btbbx_pkt_in entry, uint32_t clk_div, uint32_t clk_phase,
+								    SurveyChannels table, int identity,
+								    uint32_t *gstart, uint32_t *chan, btbbx_hit *hits_out, btbbx_pkt_in *pin)
+{
+	__shared__ uint32_t lds[SV_WAVES];
+	const uint32_t tid = threadIdx.x, n = params[0];
+	uint32_t carry = tiles[blockIdx.x];
+	for (uint32_t k = 0; k < SV_GRP_TILE / SV_THREADS; k++) {
+		const uint32_t i = blockIdx.x * SV_GRP_TILE + k * SV_THREADS + tid;
+		const bool first = sv_first_of_lap(keys, i, n);
+		uint32_t sum;
+		const uint32_t ex = sv_block_scan(first ? 1u : 0u, lds, sum);
+		const uint32_t gid = carry + ex + (first ? 1u : 0u) - 1u;         // (i < n: some record at or before i is a first one)
+		carry += sum;
+		btbbx_hit h;
+		h.offset = SV_PAD_OFFSET;
+		h.lap = 0;
+		h.ac_errors = 0;
+		h.reserved = 0;
+		h.stream = 0;
+		btbbx_pkt_in p = entry;
+		p.length = 0;
+		uint32_t word = 3, bit = 0;                                        // (word 3 of a group's four: never read)
+		if (i < n) {
+			h = hits[vals[i]];
+			if (first)
+				gstart[gid] = i;
+			p.clkn = entry.clkn + (uint32_t)((h.offset + clk_phase) / clk_div);
+			if (h.stream < n_streams) {
+				const uint32_t ch = identity ? h.stream : table.ch[h.stream];
+				word = ch >> 5;
+				bit = 1u << (ch & 31);
+				// the captured length, as gather_kernel computes it
+				const uint64_t avail = h.offset < total_bits ? total_bits - h.offset : 0;
+				uint32_t len = avail < max_length ? (uint32_t)avail : max_length;
+				p.length = len > BTBBX_MAX_SYMBOLS ? BTBBX_MAX_SYMBOLS : len;
+			} else {
+				h.offset = SV_PAD_OFFSET;                                 // a stream that does not exist: no symbols, no channel
+				h.stream = 0;
+			}
+		}
+		if (i < n) {
+			hits_out[i] = h;
+			pin[i] = p;
+		}
+		// channel map: a wave whose records all belong to one group (the waves of a large piconet) sends three atomics
+		const uint64_t active = __ballot(i < n);
+		const uint32_t g0 = __shfl(gid, 0, 64);
+		if (active == ~0ULL && __ballot(gid == g0) == ~0ULL) {
+			uint32_t m0 = word == 0 ? bit : 0, m1 = word == 1 ? bit : 0, m2 = word == 2 ? bit : 0;
+#pragma unroll
+			for (int d = 32; d >= 1; d >>= 1) {
+				m0 |= __shfl_xor(m0, d, 64);
+				m1 |= __shfl_xor(m1, d, 64);
+				m2 |= __shfl_xor(m2, d, 64);
+			}
+			if ((tid & 63) < 3) {
+				const uint32_t m = (tid & 63) == 0 ? m0 : (tid & 63) == 1 ? m1 : m2;
+				if (m)
+					atomicOr(&chan[(size_t)g0 * 4 + (tid & 63)], m);
+			}
+		} else if (i < n && bit) {
+			atomicOr(&chan[(size_t)gid * 4 + word], bit);
+		}
+	}
+}
+
+// ---- 3b. the packets a walk can touch ------------------------------------------------------------------
+// A packet without a header is never walked (it only marks its channel), and one piconet may own a million of them: the
+// header-bearing packets are compacted, in sorted order, into widx[]; wpos[i] = how many of them lie before record i, so
+// group g walks widx[wpos[gstart[g]] .. wpos[gstart[g + 1]]) and never looks at the others.
+
+__global__ __launch_bounds__(SV_THREADS) void survey_wmark_kernel(const uint8_t *present, const uint32_t *params, uint32_t *wtiles)
+{
+	__shared__ uint32_t count;
+	const uint32_t tid = threadIdx.x, n = params[0];
+	if (tid == 0)
+		count = 0;
+	__syncthreads();
+	uint32_t mine = 0;
+	for (uint32_t k = 0; k < SV_GRP_TILE / SV_THREADS; k++) {
+		const uint32_t i = blockIdx.x * SV_GRP_TILE + k * SV_THREADS + tid;
+		mine += i < n && present[i] ? 1u : 0u;
+	}
+	if (mine)
+		atomicAdd(&count, mine);
+	__syncthreads();
+	if (tid == 0)
+		wtiles[blockIdx.x] = count;
+}
+
+// one workgroup: tile counts -> exclusive prefix sums; wpos[n] = all header-bearing packets
+__global__ __launch_bounds__(SV_THREADS) void survey_wtiles_kernel(uint32_t *wtiles, uint32_t n_tiles, const uint32_t *params, uint32_t *wpos)
+{
+	__shared__ uint32_t lds[SV_WAVES];
+	uint32_t carry = 0;
+	for (uint32_t base = 0; base < n_tiles; base += SV_THREADS) {
+		const uint32_t i = base + threadIdx.x;
+		const uint32_t v = i < n_tiles ? wtiles[i] : 0;
+		uint32_t sum;
+		const uint32_t ex = sv_block_scan(v, lds, sum);
+		if (i < n_tiles)
+			wtiles[i] = carry + ex;
+		carry += sum;
+	}
+	if (threadIdx.x == 0)
+		wpos[params[0]] = carry;
+}
+
+__global__ __launch_bounds__(SV_THREADS) void survey_wlist_kernel(const uint8_t *present, const uint32_t *params, const uint32_t *wtiles,
+								    uint32_t *wpos, uint32_t *widx)
+{
+	__shared__ uint32_t lds[SV_WAVES];
+	const uint32_t tid = threadIdx.x, n = params[0];
+	uint32_t carry = wtiles[blockIdx.x];
+	for (uint32_t k = 0; k < SV_GRP_TILE / SV_THREADS; k++) {
+		const uint32_t i = blockIdx.x * SV_GRP_TILE + k * SV_THREADS + tid;
+		const bool has = i < n && present[i];
+		uint32_t sum;
+		const uint32_t at = carry + sv_block_scan(has ? 1u : 0u, lds, sum);
+		carry += sum;
+		if (i < n) {
+			wpos[i] = at;
+			if (has)
+				widx[at] = i;                           // (at < n: fewer header-bearing packets than packets before and at i)
+		}
+	}
+}
+
+// ---- 4. the walk ------------------------------------------------------------------------------------
+
+// One wave per piconet, lane c = candidate "CLK1-6 of the first packet was c".  Trial rows are loaded as they lie
+// (lane c reads trial c) SV_BATCH packets at a time, none of them depending on the piconet's state; the rotation by
+// the packet's distance from the first packet is a lane permutation once the state is known.  Only header-bearing packets
+// are visited (widx, above): per 64 of them one load of their indices and clocks.
+__global__ __launch_bounds__(SV_THREADS) void survey_walk_kernel(const uint32_t *params, uint32_t rec_cap, const uint32_t *gstart,
+								   const uint32_t *chan, const btbbx_hit *hits, const uint32_t *vals,
+								   const btbbx_pkt_in *pin, const uint32_t *wpos, const uint32_t *widx, const uint32_t *trials,
+								   btbbx_survey_rec *recs, int16_t *candidates)
+{
+	const uint32_t lane = threadIdx.x & 63;
+	const uint32_t g = blockIdx.x * SV_WAVES + (threadIdx.x >> 6);
+	const uint32_t n_groups = params[1];
+	if (g >= n_groups || g >= rec_cap)
+		return;
+	const uint32_t start = gstart[g], end = gstart[g + 1];
+
+	int cand = 0;                                     // clock6_candidates[lane] of a new piconet object
+	uint32_t flags = SVF_LAP_VALID;
+	uint32_t first_pkt_time = 0, n_walked = 0, n_resets = 0;
+	int packets_observed = 0, total_observed = 0;
+	uint32_t settled_by = 0, settled_after = 0, settled_at = 0xffffffffu, uap = 0, clk_offset = 0;
+
+	const uint32_t wfirst = wpos[start], wend = wpos[end];
+	for (uint32_t base = wfirst; base < wend && !settled_by; base += 64) {
+		const bool ok = base + lane < wend;
+		const uint32_t my_idx = ok ? widx[base + lane] : 0;
+		const uint32_t my_clkn = ok ? pin[my_idx].clkn : 0;
+		uint64_t todo = __ballot(ok);
+		while (todo && !settled_by) {
+			uint32_t row[SV_BATCH];
+			int which[SV_BATCH];
+#pragma unroll
+			for (int k = 0; k < SV_BATCH; k++) {
+				which[k] = -1;
+				row[k] = 0;
+				if (todo) {
+					which[k] = __builtin_ctzll(todo);
+					todo &= todo - 1;
+					row[k] = trials[(size_t)__shfl(my_idx, which[k], 64) * 64 + lane];
+				}
+			}
+#pragma unroll
+			for (int k = 0; k < SV_BATCH; k++) {
+				if (which[k] < 0 || settled_by)
+					continue;
+				const uint32_t clkn = __shfl(my_clkn, which[k], 64);
+				n_walked++;
+				const bool opening = !(flags & SVF_GOT_FIRST);
+				if (opening)
+					first_pkt_time = clkn;
+				if (packets_observed >= SV_MAX_PATTERN) {         // "Oops. More hops than we can remember."
+					flags &= ~(SVF_GOT_FIRST | SVF_UAP_VALID | SVF_CLK6_VALID);
+					packets_observed = 0;
+					n_resets++;
+					continue;
+				}
+				packets_observed++;
+				total_observed++;
+				const uint32_t rot = (clkn - first_pkt_time) & 63;
+				const uint32_t t = __shfl(row[k], (lane + rot) & 63, 64);
+				const int t_uap = (int)(t & 0xff);
+				const int rv = (int)(int16_t)(t >> 16);
+				const bool live = opening || cand >= 0;
+				const bool checked = live && (opening || t_uap == cand);
+				const bool kept = checked && (rv == 1 || rv == 2);
+				const uint64_t proven = __ballot(checked && !kept && rv != 0);
+				const uint32_t winner = proven ? (uint32_t)__builtin_ctzll(proven) : 64u;
+				if (live && lane < winner)
+					cand = kept ? t_uap : -1;
+				if (winner < 64) {                                  // "Correct CRC!"
+					uap = (uint32_t)__shfl(t_uap, winner, 64);
+					clk_offset = (winner - (first_pkt_time & 0x3f)) & 0x3f;
+					settled_by = 2;
+				} else {
+					flags |= SVF_GOT_FIRST;
+					const uint64_t survivors = __ballot(kept);
+					const uint32_t left = __popcll(survivors);
+					if (left == 1) {
+						const uint32_t only = (uint32_t)__builtin_ctzll(survivors);
+						uap = (uint32_t)__shfl(t_uap, only, 64);
+						clk_offset = (only - (first_pkt_time & 0x3f)) & 0x3f;
+						settled_by = 1;
+					} else if (left == 0) {
+						flags &= ~(SVF_GOT_FIRST | SVF_UAP_VALID | SVF_CLK6_VALID);
+						packets_observed = 0;
+						n_resets++;
+					}
+				}
+				if (settled_by) {
+					flags |= SVF_CLK6_VALID | SVF_UAP_VALID;
+					settled_after = (uint32_t)total_observed;
+					total_observed = 0;
+					settled_at = vals[__shfl(my_idx, which[k], 64)];
+				}
+			}
+		}
+	}
+
+	if (candidates)
+		candidates[(size_t)g * 64 + lane] = (int16_t)cand;
+	if (lane == 0) {
+		const btbbx_hit h0 = hits[start];
+		const uint32_t m0 = chan[(size_t)g * 4], m1 = chan[(size_t)g * 4 + 1], m2 = chan[(size_t)g * 4 + 2];
+		btbbx_survey_rec r;
+		r.lap = h0.lap;
+		r.flags = flags;
+		r.uap = (uint8_t)uap;
+		r.clk_offset = (uint8_t)clk_offset;
+		r.used_channels = (uint8_t)(__popc(m0) + __popc(m1) + __popc(m2));
+		r.settled_by = (uint8_t)settled_by;
+#pragma unroll
+		for (int b = 0; b < 10; b++) {
+			const uint32_t m = b < 4 ? m0 : b < 8 ? m1 : m2;
+			r.afh_map[b] = (uint8_t)(m >> (8 * (b & 3)));
+		}
+		r.first_stream = h0.stream;
+		r.n_packets = end - start;
+		r.n_walked = n_walked;
+		r.n_resets = n_resets;
+		r.settled_after = settled_after;
+		r.settled_hit = settled_at;
+		r.packets_observed = packets_observed;
+		r.total_packets_observed = total_observed;
+		r.first_pkt_time = first_pkt_time;
+		r.first_offset = h0.offset;
+		recs[g] = r;
+	}
+}
+
+// ---- C ABI ------------------------------------------------------------------------------------------
+
+extern "C" size_t btbbx_survey_scratch_bytes(uint32_t cap)
+{
+	return survey_layout(cap).total;
+}
+
+static uint32_t bits_of(uint64_t v)
+{
+	uint32_t b = 0;
+	while (v) {
+		b++;
+		v >>= 1;
+	}
+	return b;
+}
+
+static int survey_check_args(const char *who, uint64_t n_words, uint32_t n_streams, const uint8_t *channels, const btbbx_pkt_in *entry,
+			     uint32_t clk_div, uint32_t clk_phase)
+{
+	if (!n_streams || !n_words || n_words > (1ULL << 34)) {
+		set_error("%s: no streams, no words or offsets beyond 2^40", who);
+		return BTBBX_E_ARG;
+	}
+	if (!entry || !clk_div || clk_phase >= clk_div) {
+		set_error("%s: no entry state, clk_div = 0 or clk_phase >= clk_div", who);
+		return BTBBX_E_ARG;
+	}
+	if (!channels && n_streams > 79) {
+		set_error("%s: %u streams need a channel table (BR/EDR has channels 0..78)", who, n_streams);
+		return BTBBX_E_ARG;
+	}
+	if (channels) {
+		if (n_streams > SV_CHAN_STREAMS) {
+			set_error("%s: a channel table covers at most %u streams", who, SV_CHAN_STREAMS);
+			return BTBBX_E_ARG;
+		}
+		for (uint32_t s = 0; s < n_streams; s++)
+			if (channels[s] > 78) {
+				set_error("%s: channels[%u] = %u is not a BR/EDR channel (0..78)", who, s, channels[s]);
+				return BTBBX_E_ARG;
+			}
+	}
+	return BTBBX_OK;
+}
+
+extern "C" int btbbx_survey_hits_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+					const btbbx_hit *d_hits, const uint32_t *d_count, uint32_t cap, const uint8_t *channels,
+					const btbbx_pkt_in *entry, uint32_t clk_div, uint32_t clk_phase, uint32_t max_length,
+					btbbx_survey_rec *d_recs, uint32_t rec_cap, uint32_t *d_rec_count, int16_t *d_candidates,
+					void *d_scratch, size_t scratch_bytes, void *hip_stream)
+{
+	int rc = survey_check_args("btbbx_survey_hits_device", n_words, n_streams, channels, entry, clk_div, clk_phase);
+	if (rc)
+		return rc;
+	const SurveyLayout L = survey_layout(cap);
+	if (!d_words || !d_rec_count || (cap && !d_hits) || (cap && rec_cap && !d_recs) || !d_scratch || scratch_bytes < L.total) {
+		set_error("btbbx_survey_hits_device: null pointer, or scratch of %zu bytes needed and %zu given", L.total, scratch_bytes);
+		return BTBBX_E_ARG;
+	}
+	if (((uintptr_t)d_scratch & 15) || ((uintptr_t)d_hits & 15) || ((uintptr_t)d_recs & 7) || ((uintptr_t)d_words & 7) ||
+	    ((uintptr_t)d_rec_count & 3) || ((uintptr_t)d_count & 3) || ((uintptr_t)d_candidates & 1)) {
+		set_error("btbbx_survey_hits_device: misaligned pointer (scratch and hits 16 bytes, records and words 8)");
+		return BTBBX_E_ARG;
+	}
+	if (n_streams > 1 && pitch_words < n_words) {
+		set_error("btbbx_survey_hits_device: pitch_words < n_words");
+		return BTBBX_E_ARG;
+	}
+	rc = ctx_require();
+	if (rc)
+		return rc;
+	hipStream_t q = (hipStream_t)hip_stream;
+	if (!cap) {
+		HIP_TRY(hipMemsetAsync(d_rec_count, 0, sizeof(uint32_t), q));
+		return BTBBX_OK;
+	}
+	char *s = (char *)d_scratch;
+	uint32_t *params = (uint32_t *)(s + L.params);
+	uint64_t *keys[2] = {(uint64_t *)(s + L.keys[0]), (uint64_t *)(s + L.keys[1])};
+	uint32_t *vals[2] = {(uint32_t *)(s + L.vals[0]), (uint32_t *)(s + L.vals[1])};
+	uint32_t *hist = (uint32_t *)(s + L.hist), *tot = (uint32_t *)(s + L.tot), *tiles = (uint32_t *)(s + L.tiles);
+	uint32_t *gstart = (uint32_t *)(s + L.gstart), *chan = (uint32_t *)(s + L.chan), *lengths = (uint32_t *)(s + L.lengths);
+	btbbx_hit *shits = (btbbx_hit *)(s + L.hits);
+	btbbx_pkt_in *pin = (btbbx_pkt_in *)(s + L.pin);
+	uint64_t *packets = (uint64_t *)(s + L.packets);
+	btbbx_trial *trials = (btbbx_trial *)(s + L.trials);
+	uint8_t *present = (uint8_t *)(s + L.present);
+	uint32_t *wtiles = (uint32_t *)(s + L.wtiles), *wpos = (uint32_t *)(s + L.wpos), *widx = (uint32_t *)(s + L.widx);
+
+	HIP_TRY(hipMemsetAsync(chan, 0, (size_t)cap * 16, q));
+	const uint32_t cap_blocks = (cap + SV_THREADS - 1) / SV_THREADS;
+	hipLaunchKernelGGL(survey_key_kernel, dim3(cap_blocks), dim3(SV_THREADS), 0, q, d_hits, d_count, cap, params, keys[0], vals[0]);
+
+	// digits from the least significant: stream, offset, LAP -- only those that can differ
+	struct Pass { int by_stream; uint32_t shift; } passes[12];
+	int n_passes = 0;
+	for (uint32_t b = 0; b < bits_of(n_streams - 1); b += 8)
+		passes[n_passes++] = {1, b};
+	for (uint32_t b = 0; b < bits_of(n_words * 64 - 1) && b < 40; b += 8)
+		passes[n_passes++] = {0, b};
+	for (uint32_t b = 40; b < 64; b += 8)
+		passes[n_passes++] = {0, b};
+	int cur = 0;
+	for (int p = 0; p < n_passes; p++) {
+		hipLaunchKernelGGL(survey_hist_kernel, dim3(L.sort_blocks), dim3(SV_THREADS), 0, q, keys[cur], vals[cur], d_hits, params,
+				   L.sort_blocks, passes[p].by_stream, passes[p].shift, hist);
+		hipLaunchKernelGGL(survey_rows_kernel, dim3(256), dim3(SV_THREADS), 0, q, hist, L.sort_blocks, tot);
+		hipLaunchKernelGGL(survey_scatter_kernel, dim3(L.sort_blocks), dim3(SV_THREADS), 0, q, keys[cur], vals[cur], d_hits, params, cap,
+				   L.sort_blocks, passes[p].by_stream, passes[p].shift, hist, tot, keys[cur ^ 1], vals[cur ^ 1]);
+		cur ^= 1;
+	}
+
+	hipLaunchKernelGGL(survey_mark_kernel, dim3(L.grp_tiles), dim3(SV_THREADS), 0, q, keys[cur], params, tiles);
+	hipLaunchKernelGGL(survey_tiles_kernel, dim3(1), dim3(SV_THREADS), 0, q, tiles, L.grp_tiles, params, gstart, d_rec_count);
+	SurveyChannels table;
+	memset(&table, 0, sizeof(table));
+	if (channels)
+		memcpy(table.ch, channels, n_streams);
+	hipLaunchKernelGGL(survey_group_kernel, dim3(L.grp_tiles), dim3(SV_THREADS), 0, q, keys[cur], vals[cur], d_hits, params, cap, tiles,
+			   n_words * 64, n_streams, max_length, *entry, clk_div, clk_phase, table, channels ? 0 : 1, gstart, chan, shits, pin);
+	HIP_TRY(hipGetLastError());
+
+	// (launched for cap, worked for the list's length: params[0])
+	rc = launch_gather(d_words, n_words, pitch_words, shits, cap, params, max_length, packets, lengths, q);
+	if (rc)
+		return rc;
+	rc = launch_trials(packets, pin, cap, params, trials, q);
+	if (rc)
+		return rc;
+	rc = launch_header_flags(packets, lengths, cap, params, present, q);
+	if (rc)
+		return rc;
+	hipLaunchKernelGGL(survey_wmark_kernel, dim3(L.grp_tiles), dim3(SV_THREADS), 0, q, present, params, wtiles);
+	hipLaunchKernelGGL(survey_wtiles_kernel, dim3(1), dim3(SV_THREADS), 0, q, wtiles, L.grp_tiles, params, wpos);
+	hipLaunchKernelGGL(survey_wlist_kernel, dim3(L.grp_tiles), dim3(SV_THREADS), 0, q, present, params, wtiles, wpos, widx);
+
+	const uint32_t walkers = rec_cap < cap ? rec_cap : cap;
+	if (walkers)
+		hipLaunchKernelGGL(survey_walk_kernel, dim3((walkers + SV_WAVES - 1) / SV_WAVES), dim3(SV_THREADS), 0, q, params, rec_cap,
+				   gstart, chan, shits, vals[cur], pin, wpos, widx, (const uint32_t *)trials, d_recs, d_candidates);
+	HIP_TRY(hipGetLastError());
+	return BTBBX_OK;
+}
+
+extern "C" int64_t btbbx_survey_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				     uint64_t search_bits, int max_ac_errors, const uint8_t *channels,
+				     uint32_t clkn0, uint32_t clk_div, uint32_t clk_phase,
+				     btbbx_survey_rec *recs, uint64_t rec_cap, int16_t *candidates)
+{
+	btbbx_pkt_in entry;
+	memset(&entry, 0, sizeof(entry));
+	entry.clkn = clkn0;
+	entry.flags = 1u << 0;                                  // BTBB_WHITENED: what btbb_find_ac leaves (init_packet)
+	int rc = survey_check_args("btbbx_survey_host", n_words, n_streams, channels, &entry, clk_div, clk_phase);
+	if (rc)
+		return rc;
+	if (n_streams == 1)
+		pitch_words = n_words;
+	if (!words || (!recs && rec_cap) || pitch_words < n_words || search_bits + 63 > n_words * 64) {
+		set_error("btbbx_survey_host: null pointer, pitch_words < n_words or search_bits + 63 > 64 n_words");
+		return BTBBX_E_ARG;
+	}
+	rc = ctx_require();
+	if (rc)
+		return rc;
+	if (!search_bits)
+		return 0;
+	CallScope scope;
+	hipStream_t q = scope_stream();
+	const uint64_t cap_words = (uint64_t)(n_streams - 1) * pitch_words + n_words;
+	uint64_t *d_words = (uint64_t *)scope_device((size_t)(cap_words + 2) * 8);
+	if (!d_words)
+		return BTBBX_E_NOMEM;
+	HIP_TRY(hipMemcpyAsync(d_words, words, (size_t)cap_words * 8, hipMemcpyHostToDevice, q));
+
+	// Scan first (one hit per 1024 offsets + slack; again with room for every match when more were found, as
+	// btbbx_scan_host does), read the count back, and size the survey's scratch from it.
+	uint64_t guess = search_bits / 1024 * n_streams + 4096;
+	uint32_t dev_cap = guess > 0xfffffff0ULL ? 0xfffffff0u : (uint32_t)guess;
+	uint32_t count = 0;
+	char *block = nullptr;
+	for (int pass = 0; pass < 2; pass++) {
+		const size_t hit_bytes = sv_up((size_t)dev_cap * sizeof(btbbx_hit));
+		const size_t order_bytes = sv_up(btbbx_scan_ordered_scratch_bytes(search_bits, n_streams, BTBBX_LAP_ANY, dev_cap));
+		block = (char *)scope_hits(256 + hit_bytes + order_bytes);
+		if (!block)
+			return BTBBX_E_NOMEM;
+		HIP_TRY(hipMemsetAsync(block, 0, 2 * sizeof(uint32_t), q));
+		rc = btbbx_scan_ordered_device(d_words, n_words, pitch_words, n_streams, search_bits, BTBBX_LAP_ANY, max_ac_errors,
+					       (btbbx_hit *)(block + 256), dev_cap, (uint32_t *)block, block + 256 + hit_bytes, order_bytes, q);
+		if (rc)
+			return rc;
+		HIP_TRY(hipMemcpyAsync(&count, block, sizeof(count), hipMemcpyDeviceToHost, q));
+		HIP_TRY(hipStreamSynchronize(q));
+		if (count <= dev_cap)
+			break;
+		dev_cap = count;
+	}
+	const uint32_t have = std::min(count, dev_cap);
+	if (!have)
+		return 0;
+	// records, candidates and the survey's scratch: one block for the life of the call
+	const uint32_t dev_recs = (uint32_t)std::min<uint64_t>(rec_cap, have);
+	const size_t survey_bytes = sv_up(btbbx_survey_scratch_bytes(have));
+	const size_t rec_bytes = sv_up((size_t)dev_recs * sizeof(btbbx_survey_rec));
+	const size_t cand_bytes = candidates ? sv_up((size_t)dev_recs * 64 * sizeof(int16_t)) : 0;
+	char *work = nullptr;
+	if (hipMalloc((void **)&work, survey_bytes + rec_bytes + cand_bytes + 256) != hipSuccess) {
+		(void)hipGetLastError();
+		set_error("btbbx_survey_host: %zu bytes of device memory for %u hits not available", survey_bytes + rec_bytes + cand_bytes, have);
+		return BTBBX_E_NOMEM;
+	}
+	btbbx_survey_rec *d_recs = (btbbx_survey_rec *)(work + survey_bytes);
+	int16_t *d_cand = candidates ? (int16_t *)(work + survey_bytes + rec_bytes) : nullptr;
+	uint32_t *d_rec_count = (uint32_t *)block + 1;
+	uint32_t n_piconets = 0;
+	rc = btbbx_survey_hits_device(d_words, n_words, pitch_words, n_streams, (const btbbx_hit *)(block + 256), (const uint32_t *)block, have,
+				      channels, &entry, clk_div, clk_phase, BTBBX_MAX_SYMBOLS, d_recs, dev_recs, d_rec_count, d_cand, work,
+				      survey_bytes, q);
+	hipError_t e = hipSuccess;
+	if (!rc) {
+		e = hipMemcpyAsync(&n_piconets, d_rec_count, sizeof(n_piconets), hipMemcpyDeviceToHost, q);
+		if (e == hipSuccess)
+			e = hipStreamSynchronize(q);
+		const uint64_t n = std::min<uint64_t>(n_piconets, dev_recs);
+		if (e == hipSuccess && n)
+			e = hipMemcpyAsync(recs, d_recs, (size_t)n * sizeof(btbbx_survey_rec), hipMemcpyDeviceToHost, q);
+		if (e == hipSuccess && n && candidates)
+			e = hipMemcpyAsync(candidates, d_cand, (size_t)n * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, q);
+	}
+	const hipError_t f = hipStreamSynchronize(q);
+	(void)hipFree(work);
+	if (rc)
+		return rc;
+	HIP_TRY(e);
+	HIP_TRY(f);
+	return (int64_t)n_piconets;
+}
