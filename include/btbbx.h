@@ -117,7 +117,9 @@ int btbbx_slide_set(int max_ac_errors, uint32_t *bitmap_words, uint64_t *taps);
  * levels, as the kernel reads them: first_words = a 2^20-bit set (32768 words) over twenty positions of the check
  * taps[0], indexed by the COMPLEMENT of the checks' value (index i, bit i & 31 of word i >> 5); second_words = a
  * 2^24-bit set (524288 words) over twenty-four positions of the check taps[1], index i at bit 31 - (i & 31) of word
- * i >> 5.  A window within max_ac_errors of a sync word is a member of both.  Returns 0 or a negative BTBBX_E_*. */
+ * i >> 5.  A window within max_ac_errors of a sync word is a member of both.  Returns 0 or a negative BTBBX_E_*.
+ * max_ac_errors = 5 (first_words may be NULL and is not written): second_words alone = the front set the five-error scan
+ * probes before its exact check, the same size and bit order; taps[0] = 0, taps[1] = its check. */
 int btbbx_slide_sets_two_level(int max_ac_errors, uint32_t *first_words, uint32_t *second_words, uint64_t *taps);
 
 /* ---- device memory helpers (so C callers need not link HIP themselves) -------- */
@@ -216,12 +218,14 @@ int btbbx_order_scan_hits_device(btbbx_hit *d_hits, const uint32_t *d_count, uin
  * *d_count itself (on hip_stream): the list is built from this call's matches only, records an earlier scan appended
  * are not carried over -- chain scans with btbbx_scan_device and order the whole list once with btbbx_order_hits_device. */
 /* Scratch for btbbx_scan_ordered_device over n_streams streams of search_bits offsets each (round 6).  Where the scan has its
- * segment-slot form -- LAP_ANY with tables for up to two errors -- every wave leaves its hits, ranked, in slots of the 4032 offsets
- * they lie in (16 bytes per 4032 offsets of scratch), and the ordered list is one compaction of those slots: no bucket counters, no
- * scatter, no ranking pass.  The size returned covers that (and the general ordering, which stays the fallback for a stream the
- * slots cannot rank: one made of sync words); for other scans it equals btbbx_order_hits_scratch_bytes(cap).  A call that is
- * handed btbbx_order_hits_scratch_bytes(cap) bytes only runs the general ordering.  Needs btbb_init / btbbx_init first (the
- * answer depends on the tables). */
+ * segment-slot form -- every known-LAP scan, and LAP_ANY with tables for up to two errors -- every wave leaves its hits, ranked,
+ * in slots of the segment they lie in (4096 offsets for a known LAP, 4032 for LAP_ANY), and the ordered list is one compaction of
+ * those slots: no bucket counters, no scatter, no ranking pass.  The slots take about 22 bytes per segment (two 8-byte slots, a
+ * 2-byte count, a 4-byte start index) plus 24 bytes per record of cap for the hits ranked beyond a segment's slots.  The size
+ * returned covers that and the general ordering, which stays the fallback for a stream the slots cannot rank (one made of sync
+ * words); for LAP_ANY with tables for more errors it equals btbbx_order_hits_scratch_bytes(cap).  A call that is handed
+ * btbbx_order_hits_scratch_bytes(cap) bytes only runs the general ordering.  Needs btbb_init / btbbx_init first (the answer
+ * depends on the tables). */
 size_t btbbx_scan_ordered_scratch_bytes(uint64_t search_bits, uint32_t n_streams, uint32_t lap, uint32_t cap);
 int btbbx_scan_ordered_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
 			      uint64_t search_bits, uint32_t lap, int max_ac_errors, btbbx_hit *d_hits, uint32_t cap,

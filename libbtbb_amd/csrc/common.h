@@ -10,12 +10,11 @@
 #include <stddef.h>
 #include "../../include/btbbx.h"
 #include "slide.h"
+#include "bitslice.h"                      // BARKER0 / BARKER1, and the bit-slice primitives of the scans
 
 // ---- spec constants ---------------------------------------------------------------
 #define SW_POLY   0260534236651ULL         // (64,30) block code generator, degree 34
 #define SW_PN     0x83848D96BBCC54FCULL    // PN overlay (bluetooth_packet.c:115)
-#define BARKER1   0x27u                    // 7-bit window when LAP bit 23 = 1 (host order)
-#define BARKER0   0x58u                    // 7-bit window when LAP bit 23 = 0
 #define LOW57     0x01ffffffffffffffULL
 
 // ---- scan kernel geometry ---------------------------------------------------------

@@ -8,7 +8,7 @@
 // x^24 + x^10 + x^9 + x^6 + x^4 + x^3 + x + 1, preset with CRCInit) covers the 2 + L PDU octets and is sent from
 // register position 23 down to 0.  Both registers run here in their reflected software form: whitening state bit j
 // = position 6 - j, CRC state bit j = position 23 - j; tests/_le.py shifts the spec's positions literally.
-#include "common.h"
+#include "tile_scan.h"
 #include <algorithm>
 #include <stddef.h>
 
@@ -16,9 +16,6 @@
 #define LE_WORDS 2                               // consecutive stream words per lane and tile (tile = 512 words)
 #define LE_TILE_WORDS (LE_THREADS * LE_WORDS)
 #define LE_RING 128                              // per-wave hit ring (entries)
-
-typedef uint32_t le_u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t le_u32x2 __attribute__((ext_vector_type(2)));
 
 struct LeScanArgs {
 	const uint64_t *words;
@@ -35,72 +32,6 @@ struct LeScanArgs {
 	uint32_t hit_cap;
 	uint32_t *hit_count;
 };
-
-__device__ __forceinline__ uint32_t le_alignbit(uint32_t hi, uint32_t lo, uint32_t sh) { return __builtin_amdgcn_alignbit(hi, lo, sh); }
-
-// truth table of f(a ^ ia, b ^ ib, c ^ ic) for the table `base` of f(a, b, c): a pattern bit of 1 folds into the
-// adder's immediate instead of costing an XOR per plane
-constexpr uint32_t le_tt3(uint32_t base, bool ia, bool ib, bool ic)
-{
-	uint32_t t = 0;
-	for (uint32_t idx = 0; idx < 8; idx++) {
-		const uint32_t a = ((idx >> 2) & 1) ^ (ia ? 1u : 0u), b = ((idx >> 1) & 1) ^ (ib ? 1u : 0u), c = (idx & 1) ^ (ic ? 1u : 0u);
-		t |= ((base >> (a * 4 + b * 2 + c)) & 1) << idx;
-	}
-	return t;
-}
-template <uint32_t TT>
-__device__ __forceinline__ uint32_t le_op3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, TT); }
-
-// Bit-sliced pre-filter over sixteen of the forty pattern bits: window bits 0..7 (the preamble) and 32..39 (the AA's
-// last octet) of 32 offsets.  r[0..7] = window bits 0..7, r[8..15] = bits 32..39.  PAT >= 0: the sixteen pattern bits
-// (bit k = plane k) are folded into the first adder level; PAT < 0: flip[k] (all ones where the pattern has a 1) is
-// XORed into each plane.  Returns the offsets with at most `limit` mismatches among the sixteen -- the count itself is
-// never formed: weight-1 sums s*, weight-2 carries c*; count = ones + 2 T with T = the number of set weight-2 bits, and
-// "<= limit" is decided from whether T is 0, <= 1 or <= 2.
-template <int PAT, int LIMIT>
-__device__ __forceinline__ uint32_t le_filter16(const uint32_t *r, const uint32_t *flip)
-{
-	uint32_t m[16];
-#pragma unroll
-	for (int k = 0; k < 16; k++)
-		m[k] = PAT < 0 ? (r[k] ^ flip[k]) : r[k];
-#define INV(k) (PAT >= 0 && ((PAT >> (k)) & 1))
-#define G3(base, i) le_op3<le_tt3(base, INV(i), INV(i + 1), INV(i + 2))>(m[i], m[i + 1], m[i + 2])
-	const uint32_t m15 = INV(15) ? ~m[15] : m[15];
-	if (LIMIT == 0) {                                   // no mismatch: the NOR of the sixteen planes
-		const uint32_t x0 = G3(0xfe, 0), x1 = G3(0xfe, 3), x2 = G3(0xfe, 6), x3 = G3(0xfe, 9), x4 = G3(0xfe, 12);
-		return ~(le_op3<0xfe>(x0, x1, x2) | le_op3<0xfe>(x3, x4, m15));
-	}
-	const uint32_t s0 = G3(0x96, 0), c0 = G3(0xe8, 0);
-	const uint32_t s1 = G3(0x96, 3), c1 = G3(0xe8, 3);
-	const uint32_t s2 = G3(0x96, 6), c2 = G3(0xe8, 6);
-	const uint32_t s3 = G3(0x96, 9), c3 = G3(0xe8, 9);
-	const uint32_t s4 = G3(0x96, 12), c4 = G3(0xe8, 12);
-#undef G3
-#undef INV
-	const uint32_t o1 = le_op3<0x96>(s0, s1, s2), k0 = le_op3<0xe8>(s0, s1, s2);
-	const uint32_t o2 = le_op3<0x96>(s3, s4, m15), k1 = le_op3<0xe8>(s3, s4, m15);
-	const uint32_t ones = o1 ^ o2, k2 = o1 & o2;
-	// the eight weight-2 bits c0..c4, k0, k1, k2 in three groups: a* = sums, b* = carries (weight 4 in the count)
-	if (LIMIT == 1)                                     // T == 0
-		return ~(le_op3<0xfe>(le_op3<0xfe>(c0, c1, c2), le_op3<0xfe>(c3, c4, k0), k1) | k2);
-	const uint32_t a0 = le_op3<0x96>(c0, c1, c2), b0 = le_op3<0xe8>(c0, c1, c2);
-	const uint32_t a1 = le_op3<0x96>(c3, c4, k0), b1 = le_op3<0xe8>(c3, c4, k0);
-	const uint32_t a2 = k1 ^ k2, b2 = k1 & k2;
-	const uint32_t b_any = le_op3<0xfe>(b0, b1, b2);
-	const uint32_t le1 = ~(b_any | le_op3<0xe8>(a0, a1, a2));                          // T <= 1
-	if (LIMIT == 3)
-		return le1;
-	if (LIMIT == 2) {                                   // T == 0, or T == 1 and no weight-1 mismatch
-		const uint32_t z = ~(b_any | le_op3<0xfe>(a0, a1, a2));
-		return z | (le1 & ~ones);
-	}
-	// LIMIT 4: T <= 1, or T == 2 and no weight-1 mismatch.  T <= 2 <=> (no b and not all three a) or (exactly one b and no a)
-	const uint32_t b_one = le_op3<0x96>(b0, b1, b2) & ~le_op3<0xe8>(b0, b1, b2);
-	const uint32_t le2 = (~b_any & ~le_op3<0x80>(a0, a1, a2)) | (b_one & ~le_op3<0xfe>(a0, a1, a2));
-	return le1 | (le2 & ~ones);
-}
 
 // One workgroup of 256 lanes works on a tile of 512 words of one stream at a time; a lane owns two consecutive words
 // (four dwords D[0..3]) and reads the next word as its halo (D[4..5]): chain c = the 32 offsets starting at dword c,
@@ -131,27 +62,6 @@ __global__ __launch_bounds__(LE_THREADS) void le_scan_kernel(LeScanArgs a)
 	}
 	const uint32_t lw = tid * LE_WORDS;
 	uint64_t nw[LE_WORDS + 1];
-	auto fetch = [&](uint32_t ft, uint32_t fstream) {
-		// a buffer descriptor over the tile: the hardware's range check returns zero for words behind the stream's end
-		uint32_t bytes = 0;
-		const uint64_t *tp = a.words;
-		if (fstream < a.n_streams) {
-			tp = a.words + (uint64_t)fstream * a.pitch_words + (uint64_t)ft * LE_TILE_WORDS;
-			bytes = (LE_TILE_WORDS + 1u) * 8u;
-			if (ft >= a.full_tiles) {
-				asm volatile("" ::: "memory");
-				const uint64_t first = (uint64_t)ft * LE_TILE_WORDS;
-				const uint64_t left = first < a.n_words ? a.n_words - first : 0;
-				bytes = (uint32_t)(left < LE_TILE_WORDS + 1u ? left : LE_TILE_WORDS + 1u) * 8u;
-			}
-		}
-		const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint64_t *>(tp), 0, (int)bytes, 0x00020000);
-		const le_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(lw * 8u), 0, 0);
-		const le_u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)(lw * 8u), 16, 0);
-		nw[0] = ((uint64_t)v.y << 32) | v.x;
-		nw[1] = ((uint64_t)v.w << 32) | v.z;
-		nw[2] = ((uint64_t)w.y << 32) | w.x;
-	};
 	// Hits wait in a per-wave LDS ring and leave 64 at a time: one counter atomic per 64 hits (a single counter word saturates
 	// near 88 M atomics/s, which one atomic per wave and pass ran into at one packet per 4096 bits: 0.46 Tbit/s)
 	uint4 *ring = ring_mem[tid >> 6];
@@ -182,7 +92,8 @@ __global__ __launch_bounds__(LE_THREADS) void le_scan_kernel(LeScanArgs a)
 		}
 		q_tail += (uint32_t)__popcll(mask);
 	};
-	fetch(t, stream);
+	auto fetch = [&](uint32_t ft, uint32_t fstream) { fetch_run<LE_TILE_WORDS>(a, ft, fstream, lw * 8u, nw); };
+	fetch(t, stream);                                   // (not waited for in front of the loop as in scan_known_lap_kernel: DESIGN 3.8)
 	constexpr int NCH = 2 * LE_WORDS;
 	while (stream < a.n_streams) {
 		const uint64_t word0 = (uint64_t)t * LE_TILE_WORDS + lw;
@@ -205,14 +116,14 @@ __global__ __launch_bounds__(LE_THREADS) void le_scan_kernel(LeScanArgs a)
 			P[0][0] = D[0];
 #pragma unroll
 			for (int j = 1; j < 8; j++)
-				P[0][j] = le_alignbit(D[1], D[0], j);
+				P[0][j] = alignbit(D[1], D[0], j);
 #pragma unroll
 			for (int c = 0; c < NCH; c++) {
 				uint32_t *up = P[(c + 1) & 1];
 				up[0] = D[c + 1];
 #pragma unroll
 				for (int j = 1; j < 8; j++)
-					up[j] = le_alignbit(D[c + 2], D[c + 1], j);
+					up[j] = alignbit(D[c + 2], D[c + 1], j);
 				uint32_t r[16];
 #pragma unroll
 				for (int j = 0; j < 8; j++) {
@@ -244,7 +155,7 @@ __global__ __launch_bounds__(LE_THREADS) void le_scan_kernel(LeScanArgs a)
 				if (!__ballot(m[c] != 0))
 					continue;
 				const uint32_t p = (uint32_t)__builtin_ctz(m[c] | 0x80000000u);
-				const uint32_t lo = le_alignbit(D[c + 1], D[c], p), hi = le_alignbit(D[c + 2], D[c + 1], p);
+				const uint32_t lo = alignbit(D[c + 1], D[c], p), hi = alignbit(D[c + 2], D[c + 1], p);
 				const uint32_t e = (uint32_t)__popc(lo ^ pat_lo) + (uint32_t)__popc((hi ^ pat_hi) & 0xffu);
 				const bool hit = m[c] != 0 && e <= (uint32_t)LIMIT;
 				m[c] &= m[c] - 1;
@@ -463,19 +374,7 @@ static int le_check_args(const char *who, uint64_t n_words, uint64_t pitch_words
 		set_error("%s: max_errors must be 0..%d", who, BTBBX_LE_MAX_ERRORS);
 		return BTBBX_E_ARG;
 	}
-	if (n_streams == 0 || n_streams > 65535) {
-		set_error("%s: n_streams must be 1..65535", who);
-		return BTBBX_E_ARG;
-	}
-	if (n_streams > 1 && pitch_words < n_words) {
-		set_error("%s: pitch_words < n_words", who);
-		return BTBBX_E_ARG;
-	}
-	if (n_words > (1ull << 40) || search_bits + 39 > n_words * 64) {
-		set_error("%s: search_bits + 39 exceeds the stream (%llu bits)", who, (unsigned long long)(n_words * 64));
-		return BTBBX_E_ARG;
-	}
-	return BTBBX_OK;
+	return check_scan_args(who, 40, n_words, pitch_words, n_streams, search_bits);
 }
 
 static int le_launch_scan(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, uint64_t search_bits,
@@ -499,24 +398,16 @@ static int le_launch_scan(const uint64_t *d_words, uint64_t n_words, uint64_t pi
 	a.hits = d_hits;
 	a.hit_cap = hit_cap;
 	a.hit_count = d_hit_count;
-	const uint64_t search_words = (search_bits + 63) / 64;
-	const uint64_t tps = (search_words + LE_TILE_WORDS - 1) / LE_TILE_WORDS;
-	const uint64_t n_tiles = tps * n_streams;
-	{	// tile t is full iff (t + 1) * 512 + 1 <= n_words and (t + 1) * 512 * 64 <= search_bits
-		const uint64_t by_words = n_words ? (n_words - 1) / LE_TILE_WORDS : 0, by_bits = search_bits / (LE_TILE_WORDS * 64ull);
-		const uint64_t full = std::min(by_words, by_bits);
-		a.full_tiles = full > 0xffffffffull ? 0xffffffffu : (uint32_t)full;
-	}
-	const uint64_t grid = std::min<uint64_t>(n_tiles, (uint64_t)ctx().num_cus * 8);
-	if (tps + grid >= (1ull << 32)) {
-		set_error("btbbx_le_scan_device: stream too long for one launch (split it)");
-		return BTBBX_E_ARG;
-	}
-	a.tiles_per_stream = (uint32_t)tps;
+	TileGrid g;
+	const int rc = tile_grid("btbbx_le_scan_device", search_bits, n_words, n_streams, LE_TILE_WORDS, ctx().num_cus, &g);
+	if (rc)
+		return rc;
+	a.full_tiles = g.full_tiles;
+	a.tiles_per_stream = (uint32_t)g.tiles_per_stream;
 	const bool adv = aa == BTBBX_LE_ADV_AA;
 	// the advertising AA's sixteen filter bits (preamble 0xaa, AA octet 0x8e) folded into the adders; any other AA: XORs
 	constexpr int ADV_PAT = 0xaa | (0x8e << 8);
-#define LE_LAUNCH(P, L) hipLaunchKernelGGL((le_scan_kernel<P, L>), dim3((uint32_t)grid), dim3(LE_THREADS), 0, q, a)
+#define LE_LAUNCH(P, L) hipLaunchKernelGGL((le_scan_kernel<P, L>), dim3(g.grid), dim3(LE_THREADS), 0, q, a)
 #define LE_LAUNCH_L(L) do { if (adv) LE_LAUNCH(ADV_PAT, L); else LE_LAUNCH(-1, L); } while (0)
 	switch (max_errors) {
 	case 0: LE_LAUNCH_L(0); break;

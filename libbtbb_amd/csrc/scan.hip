@@ -30,7 +30,7 @@
 // work, no MFMA; bound by VALU issue, not by HBM (DESIGN.md 3.1 and 6 say what it is bound by).
 #include <stdlib.h>
 #include <string.h>
-#include "common.h"
+#include "tile_scan.h"
 
 #define FULL_MASK 0xffffffffffffffffULL
 
@@ -92,11 +92,6 @@ __device__ unsigned long long g_scan_prof[32];
 #define PROF_MARK(k) do { (void)(k); } while (0)
 #define PROF_PIN(x) do { } while (0)
 #endif
-
-__device__ __forceinline__ uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t sh)
-{
-	return __builtin_amdgcn_alignbit(hi, lo, sh);
-}
 
 __device__ __forceinline__ void count_bucket(const ScanArgs &a, uint32_t stream, uint64_t offset)
 {
@@ -164,8 +159,6 @@ __device__ __forceinline__ uint64_t sign16_after_shl(uint32_t x, uint32_t sh)
 	asm("v_lshlrev_b16 %1, %2, %3\n\tv_cmp_gt_i16_e64 %0, 0, %1" : "=s"(m), "=&v"(r) : "v"(sh), "v"(x));
 	return m;
 }
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) u32x4 lds_u32x4_t;
 __device__ __forceinline__ u32x4 lds_ld4(uint32_t byte_off) { return *reinterpret_cast<lds_u32x4_t *>(byte_off); }
 __device__ __forceinline__ void lds_st4(uint32_t byte_off, u32x4 v) { *reinterpret_cast<lds_u32x4_t *>(byte_off) = v; }
@@ -232,19 +225,6 @@ __device__ __forceinline__ bool verify_lap_any(const ScanArgs &a, uint64_t w, ui
 }
 
 // ---- LAP_ANY ----------------------------------------------------------------------------
-
-// index of the lowest set bit; 0xffffffff for 0 (v_ffbl_b32), which the callers use as
-// "offset 31 of a lane that has nothing left" -- its result is masked out afterwards
-__device__ __forceinline__ uint32_t lowest_bit(uint32_t m)
-{
-	uint32_t p;
-	asm("v_ffbl_b32 %0, %1" : "=v"(p) : "v"(m));
-	return p;
-}
-
-// three-input boolean in one full-rate instruction (truth table index = a*4 + b*2 + c)
-#define BITOP3(a, b, c, tt) __builtin_amdgcn_bitop3_b32((a), (b), (c), (tt))
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return BITOP3(a, b, c, 0x96); }
 
 // Barker pre-filter for the 32 offsets whose 7-bit window (LAP MSB + 6 barker bits,
 // bluetooth_packet.c:378-385) lives in dh:dm: bit k of the window at offset p is bit
@@ -1433,178 +1413,6 @@ void scan_slide_kernel(ScanArgs a)
 
 // ---- known LAP --------------------------------------------------------------------------
 
-// Truth table of a three-input function whose inputs are (compile-time) inverted: index = a*4 + b*2 + c as v_bitop3 wants it.
-// The sync word's top seven bits are the LAP's MSB and the barker code that follows from it (bluetooth_packet.c:81-113), so for
-// a given class the mismatch planes of window bits 57..63 are the stream planes themselves or their complements -- the
-// complement goes into the adders' truth tables instead of costing an XOR per plane (CLS = 0 / 1; -1 = every plane XORed with
-// its run-time flip mask as before).
-constexpr uint32_t tt3(uint32_t base, bool ia, bool ib, bool ic)
-{
-	uint32_t t = 0;
-	for (uint32_t idx = 0; idx < 8; idx++) {
-		const uint32_t a = ((idx >> 2) & 1) ^ (ia ? 1u : 0u), b = ((idx >> 1) & 1) ^ (ib ? 1u : 0u), c = (idx & 1) ^ (ic ? 1u : 0u);
-		t |= ((base >> (a * 4 + b * 2 + c)) & 1) << idx;
-	}
-	return t;
-}
-// sync-word bit 57 + j of class CLS: 0x27 = 0100111b for LAP MSB 1, its complement for 0 (BARKER1 / BARKER0, common.h)
-constexpr bool barker_bit(int cls, int j) { return (((cls ? BARKER1 : BARKER0) >> j) & 1) != 0; }
-// (the truth table of v_bitop3 is an immediate: it has to reach the builtin as a template constant)
-template <uint32_t TT>
-__device__ __forceinline__ uint32_t bitop3_tt(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, TT); }
-
-// The planes of the known-LAP filters (round 6, late): the filter may count mismatches in ANY subset of the sync word's bits, so it
-// takes them where the funnel shifts can be shared -- window bits 24 + j and 56 + j (j = 0 .. 7) of the offsets p of a 32-offset half
-// are the stream bits p + 24 + j of two neighbouring dword pairs, and the UPPER planes of one half are the LOWER planes of the next:
-// three sets of eight shifts per word instead of four (sixteen top bits per half: 32 v_alignbit per word -> 24).  Bits 57 .. 63 are
-// still the class bits whose complement folds into the adders' truth tables.
-// P[j] = stream bit p + 24 + j of hi:lo for the 32 offsets p of a half (j = FIRST .. 7)
-template <int FIRST>
-__device__ __forceinline__ void pair_planes(uint32_t lo, uint32_t hi, uint32_t *P)
-{
-#pragma unroll
-	for (int j = FIRST; j < 8; j++)
-		P[j] = alignbit(hi, lo, 24 + j);
-}
-
-// bit-sliced "mismatches in sync-word bits 28..31 and 56..63 <= limit" for 32 offsets: twelve planes
-// (lowp[4 .. 7] = window bits 28 .. 31, highp[0 .. 7] = window bits 56 .. 63; flip[4 + k] = the sync word's bit of plane k),
-// a carry-save adder tree to a 4-bit count per offset, and a bit-sliced compare with the run-time limit.  For limit 2 it keeps
-// 79 / 4096 = 1.9 % of the offsets of a random stream.
-template <int CLS>
-__device__ __forceinline__ uint32_t top12_filter(const uint32_t *lowp, const uint32_t *highp, const uint32_t *flip, int limit)
-{
-	if (limit >= 12)
-		return 0xffffffffu;
-	uint32_t m[12];
-#pragma unroll
-	for (int k = 0; k < 12; k++) {                      // plane k: 0 .. 3 = window bits 28 .. 31, 4 = bit 56, 5 .. 11 = the class bits 57 .. 63
-		m[k] = k < 4 ? lowp[4 + k] : highp[k - 4];
-		if (CLS < 0 || k < 5)
-			m[k] ^= flip[4 + k];
-	}
-	constexpr bool K = CLS >= 0;
-#define INV(k) (K && barker_bit(CLS, (k) - 5))
-#define FA_SUM(a, b, c) BITOP3((a), (b), (c), 0x96)
-#define FA_CARRY(a, b, c) BITOP3((a), (b), (c), 0xe8)
-	if (limit == 0) {                                   // no mismatch at all: the OR of the twelve planes (six instructions; third session of round 6)
-		const uint32_t r0 = BITOP3(m[0], m[1], m[2], 0xfe);
-		const uint32_t r1 = bitop3_tt<tt3(0xfe, false, false, INV(5))>(m[3], m[4], m[5]);
-		const uint32_t r2 = bitop3_tt<tt3(0xfe, INV(6), INV(7), INV(8))>(m[6], m[7], m[8]);
-		const uint32_t r3 = bitop3_tt<tt3(0xfe, INV(9), INV(10), INV(11))>(m[9], m[10], m[11]);
-		return ~(BITOP3(r0, r1, r2, 0xfe) | r3);
-	}
-	const uint32_t s0 = FA_SUM(m[0], m[1], m[2]), c0 = FA_CARRY(m[0], m[1], m[2]);
-	const uint32_t s1 = bitop3_tt<tt3(0x96, false, false, INV(5))>(m[3], m[4], m[5]), c1 = bitop3_tt<tt3(0xe8, false, false, INV(5))>(m[3], m[4], m[5]);
-	const uint32_t s2 = bitop3_tt<tt3(0x96, INV(6), INV(7), INV(8))>(m[6], m[7], m[8]), c2 = bitop3_tt<tt3(0xe8, INV(6), INV(7), INV(8))>(m[6], m[7], m[8]);
-	const uint32_t s3 = bitop3_tt<tt3(0x96, INV(9), INV(10), INV(11))>(m[9], m[10], m[11]), c3 = bitop3_tt<tt3(0xe8, INV(9), INV(10), INV(11))>(m[9], m[10], m[11]);
-#undef INV
-	const uint32_t o1 = FA_SUM(s0, s1, s2), k0 = FA_CARRY(s0, s1, s2);
-	if (limit == 1) {                                   // count = o1 + s3 + 2 x (c0 .. c3, k0): <= 1 <=> none of those five and not both of o1, s3
-		const uint32_t w = BITOP3(c0, c1, c2, 0xfe);
-		const uint32_t x = BITOP3(c3, k0, w, 0xfe);
-		return ~BITOP3(x, o1, s3, 0xf8);                // ~(x | (o1 & s3))
-	}
-	const uint32_t ones = o1 ^ s3, k1 = o1 & s3;
-	const uint32_t t0 = FA_SUM(c0, c1, c2), f0 = FA_CARRY(c0, c1, c2);
-	const uint32_t t1 = FA_SUM(c3, k0, k1), f1 = FA_CARRY(c3, k0, k1);
-	const uint32_t twos = t0 ^ t1, f2 = t0 & t1;
-	if (limit <= 3) {                                   // (see top16_filter)
-		const uint32_t ge4 = BITOP3(f0, f1, f2, 0xfe);
-		const uint32_t low = limit == 0 ? (twos | ones) : limit == 1 ? twos : limit == 2 ? (twos & ones) : 0u;
-		return ~(ge4 | low);
-	}
-	const uint32_t fours = FA_SUM(f0, f1, f2), eights = FA_CARRY(f0, f1, f2);
-#undef FA_SUM
-#undef FA_CARRY
-	// count = ones + 2 twos + 4 fours + 8 eights; keep offsets with count <= limit
-	uint32_t gt = 0, eq = 0xffffffffu;
-	const uint32_t planes[4] = { eights, fours, twos, ones };
-#pragma unroll
-	for (int b = 0; b < 4; b++) {
-		const uint32_t lim_bit = ((limit >> (3 - b)) & 1) ? 0xffffffffu : 0u;
-		gt |= eq & planes[b] & ~lim_bit;
-		eq &= ~(planes[b] ^ lim_bit);
-	}
-	return ~gt;
-}
-
-// The same over sixteen sync-word bits (24..31 and 56..63): five more adders, but for limit >= 2 it
-// leaves a tenth of the survivors (0.2 % instead of 1.9 % at limit 2), which is worth more than it
-// costs; for limit <= 1 the twelve-plane filter is already sparse enough and cheaper.
-template <int CLS>
-__device__ __forceinline__ uint32_t top16_filter(const uint32_t *lowp, const uint32_t *highp, const uint32_t *flip, int limit)
-{
-	if (limit >= 16)
-		return 0xffffffffu;
-	uint32_t m[16];
-#pragma unroll
-	for (int k = 0; k < 16; k++) {                      // plane k: 0 .. 7 = window bits 24 .. 31, 8 = bit 56, 9 .. 15 = the class bits 57 .. 63
-		m[k] = k < 8 ? lowp[k] : highp[k - 8];
-		if (CLS < 0 || k < 9)
-			m[k] ^= flip[k];
-	}
-	constexpr bool K = CLS >= 0;
-#define INV(k) (K && barker_bit(CLS, (k) - 9))
-#define FA_SUM(a, b, c) BITOP3((a), (b), (c), 0x96)
-#define FA_CARRY(a, b, c) BITOP3((a), (b), (c), 0xe8)
-	// weight 1
-	const uint32_t s0 = FA_SUM(m[0], m[1], m[2]), c0 = FA_CARRY(m[0], m[1], m[2]);
-	const uint32_t s1 = FA_SUM(m[3], m[4], m[5]), c1 = FA_CARRY(m[3], m[4], m[5]);
-	const uint32_t s2 = FA_SUM(m[6], m[7], m[8]), c2 = FA_CARRY(m[6], m[7], m[8]);
-	const uint32_t s3 = bitop3_tt<tt3(0x96, INV(9), INV(10), INV(11))>(m[9], m[10], m[11]), c3 = bitop3_tt<tt3(0xe8, INV(9), INV(10), INV(11))>(m[9], m[10], m[11]);
-	const uint32_t s4 = bitop3_tt<tt3(0x96, INV(12), INV(13), INV(14))>(m[12], m[13], m[14]), c4 = bitop3_tt<tt3(0xe8, INV(12), INV(13), INV(14))>(m[12], m[13], m[14]);
-	const uint32_t o1 = FA_SUM(s0, s1, s2), k0 = FA_CARRY(s0, s1, s2);
-	const uint32_t o2 = bitop3_tt<tt3(0x96, false, false, INV(15))>(s3, s4, m[15]), k1 = bitop3_tt<tt3(0xe8, false, false, INV(15))>(s3, s4, m[15]);
-#undef INV
-	// limit 2 or 3 (third session of round 6): count = o1 + o2 + 2 x (bits set among W = c0 .. c4, k0, k1), so
-	//   count <= 2  <=>  no bit of W, or exactly one and neither o1 nor o2     = at_most_one(W) & ~(any(W) & (o1 | o2))
-	//   count <= 3  <=>  no bit of W, or exactly one and not both o1 and o2    = at_most_one(W) & ~(any(W) & o1 & o2)
-	// at_most_one over the groups (c0 c1 c2) (c3 c4 k0) (k1): no group holds two, no two groups hold one -- nine instructions
-	// where the twos / fours columns, their carries and the compare took thirteen (27 -> 23 per 32 offsets)
-	if (limit == 2 || limit == 3) {
-		const uint32_t a0 = BITOP3(c0, c1, c2, 0xfe), t0 = BITOP3(c0, c1, c2, 0xe8);     // any / at least two of a group
-		const uint32_t a1 = BITOP3(c3, c4, k0, 0xfe), t1 = BITOP3(c3, c4, k0, 0xe8);
-		const uint32_t two_groups = BITOP3(a0, a1, k1, 0xe8);
-		const uint32_t any = BITOP3(a0, a1, k1, 0xfe);
-		const uint32_t odd = limit == 2 ? BITOP3(any, o1, o2, 0xe0)                       // any & (o1 | o2)
-						: BITOP3(any, o1, o2, 0x80);                      // any & o1 & o2
-		const uint32_t bad = BITOP3(t0, t1, two_groups, 0xfe);
-		return ~(bad | odd);
-	}
-	const uint32_t ones = o1 ^ o2, k2 = o1 & o2;
-	// weight 2: c0..c4, k0, k1, k2
-	const uint32_t t0 = FA_SUM(c0, c1, c2), f0 = FA_CARRY(c0, c1, c2);
-	const uint32_t t1 = FA_SUM(c3, c4, k0), f1 = FA_CARRY(c3, c4, k0);
-	const uint32_t t2 = FA_SUM(k1, k2, t0), f2 = FA_CARRY(k1, k2, t0);
-	const uint32_t twos = t1 ^ t2, f3 = t1 & t2;
-	// limit <= 3: "count >= 4" is all that matters of the upper weights, and it is the OR of the four carries out of the
-	// twos column -- six adder instructions and the compare become three (the compiler cannot find this: it is not the
-	// same function as the sum it replaces)
-	if (limit <= 3) {
-		const uint32_t ge4 = BITOP3(f0, f1, f2, 0xfe);
-		const uint32_t low = limit == 0 ? (twos | ones) : limit == 1 ? twos : limit == 2 ? (twos & ones) : 0u;
-		return ~BITOP3(ge4, f3, low, 0xfe);
-	}
-	// weight 4: f0..f3
-	const uint32_t g0 = FA_SUM(f0, f1, f2), h0 = FA_CARRY(f0, f1, f2);
-	const uint32_t fours = g0 ^ f3, h1 = g0 & f3;
-	// weight 8, 16
-	const uint32_t eights = h0 ^ h1, sixteens = h0 & h1;
-#undef FA_SUM
-#undef FA_CARRY
-	// count = ones + 2 twos + 4 fours + 8 eights + 16 sixteens; keep offsets with count <= limit
-	uint32_t gt = sixteens, eq = ~sixteens;
-	const uint32_t planes[4] = { eights, fours, twos, ones };
-#pragma unroll
-	for (int b = 0; b < 4; b++) {
-		const uint32_t lim_bit = ((limit >> (3 - b)) & 1) ? 0xffffffffu : 0u;
-		gt |= eq & planes[b] & ~lim_bit;
-		eq &= ~(planes[b] ^ lim_bit);
-	}
-	return ~gt;
-}
-
 // Known-LAP hits are staged in a per-wave LDS ring and flushed 64 at a time: one global
 // counter atomic per 64 hits (a single counter word saturates near 88 M atomics/s on this
 // chip, which a dense hit stream would otherwise run into).
@@ -1808,30 +1616,9 @@ __global__ __launch_bounds__(256) void scan_known_lap_kernel(ScanArgs a)
 	constexpr int NCH = 2 * KL_WORDS;                   // chains (32-offset halves) per lane and tile
 	const uint32_t lw = tid * KL_WORDS;                 // the lane's first word in a tile
 	uint64_t nw[KL_WORDS + 1];                          // the lane's words of the next tile and the word behind them
-	static_assert(KL_WORDS == 2, "fetch: one 16-byte and one 8-byte buffer load per lane");
+	static_assert(KL_WORDS == 2, "fetch_run: one 16-byte and one 8-byte buffer load per lane");
 	const uint32_t lw_bytes = lw * 8u;
-	auto fetch = [&](uint32_t ft, uint32_t fstream) {
-		// The lane's run of the next tile through a buffer descriptor over the tile (as scan_slide_kernel's load_pair: the hardware's
-		// range check returns zero for the words behind the stream's end): no zero-initialised registers, no exec masks.
-		uint32_t bytes = 0;                             // wave-uniform
-		const uint64_t *tp = a.words;
-		if (fstream < a.n_streams) {
-			tp = a.words + (uint64_t)fstream * a.pitch_words + (uint64_t)ft * (KL_WORDS * 256);
-			bytes = (KL_WORDS * 256u + 1u) * 8u;         // (a full tile: every word and the halo word are in range)
-			if (ft >= a.full_tiles) {
-				asm volatile("" ::: "memory");              // (a real branch: flattened, its 64-bit compares are vector instructions of every tile)
-				const uint64_t first = (uint64_t)ft * (KL_WORDS * 256);
-				const uint64_t left = first < a.n_words ? a.n_words - first : 0;
-				bytes = (uint32_t)(left < KL_WORDS * 256u + 1u ? left : KL_WORDS * 256u + 1u) * 8u;
-			}
-		}
-		const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint64_t *>(tp), 0, (int)bytes, 0x00020000);
-		const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)lw_bytes, 0, 0);
-		const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)lw_bytes, 16, 0);
-		nw[0] = ((uint64_t)v.y << 32) | v.x;
-		nw[1] = ((uint64_t)v.w << 32) | v.z;
-		nw[2] = ((uint64_t)w.y << 32) | w.x;
-	};
+	auto fetch = [&](uint32_t ft, uint32_t fstream) { fetch_run<KL_WORDS * 256>(a, ft, fstream, lw_bytes, nw); };
 	fetch(t, stream);
 	// The first tile's words are waited for HERE: with these loads still counted as pending at the loop head the compiler waits for
 	// "everything in flight" (s_waitcnt vmcnt(0)) in front of the filter of EVERY tile -- right behind the next tile's loads, which
@@ -2067,26 +1854,8 @@ __global__ __launch_bounds__(256) void bitrev_bytes_kernel(uint64_t *words, uint
 
 // ---- launchers ----------------------------------------------------------------------------
 
-static int check_scan_args(uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, uint64_t search_bits)
-{
-	if (n_streams == 0 || n_streams > 65535) {
-		set_error("btbbx_scan: n_streams must be 1..65535");
-		return BTBBX_E_ARG;
-	}
-	if (n_streams > 1 && pitch_words < n_words) {
-		set_error("btbbx_scan: pitch_words < n_words");
-		return BTBBX_E_ARG;
-	}
-	if (search_bits + 63 > n_words * 64) {
-		set_error("btbbx_scan: search_bits + 63 exceeds the stream (%llu > %llu bits)",
-			  (unsigned long long)(search_bits + 63), (unsigned long long)(n_words * 64));
-		return BTBBX_E_ARG;
-	}
-	return BTBBX_OK;
-}
-
 // geometry of the segment slots for a scan of these streams (sort.hip sizes its scratch from it); false: this scan has no slot form
-// (known LAP, or tables for more than two errors)
+// (LAP_ANY with tables for more than two errors) or more segments than the slots' 31-bit numbers hold
 bool scan_slot_geometry(uint64_t search_bits, uint32_t n_streams, uint32_t lap, uint32_t *segs_per_stream, uint64_t *n_segs)
 {
 	int table_errors = 0;
@@ -2119,7 +1888,7 @@ int launch_scan(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words,
 	int rc = ctx_require();
 	if (rc)
 		return rc;
-	rc = check_scan_args(n_words, pitch_words, n_streams, search_bits);
+	rc = check_scan_args("btbbx_scan", 64, n_words, pitch_words, n_streams, search_bits);
 	if (rc)
 		return rc;
 	if (search_bits == 0)
@@ -2259,26 +2028,19 @@ int launch_scan(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words,
 	} else {
 		a.syncword = host_gen_syncword(lap & 0xffffff);
 		a.lap = lap;
-		const uint64_t kl_tile = 256ull * KL_WORDS;
-		a.tiles_per_stream = (search_words + kl_tile - 1) / kl_tile;
-		a.n_tiles = a.tiles_per_stream * n_streams;
-		{	// tile t (kl_tile words) is full iff (t + 1) * kl_tile + 1 <= n_words and (t + 1) * kl_tile * 64 <= search_bits
-			const uint64_t by_words = n_words ? (n_words - 1) / kl_tile : 0, by_bits = search_bits / (kl_tile * 64ull);
-			const uint64_t full = by_words < by_bits ? by_words : by_bits;
-			a.full_tiles = full > 0xffffffffull ? 0xffffffffu : (uint32_t)full;
-		}
-		uint64_t cap = (uint64_t)c.num_cus * 8;
-		uint64_t grid = a.n_tiles < cap ? a.n_tiles : cap;
-		if (a.tiles_per_stream + grid >= (1ull << 32)) {
-			set_error("btbbx_scan: stream too long for one launch (split it)");
-			return BTBBX_E_ARG;
-		}
+		TileGrid g;
+		rc = tile_grid("btbbx_scan", search_bits, n_words, n_streams, 256 * KL_WORDS, c.num_cus, &g);
+		if (rc)
+			return rc;
+		a.tiles_per_stream = g.tiles_per_stream;
+		a.n_tiles = g.n_tiles;
+		a.full_tiles = g.full_tiles;
 		if (slots && (a.segs_per_stream != a.tiles_per_stream * (4 * KL_WORDS) || d_first)) {
 			set_error("btbbx_scan: internal: segment slots laid out for another geometry");
 			return BTBBX_E_ARG;
 		}
 		const bool cls1 = ((a.syncword >> 57) & 1) != 0;          // = bit 23 of the LAP
-#define LAUNCH_KNOWN__(L, C_, M_, O_) hipLaunchKernelGGL((scan_known_lap_kernel<L, C_, M_, O_>), dim3((uint32_t)grid), dim3(256), 0, stream, a)
+#define LAUNCH_KNOWN__(L, C_, M_, O_) hipLaunchKernelGGL((scan_known_lap_kernel<L, C_, M_, O_>), dim3(g.grid), dim3(256), 0, stream, a)
 #define LAUNCH_KNOWN_(L, C_, M_) do { if (slots) LAUNCH_KNOWN__(L, C_, M_, true); else LAUNCH_KNOWN__(L, C_, M_, false); } while (0)
 #define LAUNCH_KNOWN(L) do { if (cls1) { if (msb) LAUNCH_KNOWN_(L, 1, true); else LAUNCH_KNOWN_(L, 1, false); } \
 		else { if (msb) LAUNCH_KNOWN_(L, 0, true); else LAUNCH_KNOWN_(L, 0, false); } } while (0)
@@ -2497,7 +2259,7 @@ extern "C" int64_t btbbx_scan_host(const uint64_t *words, uint64_t n_words, uint
 	int rc = ctx_require();
 	if (rc)
 		return rc;
-	rc = check_scan_args(n_words, n_words, 1, search_bits);
+	rc = check_scan_args("btbbx_scan", 64, n_words, n_words, 1, search_bits);
 	if (rc)
 		return rc;
 	CallScope scope;
@@ -2626,7 +2388,7 @@ extern "C" int64_t btbbx_scan_host_multi(const uint64_t *words, uint64_t n_words
 		set_error("btbbx_scan_host_multi: bad argument");
 		return BTBBX_E_ARG;
 	}
-	int rc = check_scan_args(n_words, n_words, 1, search_bits);
+	int rc = check_scan_args("btbbx_scan", 64, n_words, n_words, 1, search_bits);
 	if (rc)
 		return rc;
 	struct Part {
