@@ -9,19 +9,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include "common.h"
-#include "packet_obj.h"
+#include "packet_launch.h"
 #include "../../include/btbb.h"
-
-int launch_trials_state(const uint8_t *d_sym, const btbbx_pkt_in *d_in, const btbbx_pkt_out *d_out, void *d_state,
-			btbbx_trial *d_trials, hipStream_t stream);
-int launch_trials_merge(const void *d_state, const btbbx_pkt_in *d_in, btbbx_pkt_out *d_out, uint8_t *d_pay,
-			const TrialPlan *plan, hipStream_t stream);
-size_t trials_state_bytes();
-int launch_decode_bytes(const uint8_t *d_sym, uint8_t *d_pay, const btbbx_pkt_in *d_in, btbbx_pkt_out *d_out,
-			uint32_t mode, bool with_payload, hipStream_t stream);
-int launch_decode(const uint64_t *d_packets, const btbbx_pkt_in *d_in, uint32_t n_packets,
-		  btbbx_pkt_out *d_out, uint32_t mode, const TrialPlan *plan, hipStream_t stream);
 
 #ifndef BTBB_RELEASE
 #define BTBB_RELEASE "mi355x-r1"

@@ -16,6 +16,8 @@
 //
 // Nothing here synchronises or reads back: the list's length stays in device memory.
 #include "common.h"
+#include "packet_launch.h"
+#include "wave_scan.h"
 #include <algorithm>
 #include <string.h>
 
@@ -37,14 +39,6 @@
 static_assert(sizeof(btbbx_survey_rec) == 64, "btbbx_survey_rec is 64 bytes");
 static_assert(offsetof(btbbx_survey_rec, afh_map) == 12 && offsetof(btbbx_survey_rec, first_stream) == 22 &&
 	      offsetof(btbbx_survey_rec, first_offset) == 56, "btbbx_survey_rec layout (libbtbb_amd.SURVEY_DTYPE)");
-
-// launchers of the packet chain's kernels (packet.hip)
-int launch_gather(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, const btbbx_hit *d_hits, uint32_t n_packets,
-		  const uint32_t *d_count, uint32_t max_length, uint64_t *d_packets, uint32_t *d_lengths, hipStream_t hip_stream);
-int launch_trials(const uint64_t *d_packets, const btbbx_pkt_in *d_in, uint32_t n_packets, const uint32_t *d_count,
-		  btbbx_trial *d_trials, hipStream_t hip_stream);
-int launch_header_flags(const uint64_t *d_packets, const uint32_t *d_lengths, uint32_t n_packets, const uint32_t *d_count,
-			uint8_t *d_present, hipStream_t stream);
 
 struct SurveyChannels {
 	uint8_t ch[SV_CHAN_STREAMS];           // channel of every stream
@@ -89,33 +83,6 @@ static SurveyLayout survey_layout(uint32_t cap)
 }
 
 // ---- workgroup helpers ------------------------------------------------------------------------------
-
-// exclusive prefix sum over the 256 threads of a workgroup; lds: SV_WAVES words; ends with a barrier
-__device__ __forceinline__ uint32_t sv_block_scan(uint32_t v, uint32_t *lds, uint32_t &total)
-{
-	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	uint32_t inc = v;
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const uint32_t up = __shfl_up(inc, d, 64);
-		if (lane >= (uint32_t)d)
-			inc += up;
-	}
-	if (lane == 63)
-		lds[wave] = inc;
-	__syncthreads();
-	uint32_t before = 0, sum = 0;
-#pragma unroll
-	for (uint32_t w = 0; w < SV_WAVES; w++) {
-		const uint32_t t = lds[w];
-		if (w < wave)
-			before += t;
-		sum += t;
-	}
-	total = sum;
-	__syncthreads();
-	return before + inc - v;
-}
 
 __device__ __forceinline__ uint32_t sv_lap_of(uint64_t key) { return (uint32_t)(key >> 40); }
 
@@ -178,7 +145,7 @@ __global__ __launch_bounds__(SV_THREADS) void survey_rows_kernel(uint32_t *hist,
 		const uint32_t i = base + threadIdx.x;
 		const uint32_t v = i < n_blocks ? row[i] : 0;
 		uint32_t sum;
-		const uint32_t ex = sv_block_scan(v, lds, sum);
+		const uint32_t ex = block_exclusive_scan<SV_WAVES>(v, lds, sum);
 		if (i < n_blocks)
 			row[i] = carry + ex;
 		carry += sum;
@@ -198,7 +165,7 @@ __global__ __launch_bounds__(SV_THREADS) void survey_scatter_kernel(const uint64
 	__shared__ uint32_t wcnt[SV_WAVES][256];
 	const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = params[0];
 	uint32_t all;
-	const uint32_t digit_base = sv_block_scan(tot[tid], lds, all);
+	const uint32_t digit_base = block_exclusive_scan<SV_WAVES>(tot[tid], lds, all);
 	run[tid] = digit_base + hist[(size_t)tid * n_blocks + blockIdx.x];
 #pragma unroll
 	for (uint32_t w = 0; w < SV_WAVES; w++)
@@ -284,7 +251,7 @@ __global__ __launch_bounds__(SV_THREADS) void survey_tiles_kernel(uint32_t *tile
 		const uint32_t i = base + threadIdx.x;
 		const uint32_t v = i < n_tiles ? tiles[i] : 0;
 		uint32_t sum;
-		const uint32_t ex = sv_block_scan(v, lds, sum);
+		const uint32_t ex = block_exclusive_scan<SV_WAVES>(v, lds, sum);
 		if (i < n_tiles)
 			tiles[i] = carry + ex;
 		carry += sum;
@@ -311,7 +278,7 @@ __global__ __launch_bounds__(SV_THREADS) void survey_group_kernel(const uint64_t
 		const uint32_t i = blockIdx.x * SV_GRP_TILE + k * SV_THREADS + tid;
 		const bool first = sv_first_of_lap(keys, i, n);
 		uint32_t sum;
-		const uint32_t ex = sv_block_scan(first ? 1u : 0u, lds, sum);
+		const uint32_t ex = block_exclusive_scan<SV_WAVES>(first ? 1u : 0u, lds, sum);
 		const uint32_t gid = carry + ex + (first ? 1u : 0u) - 1u;         // (i < n: some record at or before i is a first one)
 		carry += sum;
 		btbbx_hit h;
@@ -400,7 +367,7 @@ __global__ __launch_bounds__(SV_THREADS) void survey_wtiles_kernel(uint32_t *wti
 		const uint32_t i = base + threadIdx.x;
 		const uint32_t v = i < n_tiles ? wtiles[i] : 0;
 		uint32_t sum;
-		const uint32_t ex = sv_block_scan(v, lds, sum);
+		const uint32_t ex = block_exclusive_scan<SV_WAVES>(v, lds, sum);
 		if (i < n_tiles)
 			wtiles[i] = carry + ex;
 		carry += sum;
@@ -419,7 +386,7 @@ __global__ __launch_bounds__(SV_THREADS) void survey_wlist_kernel(const uint8_t 
 		const uint32_t i = blockIdx.x * SV_GRP_TILE + k * SV_THREADS + tid;
 		const bool has = i < n && present[i];
 		uint32_t sum;
-		const uint32_t at = carry + sv_block_scan(has ? 1u : 0u, lds, sum);
+		const uint32_t at = carry + block_exclusive_scan<SV_WAVES>(has ? 1u : 0u, lds, sum);
 		carry += sum;
 		if (i < n) {
 			wpos[i] = at;

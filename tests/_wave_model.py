@@ -229,7 +229,7 @@ _ADV64INV = None
 
 
 def _adv64inv():
-    """Lane l's constant in the kernel as built (csrc/packet.hip long_payloads): A^(-64 l) as sixteen 16-bit columns, A = one
+    """Lane l's constant in the kernel as built (csrc/packet_stream.h long_payloads): A^(-64 l) as sixteen 16-bit columns, A = one
     zero bit through the register.  Found like the library finds it: run every register value forward over 64 zero bits and
     read the map backwards."""
     global _ADV64INV

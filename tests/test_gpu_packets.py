@@ -272,7 +272,7 @@ def _long_capture(rng, n_packets, n_streams, n_words, others=(synth.TYPE_DM1, sy
 
 def test_long_payloads_leave_through_the_wave_phase():
     """DM3 / DH3 / DM5 / DH5 payloads beyond 256 bits are not walked by a lane but decoded by a group of 8 .. 64 lanes
-    (long_payloads in packet.hip): byte-identical to cutting the packets out and decoding them lane by lane, and equal
+    (long_payloads in packet_stream.h): byte-identical to cutting the packets out and decoding them lane by lane, and equal
     to the oracle -- full lengths, every payload_length mod 8 around the word boundaries, failing FEC 2/3 blocks (the
     reference then writes nothing), wrong clocks (noise through the payload header), unwhitened packets, captures cut
     short by the stream's end and by max_length, and records that hold random bytes on entry."""
@@ -390,7 +390,7 @@ def test_dm5_of_128_bytes_keeps_its_spare_block_bits_to_itself():
 
 
 def test_ev4_ev5_payloads_leave_through_the_wave_phase():
-    """EV4 / EV5 payloads in HBM are decoded by lane groups too (ev_payloads in packet.hip: the byte count whose CRC register
+    """EV4 / EV5 payloads in HBM are decoded by lane groups too (ev_payloads in packet_stream.h: the byte count whose CRC register
     is zero comes from a prefix over the lanes, not from a walk): byte-identical to cutting the packets out and decoding
     them lane by lane, and equal to the oracle -- every body length, symbol errors (EV4: blocks that do not decode, in the
     first 45 symbols and behind them), wrong clocks, captures cut short by max_length and by the next packet, records that
