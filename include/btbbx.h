@@ -22,6 +22,9 @@
  *                        lib/src/bluetooth_packet.c:1198-1297, 1371-1408
  *   btbbx_hop_*       <- gen_hops / hop / init_candidates / channel_winnow / btbb_winnow,
  *                        lib/src/bluetooth_piconet.c:311-362, 443-446, 455-498, 575-645
+ *   btbbx_hop_reversal_batch_*
+ *                     <- btbb_init_hop_reversal + btbb_winnow for many piconets in one call,
+ *                        lib/src/bluetooth_piconet.c:455-498, 575-645
  *   btbbx_le_*        <- the LE search in front of lell_allocate_and_decode (the reference
  *                        expects found, dewhitened bytes), lib/src/bluetooth_le_packet.c:282-312
  *   btbbx_survey_*    <- btbb_uap_from_header under the survey mode of btbb_process_packet,
@@ -487,6 +490,56 @@ int btbbx_hop_reversal_winnow(btbbx_hop_reversal *h, const int32_t *index_offset
 			      uint32_t n_obs, uint32_t *stop, uint32_t *count, uint32_t *cand0);
 int64_t btbbx_hop_reversal_candidates(btbbx_hop_reversal *h, uint32_t *dst, uint64_t cap);  /* ascending */
 void btbbx_hop_reversal_close(btbbx_hop_reversal *h);
+
+/* ---- batch reversal: CLK1-27 of many piconets in one chain ---------------------------- */
+/* One job = one piconet with its observed hops.  Job j, with observations off[0..n) / ch[0..n) =
+ * [obs_first, obs_first + n_obs) of the two shared arrays, leaves exactly what
+ *     r = btbbx_hop_reversal_open(&cfg, clk6, ch[0], aliased, &n_initial);
+ *     btbbx_hop_reversal_winnow(r, off, ch, n, &stop, &count, &cand0);
+ *     btbbx_hop_reversal_candidates(r, dst, cand_cap);
+ * leave: observation 0 is applied by the winnow as well, a channel above 127 matches nothing, an empty
+ * initial list gives stop = 0 / count = 0, stop = n_obs when no observation leaves at most one candidate,
+ * cand0 = the smallest surviving clock (0 when count = 0). */
+typedef struct btbbx_clock_job {        /* 104 bytes */
+	btbbx_hop_cfg cfg;              /* as btbbx_hop_cfg_init leaves it */
+	uint32_t clk6;                  /* known CLK1-6 of the first observation, 0..63 */
+	uint32_t aliased;               /* != 0: compare ((ch + 24) % 25) + 26 */
+	uint32_t obs_first, n_obs;      /* this job's observations: [obs_first, obs_first + n_obs) of the shared arrays */
+} btbbx_clock_job;
+
+typedef struct btbbx_clock_result {     /* 24 bytes */
+	uint32_t status;                /* 0 done, 1 job rejected (every other field is 0 then) */
+	uint32_t n_initial;             /* what btbbx_hop_reversal_open reports in *n_candidates */
+	uint32_t stop, count, cand0;    /* what btbbx_hop_reversal_winnow reports for the job's observations */
+	uint32_t n_stored;              /* min(count, cand_cap) candidates written for this job (0 when d_candidates is NULL) */
+} btbbx_clock_result;
+
+/* Device scratch of a batch of up to job_cap jobs: job_cap * (2 * 1028 + 1) * 4 bytes, rounded up to 256 -- per job a
+ * histogram over the number of observations a candidate agrees with (1025 bins, padded), the smallest clock of every bin,
+ * and one threshold.  It depends neither on cand_cap nor on how many candidates a job has: no candidate list is kept, the
+ * candidates that are asked for are found a second time and go straight to d_candidates.  Host only, no device needed. */
+size_t btbbx_hop_reversal_batch_scratch_bytes(uint32_t job_cap, uint32_t cand_cap);
+/* Works the first min(*d_n_jobs, job_cap) jobs of d_jobs (d_n_jobs == NULL: job_cap jobs); records behind them are not
+ * written.  All pointers are DEVICE pointers; d_index_offsets / d_channels hold n_obs_total observations shared by all jobs
+ * (ranges may overlap).  The ascending first min(count, cand_cap) candidates of job j go to d_candidates[j * cand_cap ..];
+ * the rest of its slots is not written.  d_candidates == NULL or cand_cap == 0: records only.  Three kernels and one memset
+ * (two kernels without candidates) whatever the job count; asynchronous on hip_stream, nothing is synchronised and the job
+ * count never comes to the host.
+ * BTBBX_E_ARG before any launch for: d_jobs, d_results or d_scratch NULL, the observation arrays NULL with n_obs_total != 0,
+ * job_cap == 0 or >= 2^31, scratch too small, a pointer that is not 4-byte aligned (the scratch: 16; the channels: any).
+ * The jobs are checked on the device.  A job with clk6 > 63, n_obs == 0 or n_obs > 1024, obs_first + n_obs > n_obs_total
+ * (computed without wrapping), or cfg.afh != 0 with cfg.used_channels 0 or above 79 gets status = 1 and zeros in its
+ * record; none of its candidate slots is written and its neighbours are not disturbed. */
+int btbbx_hop_reversal_batch_device(const btbbx_clock_job *d_jobs, const uint32_t *d_n_jobs, uint32_t job_cap,
+				    const int32_t *d_index_offsets, const uint8_t *d_channels, uint32_t n_obs_total,
+				    btbbx_clock_result *d_results, uint32_t *d_candidates, uint32_t cand_cap,
+				    void *d_scratch, size_t scratch_bytes, void *hip_stream);
+/* Host wrapper: copy in, the call above with scratch of its own, copy out.  candidates (n_jobs * cand_cap words, may be
+ * NULL) keeps the caller's values in the slots no job writes.  Returns n_jobs or a negative BTBBX_E_*.  Safe to call from
+ * several host threads at once. */
+int64_t btbbx_hop_reversal_batch_host(const btbbx_clock_job *jobs, uint32_t n_jobs,
+				      const int32_t *index_offsets, const uint8_t *channels, uint32_t n_obs_total,
+				      btbbx_clock_result *results, uint32_t *candidates, uint32_t cand_cap);
 
 /* piconet introspection for tests and tools: what the reference keeps in struct btbb_piconet
  * (bluetooth_piconet.h:59-85).  field: 0 num_candidates, 1 winnowed, 2 packets_observed,

@@ -157,6 +157,9 @@ SIGNATURES = {
     "btbbx_hop_reversal_winnow": (C.c_int, [_vp, _vp, _vp, _u32, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "btbbx_hop_reversal_candidates": (C.c_int64, [_vp, _vp, _u64]),
     "btbbx_hop_reversal_close": (None, [_vp]),
+    "btbbx_hop_reversal_batch_scratch_bytes": (C.c_size_t, [_u32, _u32]),
+    "btbbx_hop_reversal_batch_device": (C.c_int, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, C.c_size_t, _vp]),
+    "btbbx_hop_reversal_batch_host": (C.c_int64, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32]),
     "btbbx_piconet_state": (C.c_int64, [_vp, C.c_int]),
     "btbbx_piconet_candidates": (C.c_int64, [_vp, _vp, _u64]),
     "btbbx_le_scan_device": (C.c_int, [_vp, _u64, _u64, _u32, _u64, _u32, C.c_int, _vp, _u32, _vp, _vp]),
@@ -586,6 +589,23 @@ def hop_cfg(lap, uap, afh_map=None):
     return cfg
 
 
+class ClockJob(C.Structure):
+    _fields_ = [("cfg", HopCfg), ("clk6", C.c_uint32), ("aliased", C.c_uint32), ("obs_first", C.c_uint32), ("n_obs", C.c_uint32)]
+
+
+class ClockResult(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("n_initial", C.c_uint32), ("stop", C.c_uint32), ("count", C.c_uint32),
+                ("cand0", C.c_uint32), ("n_stored", C.c_uint32)]
+
+
+# one job / one result of the batch reversal (include/btbbx.h btbbx_clock_job / btbbx_clock_result)
+HOP_CFG_DTYPE = np.dtype([("address", "<u4"), ("afh", "u1"), ("used_channels", "u1"), ("reserved", "u1", (2,)), ("bank", "u1", (80,))])
+CLOCK_JOB_DTYPE = np.dtype([("cfg", HOP_CFG_DTYPE), ("clk6", "<u4"), ("aliased", "<u4"), ("obs_first", "<u4"), ("n_obs", "<u4")])
+CLOCK_RESULT_DTYPE = np.dtype([("status", "<u4"), ("n_initial", "<u4"), ("stop", "<u4"), ("count", "<u4"), ("cand0", "<u4"),
+                               ("n_stored", "<u4")])
+assert CLOCK_JOB_DTYPE.itemsize == C.sizeof(ClockJob) == 104 and CLOCK_RESULT_DTYPE.itemsize == C.sizeof(ClockResult) == 24
+
+
 def hop_sequence(cfg, first=0, count=SEQUENCE_LENGTH):
     """Channels of CLK1-27 values [first, first+count) as a numpy uint8 array (generated in HBM)."""
     buf = DeviceBuffer(count)
@@ -640,3 +660,57 @@ class HopReversal:
         if self.h:
             lib().btbbx_hop_reversal_close(self.h)
             self.h = None
+
+
+def clock_jobs(cfgs, clk6, observations, aliased=False):
+    """The job table and the two shared observation arrays of hop_reversal_batch: (CLOCK_JOB_DTYPE jobs, int32 offsets,
+    uint8 channels).  clk6 and aliased are one value for all jobs or one per job; the observations of job j are laid out
+    one job after the other."""
+    n = len(cfgs)
+    assert len(observations) == n
+    jobs = np.zeros(n, dtype=CLOCK_JOB_DTYPE)
+    jobs["clk6"] = np.broadcast_to(np.asarray(clk6, dtype=np.uint32), (n,))
+    jobs["aliased"] = np.broadcast_to(np.asarray(aliased), (n,)).astype(bool)
+    offs, chans, at = [], [], 0
+    for j, (cfg, (off, ch)) in enumerate(zip(cfgs, observations)):
+        jobs["cfg"][j] = np.frombuffer(bytes(cfg), dtype=HOP_CFG_DTYPE)[0]
+        off, ch = np.asarray(off, dtype=np.int32).reshape(-1), np.asarray(ch, dtype=np.uint8).reshape(-1)
+        assert len(off) == len(ch)
+        jobs["obs_first"][j], jobs["n_obs"][j] = at, len(off)
+        offs.append(off)
+        chans.append(ch)
+        at += len(off)
+    cat = lambda parts, dt: np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0, dt), dtype=dt)
+    return jobs, cat(offs, np.int32), cat(chans, np.uint8)
+
+
+def hop_reversal_batch_raw(jobs, offsets, channels, cand_cap=0, candidates=None):
+    """btbbx_hop_reversal_batch_host over a prepared job table (CLOCK_JOB_DTYPE) and the shared observation arrays ->
+    CLOCK_RESULT_DTYPE records, and the (n_jobs, cand_cap) uint32 candidate slots when cand_cap > 0 (`candidates`: their
+    initial content, zeros if None; slots no job writes keep it)."""
+    jobs = np.ascontiguousarray(jobs, dtype=CLOCK_JOB_DTYPE)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+    channels = np.ascontiguousarray(channels, dtype=np.uint8)
+    assert len(offsets) == len(channels)
+    n = len(jobs)
+    results = np.zeros(max(n, 1), dtype=CLOCK_RESULT_DTYPE)
+    cand = None
+    if cand_cap:
+        cand = np.zeros((max(n, 1), cand_cap), np.uint32) if candidates is None else np.ascontiguousarray(candidates, dtype=np.uint32)
+        assert cand.size >= n * cand_cap and cand.size % cand_cap == 0
+        cand = cand.reshape(-1, cand_cap)
+    check(lib().btbbx_hop_reversal_batch_host(_ptr(jobs), n, _ptr(offsets), _ptr(channels), len(offsets), _ptr(results),
+                                              None if cand is None else _ptr(cand), cand_cap), "btbbx_hop_reversal_batch_host")
+    return (results[:n], cand[:n]) if cand_cap else results[:n]
+
+
+def hop_reversal_batch(cfgs, clk6, observations, aliased=False, cand_cap=0):
+    """CLK1-27 reversal of many piconets in one call (btbbx_hop_reversal_batch_host): job j is the piconet cfgs[j] with
+    CLK1-6 clk6[j] at its first observation and the observed hops observations[j] = (offsets, channels); it leaves what
+    HopReversal(cfgs[j], clk6[j], channels[0], aliased[j]) and .winnow(offsets, channels) report.  Returns the
+    CLOCK_RESULT_DTYPE records -- and, with cand_cap > 0, a list with the first min(count, cand_cap) candidates of every job."""
+    jobs, offsets, channels = clock_jobs(cfgs, clk6, observations, aliased)
+    if not cand_cap:
+        return hop_reversal_batch_raw(jobs, offsets, channels)
+    results, cand = hop_reversal_batch_raw(jobs, offsets, channels, cand_cap)
+    return results, [cand[j, :int(results["n_stored"][j])].copy() for j in range(len(jobs))]

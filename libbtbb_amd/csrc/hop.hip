@@ -33,6 +33,24 @@ struct HopArgs {
 __device__ __host__ constexpr int hop_u(int s) { constexpr int u[14] = {0, 2, 1, 3, 0, 1, 0, 3, 1, 0, 2, 1, 0, 1}; return u[s]; }
 __device__ __host__ constexpr int hop_v(int s) { constexpr int v[14] = {1, 3, 2, 4, 4, 3, 2, 4, 4, 3, 4, 3, 3, 2}; return v[s]; }
 
+// the selection inputs of an address (address_precalc, bluetooth_piconet.c:197-217); the bank is not touched.
+// Host (hop_args) and device (the batch reversal derives them per job) share it.
+__device__ __host__ inline void hop_address_fields(uint32_t address, uint32_t afh, uint32_t used_channels, HopArgs *h)
+{
+	address &= 0xfffffff;
+	h->a1 = (address >> 23) & 0x1f;
+	h->b = (address >> 19) & 0x0f;
+	h->d1 = (address >> 10) & 0x1ff;
+	h->c1 = 0;
+	h->e = 0;
+	for (int i = 0; i < 5; i++)
+		h->c1 |= ((address >> (2 * i)) & 1) << i;
+	for (int i = 0; i < 7; i++)
+		h->e |= ((address >> (2 * i + 1)) & 1) << i;
+	h->afh = afh ? 1 : 0;
+	h->mod = afh ? used_channels : HOP_NCHAN;
+}
+
 __device__ __forceinline__ void hop_build_tab(uint8_t *tab, const HopArgs &h)
 {
 	// every kernel using the table runs 256 lanes per workgroup
@@ -483,6 +501,226 @@ __global__ void hop_first_kernel(const uint32_t *cand, WinnowVerdict *v)
 		v->cand0 = cand[0];
 }
 
+// ---- batch reversal: many piconets in one chain -----------------------------------------------------
+// btbbx_hop_reversal_batch_device.  Job j leaves what open + winnow + candidates of the single path leave, but nothing about a
+// job is known on the host: the jobs, their count and their observations are device data.  So no candidate list is kept.
+// The agreement count of a clock (observations matched before the first mismatch) is a pure function of the clock; pass 1
+// evaluates it for all 2^21 clocks congruent to clk6 and keeps only a histogram over it, with the smallest clock of every bin;
+// pass 2 reads the verdict off the histogram as hop_verdict_kernel does; pass 3 evaluates again for the jobs that are asked
+// for more than one candidate.  Scratch per job: the two rows of HOP_BINS words and the verdict's threshold.
+#define HOP_BINS 1028             // HOP_MAX_OBS + 1 bins, rounded up to 16 bytes
+static_assert(sizeof(btbbx_clock_job) == 104 && offsetof(btbbx_clock_job, clk6) == 88, "btbbx_clock_job layout");
+static_assert(sizeof(btbbx_clock_result) == 24, "btbbx_clock_result layout");
+
+__device__ __forceinline__ uint32_t batch_job_count(const uint32_t *n_jobs, uint32_t job_cap)
+{
+	return n_jobs ? min(*n_jobs, job_cap) : job_cap;
+}
+
+// the rules of include/btbbx.h; a job that fails one is never worked on
+__device__ __forceinline__ bool batch_job_ok(const btbbx_clock_job &j, uint32_t n_obs_total)
+{
+	if (j.clk6 > 63 || j.n_obs == 0 || j.n_obs > HOP_MAX_OBS)
+		return false;
+	if (j.obs_first > n_obs_total || j.n_obs > n_obs_total - j.obs_first)      // obs_first + n_obs without wrapping
+		return false;
+	return !j.cfg.afh || (j.cfg.used_channels >= 1 && j.cfg.used_channels <= HOP_NCHAN);
+}
+
+// the job's bank table, straight from its configuration in global memory; at least 256 lanes, barrier included
+__device__ __forceinline__ void batch_build_tab(uint8_t *tab, const uint8_t *bank, uint32_t mod)
+{
+	if (threadIdx.x < 256) {
+		tab[threadIdx.x] = bank[threadIdx.x % mod];
+		if (threadIdx.x < HOP_TAB - 256)
+			tab[256 + threadIdx.x] = bank[(256 + threadIdx.x) % mod];
+	}
+	__syncthreads();
+}
+
+// observations [0, n) of a job into LDS, channels as the reference's signed chars
+__device__ __forceinline__ void batch_stage_obs(HopObs *obs, const int32_t *offsets, const uint8_t *channels, uint32_t first,
+						uint32_t n)
+{
+	for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+		obs[i].offset = offsets[first + i];
+		obs[i].channel = (int)(int8_t)channels[first + i];
+	}
+}
+
+// observations clock c agrees with before its first mismatch, at most `upto`
+__device__ __forceinline__ uint32_t batch_agree(const HopArgs &h, const uint8_t *tab, const HopObs *obs, uint32_t upto, int aliased,
+						uint32_t c)
+{
+	uint32_t k = 0;
+	for (; k < upto; k++) {
+		const HopObs o = obs[k];
+		const uint32_t idx = (c + (uint32_t)o.offset) & (BTBBX_SEQUENCE_LENGTH - 1);
+		if (hop_observable(tab[hop_tab_index(h, idx)], aliased) != o.channel)
+			break;
+	}
+	return k;
+}
+
+// Pass 1.  Workgroup = (job, tile of the 2^21 groups); a lane takes the clocks clk6 + 64 g of its tile, 256 groups apart.
+// rows[job][0][k] += candidates whose first mismatch is observation k (k = n_obs: none); rows[job][1][k] = the complement of
+// the smallest such clock (a maximum, so that one memset to zero prepares both rows; a clock is below 2^27, its complement
+// is never 0).
+__global__ __launch_bounds__(256) void hop_batch_agree_kernel(const btbbx_clock_job *jobs, const uint32_t *n_jobs, uint32_t job_cap,
+							       uint32_t tiles_log2, const int32_t *offsets, const uint8_t *channels,
+							       uint32_t n_obs_total, uint32_t *rows)
+{
+	__shared__ uint8_t tab[HOP_TAB];
+	__shared__ HopObs obs[HOP_MAX_OBS];
+	__shared__ uint32_t lhist[HOP_MAX_OBS + 1], lfirst[HOP_MAX_OBS + 1];
+	const uint32_t job = blockIdx.x >> tiles_log2, tile = blockIdx.x & ((1u << tiles_log2) - 1);
+	if (job >= batch_job_count(n_jobs, job_cap))
+		return;
+	const btbbx_clock_job &j = jobs[job];
+	if (!batch_job_ok(j, n_obs_total))
+		return;
+	const uint32_t n_obs = j.n_obs, clk6 = j.clk6;
+	const int aliased = j.aliased != 0;
+	HopArgs h;
+	hop_address_fields(j.cfg.address, j.cfg.afh, j.cfg.used_channels, &h);
+	batch_stage_obs(obs, offsets, channels, j.obs_first, n_obs);
+	for (uint32_t k = threadIdx.x; k <= n_obs; k += 256) {
+		lhist[k] = 0;
+		lfirst[k] = 0;
+	}
+	batch_build_tab(tab, j.cfg.bank, h.mod);
+	const int ch0 = obs[0].channel;                         // open(): the candidates are the clocks that hop on ch[0]
+	const uint32_t per = HOP_GROUPS >> tiles_log2;          // a multiple of 256
+	for (uint32_t g = tile * per + threadIdx.x; g < (tile + 1) * per; g += 256) {
+		const uint32_t c = clk6 + 64u * g;
+		if (hop_observable(tab[hop_tab_index(h, c)], aliased) != ch0)
+			continue;
+		const uint32_t k = batch_agree(h, tab, obs, n_obs, aliased, c);
+		atomicAdd(&lhist[k], 1u);
+		atomicMax(&lfirst[k], ~c);
+	}
+	__syncthreads();
+	uint32_t *hist = rows + (size_t)job * 2 * HOP_BINS;
+	for (uint32_t k = threadIdx.x; k <= n_obs; k += 256)
+		if (lhist[k]) {
+			atomicAdd(&hist[k], lhist[k]);
+			atomicMax(&hist[HOP_BINS + k], lfirst[k]);
+		}
+}
+
+// Pass 2.  One workgroup per job: stop / count / keep_above as hop_verdict_kernel takes them from the histogram, n_initial = its
+// total, cand0 = the smallest clock over the bins above keep_above.  Writes the whole result record -- for a rejected job too --
+// and the only candidate of a job that ends with one.
+__global__ __launch_bounds__(1024) void hop_batch_verdict_kernel(const btbbx_clock_job *jobs, const uint32_t *n_jobs, uint32_t job_cap,
+								  uint32_t n_obs_total, const uint32_t *rows, uint32_t *keep_above,
+								  btbbx_clock_result *results, uint32_t *candidates, uint32_t cand_cap)
+{
+	__shared__ uint32_t cum[1024];
+	__shared__ uint32_t first, best;
+	const uint32_t job = blockIdx.x, k = threadIdx.x;
+	if (job >= batch_job_count(n_jobs, job_cap))
+		return;
+	const btbbx_clock_job &j = jobs[job];
+	btbbx_clock_result r = {1, 0, 0, 0, 0, 0};
+	if (!batch_job_ok(j, n_obs_total)) {
+		if (k == 0)
+			results[job] = r;
+		return;
+	}
+	const uint32_t n_obs = j.n_obs;
+	const uint32_t *hist = rows + (size_t)job * 2 * HOP_BINS, *lowest = hist + HOP_BINS;
+	if (k == 0) {
+		first = n_obs;
+		best = 0;
+	}
+	cum[k] = k < n_obs ? hist[k] : 0;
+	__syncthreads();
+	for (uint32_t step = 1; step < 1024; step <<= 1) {
+		const uint32_t x = k >= step ? cum[k - step] : 0;
+		__syncthreads();
+		cum[k] += x;
+		__syncthreads();
+	}
+	const uint32_t n = cum[1023] + hist[n_obs];             // every candidate of open()
+	if (k < n_obs && n - cum[k] <= 1)                       // candidates left after observation k = n - cum[k]
+		atomicMin(&first, k);
+	__syncthreads();
+	const uint32_t last = first < n_obs ? first : n_obs - 1;
+	if (k > last && k < n_obs && lowest[k])
+		atomicMax(&best, lowest[k]);
+	if (k == 0 && lowest[n_obs])                            // bin n_obs has no lane of its own when n_obs = 1024
+		atomicMax(&best, lowest[n_obs]);
+	__syncthreads();
+	if (k == 0) {
+		const bool store = candidates && cand_cap;
+		r.status = 0;
+		r.n_initial = n;
+		r.stop = first;
+		r.count = n - cum[last];
+		r.cand0 = r.count ? ~best : 0;
+		r.n_stored = store ? min(r.count, cand_cap) : 0;
+		results[job] = r;
+		keep_above[job] = last;
+		if (store && r.count == 1)
+			candidates[(size_t)job * cand_cap] = r.cand0;
+	}
+}
+
+// Pass 3, when candidates are asked for.  One workgroup per job that ended with more than one: the survivors are the clocks
+// that agree with observations 0 .. keep_above; they are found again, 1024 groups at a time in ascending order, and
+// written through wave ballots and a prefix over the per-wave counts until min(count, cand_cap) are out.
+__global__ __launch_bounds__(1024) void hop_batch_emit_kernel(const btbbx_clock_job *jobs, const uint32_t *n_jobs, uint32_t job_cap,
+							       const int32_t *offsets, const uint8_t *channels,
+							       const uint32_t *keep_above, const btbbx_clock_result *results,
+							       uint32_t *candidates, uint32_t cand_cap)
+{
+	__shared__ uint8_t tab[HOP_TAB];
+	__shared__ HopObs obs[HOP_MAX_OBS];
+	__shared__ uint32_t wave_cnt[16];
+	__shared__ uint32_t base;
+	const uint32_t job = blockIdx.x, tid = threadIdx.x;
+	if (job >= batch_job_count(n_jobs, job_cap))
+		return;
+	if (results[job].status || results[job].count <= 1)     // rejected, or pass 2 wrote what there was
+		return;
+	const btbbx_clock_job &j = jobs[job];
+	const uint32_t limit = min(results[job].count, cand_cap), need = keep_above[job] + 1, clk6 = j.clk6;
+	const int aliased = j.aliased != 0;
+	HopArgs h;
+	hop_address_fields(j.cfg.address, j.cfg.afh, j.cfg.used_channels, &h);
+	batch_stage_obs(obs, offsets, channels, j.obs_first, need);
+	if (tid == 0)
+		base = 0;
+	batch_build_tab(tab, j.cfg.bank, h.mod);
+	const int ch0 = obs[0].channel;
+	uint32_t *dst = candidates + (size_t)job * cand_cap;
+	for (uint32_t g0 = 0; g0 < HOP_GROUPS; g0 += 1024) {
+		const uint32_t c = clk6 + 64u * (g0 + tid);
+		const bool live = hop_observable(tab[hop_tab_index(h, c)], aliased) == ch0 &&
+				  batch_agree(h, tab, obs, need, aliased, c) == need;
+		const uint64_t m = __ballot(live);
+		if ((tid & 63) == 0)
+			wave_cnt[tid >> 6] = (uint32_t)__popcll(m);
+		__syncthreads();
+		uint32_t at = base;
+		for (uint32_t w = 0; w < (tid >> 6); w++)
+			at += wave_cnt[w];
+		at += (uint32_t)__popcll(m & ((1ull << (tid & 63)) - 1));
+		if (live && at < limit)
+			dst[at] = c;
+		__syncthreads();
+		if (tid == 0) {
+			uint32_t all = 0;
+			for (int w = 0; w < 16; w++)
+				all += wave_cnt[w];
+			base += all;
+		}
+		__syncthreads();
+		if (base >= limit)                              // the same for every lane: the rest is past cand_cap
+			break;
+	}
+}
+
 // ---- host side ------------------------------------------------------------------------
 // hop selection needs a GPU but none of the btbb_init() tables
 static int hop_device()
@@ -505,18 +743,7 @@ static int hop_args(const btbbx_hop_cfg *cfg, HopArgs *h)
 		set_error("hop: NULL configuration");
 		return BTBBX_E_ARG;
 	}
-	const uint32_t address = cfg->address & 0xfffffff;
-	h->a1 = (address >> 23) & 0x1f;
-	h->b = (address >> 19) & 0x0f;
-	h->d1 = (address >> 10) & 0x1ff;
-	h->c1 = 0;
-	h->e = 0;
-	for (int i = 0; i < 5; i++)
-		h->c1 |= ((address >> (2 * i)) & 1) << i;
-	for (int i = 0; i < 7; i++)
-		h->e |= ((address >> (2 * i + 1)) & 1) << i;
-	h->afh = cfg->afh ? 1 : 0;
-	h->mod = cfg->afh ? cfg->used_channels : HOP_NCHAN;
+	hop_address_fields(cfg->address, cfg->afh, cfg->used_channels, h);
 	if (h->mod == 0 || h->mod > 80) {
 		set_error("hop: AFH pattern with %u used channels", h->mod);
 		return BTBBX_E_ARG;
@@ -818,6 +1045,114 @@ int64_t btbbx_hop_reversal_candidates(btbbx_hop_reversal *r, uint32_t *dst, uint
 		HIP_TRY(hipStreamSynchronize(r->w->stream));
 	}
 	return (int64_t)r->n;
+}
+
+
+// rows + thresholds; the same for every cand_cap (no candidate is ever stored outside the caller's d_candidates)
+size_t btbbx_hop_reversal_batch_scratch_bytes(uint32_t job_cap, uint32_t cand_cap)
+{
+	(void)cand_cap;
+	const size_t bytes = (size_t)job_cap * (2 * HOP_BINS + 1) * sizeof(uint32_t);
+	return (bytes + 255) & ~(size_t)255;
+}
+
+int btbbx_hop_reversal_batch_device(const btbbx_clock_job *d_jobs, const uint32_t *d_n_jobs, uint32_t job_cap,
+				    const int32_t *d_index_offsets, const uint8_t *d_channels, uint32_t n_obs_total,
+				    btbbx_clock_result *d_results, uint32_t *d_candidates, uint32_t cand_cap,
+				    void *d_scratch, size_t scratch_bytes, void *hip_stream)
+{
+	const size_t need = btbbx_hop_reversal_batch_scratch_bytes(job_cap, cand_cap);
+	if (!d_jobs || !d_results || !d_scratch || !job_cap || job_cap > 0x7fffffffu || scratch_bytes < need ||
+	    (n_obs_total && (!d_index_offsets || !d_channels))) {
+		set_error("btbbx_hop_reversal_batch_device: null pointer, no jobs (or 2^31 and more), or scratch of %zu bytes needed and "
+			  "%zu given", need, scratch_bytes);
+		return BTBBX_E_ARG;
+	}
+	if (((uintptr_t)d_jobs & 3) || ((uintptr_t)d_n_jobs & 3) || ((uintptr_t)d_index_offsets & 3) || ((uintptr_t)d_results & 3) ||
+	    ((uintptr_t)d_candidates & 3) || ((uintptr_t)d_scratch & 15)) {
+		set_error("btbbx_hop_reversal_batch_device: misaligned pointer (scratch 16 bytes, everything else but the channels 4)");
+		return BTBBX_E_ARG;
+	}
+	int rc = hop_device();
+	if (rc)
+		return rc;
+	hipStream_t q = (hipStream_t)hip_stream;
+	uint32_t *rows = (uint32_t *)d_scratch, *keep = rows + (size_t)job_cap * 2 * HOP_BINS;
+	// tiles per job: enough workgroups for the device from a few jobs, long tiles (the table and the observations are
+	// staged once per workgroup) from many
+	uint32_t tiles_log2 = 9;
+	while (tiles_log2 > 4 && ((uint64_t)job_cap << tiles_log2) > 16384)
+		tiles_log2--;
+	while (tiles_log2 && ((uint64_t)job_cap << tiles_log2) > 0x7fffffffu)
+		tiles_log2--;
+	HIP_TRY(hipMemsetAsync(rows, 0, (size_t)job_cap * 2 * HOP_BINS * sizeof(uint32_t), q));
+	hipLaunchKernelGGL(hop_batch_agree_kernel, dim3(job_cap << tiles_log2), dim3(256), 0, q, d_jobs, d_n_jobs, job_cap, tiles_log2,
+			   d_index_offsets, d_channels, n_obs_total, rows);
+	hipLaunchKernelGGL(hop_batch_verdict_kernel, dim3(job_cap), dim3(1024), 0, q, d_jobs, d_n_jobs, job_cap, n_obs_total, rows, keep,
+			   d_results, d_candidates, cand_cap);
+	if (d_candidates && cand_cap)
+		hipLaunchKernelGGL(hop_batch_emit_kernel, dim3(job_cap), dim3(1024), 0, q, d_jobs, d_n_jobs, job_cap, d_index_offsets,
+				   d_channels, keep, d_results, d_candidates, cand_cap);
+	HIP_TRY(hipGetLastError());
+	return BTBBX_OK;
+}
+
+int64_t btbbx_hop_reversal_batch_host(const btbbx_clock_job *jobs, uint32_t n_jobs, const int32_t *index_offsets,
+				      const uint8_t *channels, uint32_t n_obs_total, btbbx_clock_result *results,
+				      uint32_t *candidates, uint32_t cand_cap)
+{
+	if ((n_jobs && (!jobs || !results)) || n_jobs > 0x7fffffffu || (n_obs_total && (!index_offsets || !channels))) {
+		set_error("btbbx_hop_reversal_batch_host: null pointer or 2^31 jobs and more");
+		return BTBBX_E_ARG;
+	}
+	int rc = hop_device();
+	if (rc)
+		return rc;
+	if (!n_jobs)
+		return 0;
+	// one device block and one stream per call: concurrent callers share nothing
+	size_t off = 0;
+	auto carve = [&off](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+	const size_t want_cand = candidates ? (size_t)n_jobs * cand_cap * sizeof(uint32_t) : 0;
+	const size_t scratch_bytes = btbbx_hop_reversal_batch_scratch_bytes(n_jobs, cand_cap);
+	const size_t o_scr = carve(scratch_bytes), o_jobs = carve((size_t)n_jobs * sizeof(*jobs));
+	const size_t o_res = carve((size_t)n_jobs * sizeof(*results)), o_off = carve((size_t)n_obs_total * sizeof(int32_t));
+	const size_t o_ch = carve(n_obs_total), o_cand = carve(want_cand);
+	char *d = nullptr;
+	hipStream_t q = nullptr;
+	if (hipMalloc((void **)&d, off) != hipSuccess) {
+		(void)hipGetLastError();
+		set_error("btbbx_hop_reversal_batch_host: %zu bytes of device memory for %u jobs not available", off, n_jobs);
+		return BTBBX_E_NOMEM;
+	}
+	hipError_t e = hipStreamCreateWithFlags(&q, hipStreamNonBlocking);
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(d + o_jobs, jobs, (size_t)n_jobs * sizeof(*jobs), hipMemcpyHostToDevice, q);
+	if (e == hipSuccess && n_obs_total)
+		e = hipMemcpyAsync(d + o_off, index_offsets, (size_t)n_obs_total * sizeof(int32_t), hipMemcpyHostToDevice, q);
+	if (e == hipSuccess && n_obs_total)
+		e = hipMemcpyAsync(d + o_ch, channels, n_obs_total, hipMemcpyHostToDevice, q);
+	// the caller's candidate slots go in first, so that the slots no job writes come back as they were
+	if (e == hipSuccess && want_cand)
+		e = hipMemcpyAsync(d + o_cand, candidates, want_cand, hipMemcpyHostToDevice, q);
+	if (e == hipSuccess) {
+		rc = btbbx_hop_reversal_batch_device((const btbbx_clock_job *)(d + o_jobs), nullptr, n_jobs, (const int32_t *)(d + o_off),
+						     (const uint8_t *)(d + o_ch), n_obs_total, (btbbx_clock_result *)(d + o_res),
+						     want_cand ? (uint32_t *)(d + o_cand) : nullptr, cand_cap, d + o_scr, scratch_bytes, q);
+		if (!rc)
+			e = hipMemcpyAsync(results, d + o_res, (size_t)n_jobs * sizeof(*results), hipMemcpyDeviceToHost, q);
+		if (!rc && e == hipSuccess && want_cand)
+			e = hipMemcpyAsync(candidates, d + o_cand, want_cand, hipMemcpyDeviceToHost, q);
+	}
+	const hipError_t f = q ? hipStreamSynchronize(q) : hipSuccess;
+	if (q)
+		(void)hipStreamDestroy(q);
+	(void)hipFree(d);
+	if (rc)
+		return rc;
+	HIP_TRY(e);
+	HIP_TRY(f);
+	return (int64_t)n_jobs;
 }
 
 } // extern "C"
