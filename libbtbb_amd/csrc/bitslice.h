@@ -1,4 +1,4 @@
-// bitslice.h -- bit-slice primitives and the three "mismatch count <= limit" networks of the pattern scans (scan.hip: known
+// bitslice.h -- bit-slice primitives and the three "mismatch count <= limit" networks of the pattern scans (scan_known.h: known
 // LAP, le.hip: LE access address).  A 32-bit word is one plane: bit p belongs to offset p of a chain of 32 offsets.
 // For the device the primitives are the gfx950 instructions the kernels were measured with; for the host (no HIP headers
 // needed) plain C++ with the same results: tests/c/bitslice_check.cpp runs the networks that ship over every input.

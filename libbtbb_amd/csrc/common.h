@@ -59,7 +59,7 @@ struct ScanTables {
 	uint32_t bitmap2_shift;    // index = (low32 * golden) >> shift
 };
 
-// Segment slots of the ordered LAP_ANY scan (scan.hip scan_slide_kernel<..., ORD> fills them, sort.hip lays them out and compacts them)
+// Segment slots of the ordered LAP_ANY scan (scan_slide.h scan_slide_kernel<..., ORD> fills them, sort.hip lays them out and compacts them)
 struct ScanSlots {
 	uint64_t *slots;           // [segments][slot_n], 8 bytes each (ScanArgs::seg_slots)
 	uint32_t seg_offsets;      // offsets a segment covers: 4032 (LAP_ANY: 63 words) or 4096 (known LAP)
@@ -116,6 +116,8 @@ int ctx_require();                       // BTBBX_OK or error (sets last error)
 void ctx_scan_snapshot(ScanTables *tables, int *table_errors);   // the current device's scan tables as one consistent set (a re-init may run beside the caller)
 void set_error(const char *fmt, ...);
 int hip_fail(hipError_t e, const char *what);
+// the checks every scan entry makes of its streams (scan_host.cpp); `window` = bits of the pattern (64: access code, 40: LE preamble + AA)
+int check_scan_args(const char *who, int window, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, uint64_t search_bits);
 
 // Scratch memory, pinned staging and a stream for ONE host call.  A CallScope at the top of an entry
 // point leases a buffer set of the current device for the calling thread (nested scopes share the

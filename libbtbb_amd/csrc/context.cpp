@@ -360,7 +360,7 @@ static int build_slide_set(const HostTables &t, int max_ac_errors, std::vector<u
 // The two sets of scan_slide_kernel's two-level form (tables for three and four errors; slide.h), laid out as the kernel reads
 // them.  first: 2^SLIDE4_BITS bits over SLIDE4_TAPS for the LDS.  An idle chain of the kernel indexes 0 or 1, and with four
 // errors the all-zero value of these twenty checks IS a sum of four columns and PN's -- its complement is not: the kernel runs
-// on the COMPLEMENTED check stream (Slide4::INVERT in scan.hip), so member i stands at index ~i here.  second: 2^SLIDE4B_BITS
+// on the COMPLEMENTED check stream (Slide4::INVERT in scan_slide.h), so member i stands at index ~i here.  second: 2^SLIDE4B_BITS
 // bits over SLIDE4B_TAPS, read from L2 one word per look-up: member bit of index i at bit 31 - (i & 31) of word i >> 5 (a left
 // shift by i brings it to the sign).
 static int build_two_level_sets(const HostTables &t, int max_ac_errors, std::vector<uint32_t> &first, std::vector<uint32_t> &second)

@@ -17,7 +17,7 @@
 // and idx(o) ^ K (K = the same checks over PN) is the XOR of at most max_ac_errors columns for a window
 // the reference accepts -- a 2^19-bit set, the candidate bitmap of the survivor loop.  It replaces the
 // two syndrome-table reads and the window extraction per survivor; the exact rule still runs on the
-// candidates (scan.hip verify_lap_any).
+// candidates (scan_core.h verify_lap_any).
 #pragma once
 #include <stdint.h>
 
@@ -88,7 +88,7 @@ constexpr uint64_t remainder_of(uint64_t g)
 // codeword of length 64 does not hold, checks 1 .. 33 do)
 constexpr uint64_t SLIDE_TAPS = slide::lightest_check(0260534236651ULL, SLIDE_SPAN) << 1;
 
-// Tables for FOUR errors (scan_slide4 in scan.hip).  263 247 of the 2^19 values of the nineteen checks above are sums of at
+// Tables for FOUR errors (Slide4 in scan_slide.h).  263 247 of the 2^19 values of the nineteen checks above are sums of at
 // most four columns -- half of all survivors would pass -- and no set that fits the LDS can do much better (397 k patterns against
 // 2^20 .. 2^21 bits).  So the kernel for four errors runs one workgroup per CU with a 2^20-bit set over TWENTY checks (the
 // lightest multiple of degree <= 36: 31.8 % pass) and sends those through a second level in L2: twenty-four positions of a

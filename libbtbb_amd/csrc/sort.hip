@@ -24,6 +24,7 @@
 #include <mutex>
 #include <vector>
 #include "common.h"
+#include "scan_launch.h"
 #include "wave_scan.h"
 
 struct __attribute__((aligned(16))) HitRec { uint64_t a, b; };      // a btbbx_hit as an opaque 16-byte value
@@ -531,7 +532,7 @@ __global__ __launch_bounds__(1024) void order_single_kernel(const btbbx_hit *lis
 
 // ---- segment slots: the ordered LAP_ANY scan without a sort (round 6) ------------------------------------------------------
 //
-// scan_slide_kernel<..., ORD> (scan.hip) leaves every hit in a slot of its SEGMENT -- the 63 words of a tile one wave owns, 4032
+// scan_slide_kernel<..., ORD> (scan_slide.h) leaves every hit in a slot of its SEGMENT -- the 63 words of a tile one wave owns, 4032
 // offsets -- at its rank among the segment's hits, and the segment's count in cnt[segment]: plain stores next to each other in
 // stream order, which the L2 of the XCD that works on that part of the stream merges into whole lines.  The list in (stream, offset)
 // order is then a COMPACTION of the slots: counts -> prefix -> one copy, every read and write coalesced; no bucket atomics in the
@@ -876,11 +877,7 @@ extern "C" int btbbx_order_scan_hits_device(btbbx_hit *d_hits, const uint32_t *d
 // Scan and order in one call: the scan kernels count every record they write in its bucket (one more atomic beside the
 // record, no pass over the list afterwards), then scan of the counts, scatter, rank as above.  The arguments are
 // btbbx_scan_device's plus the ordering scratch; d_hits comes back in (stream, offset) order, *d_count as btbbx_scan_device
-// leaves it.  Nothing is synchronised.
-int launch_scan(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, uint64_t search_bits,
-		uint32_t lap, int max_ac_errors, btbbx_hit *d_hits, uint32_t hit_cap, uint32_t *d_hit_count,
-		unsigned long long *d_first, hipStream_t stream, uint32_t *bucket_cnt, uint64_t bucket_mul, uint32_t bucket_shift, bool msb,
-		const ScanSlots *slots, const uint32_t *gate);
+// leaves it.  Nothing is synchronised.  (launch_scan: scan_launch.h)
 
 // The fallback of the segment slots -- the general path, every launch of it gated on SlotHeader::irregular -- is seven launches that
 // return at once for any stream but one made of sync words, 4.7 us each when they queue behind one another: 33 us of a 0.6 ms
@@ -936,7 +933,6 @@ static void side_pool_release()                            // btbbx_shutdown
 }
 
 // ---- segment slots: layout behind the general ordering's scratch (which the fallback uses) ----
-bool scan_slot_geometry(uint64_t search_bits, uint32_t n_streams, uint32_t lap, uint32_t *segs_per_stream, uint64_t *n_segs);
 
 struct SlotLayout { size_t header, cnt, sums, seg_start, slots, ovf_recs, ovf_meta, total; uint32_t n_segs, n_blocks, ovf_cap, segs_per_stream; };
 static SlotLayout slot_layout(size_t front, uint32_t segs_per_stream, uint64_t n_segs, uint32_t cap)

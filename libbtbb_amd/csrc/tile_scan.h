@@ -1,6 +1,6 @@
-// tile_scan.h -- what the two-words-per-lane pattern scans share (scan.hip scan_known_lap_kernel, le.hip le_scan_kernel:
+// tile_scan.h -- what the two-words-per-lane pattern scans share (scan_known.h scan_known_lap_kernel, le.hip le_scan_kernel:
 // 256-lane workgroups stride over 512-word tiles of one stream at a time): the fetch of a lane's run, the launchers' tile
-// arithmetic and the argument checks.  NOT shared, on purpose: the (stream, tile) cursor, the cut of a ragged tile's masks
+// arithmetic (their argument checks: check_scan_args, common.h).  NOT shared, on purpose: the (stream, tile) cursor, the cut of a ragged tile's masks
 // and the hit ring.  As functions they change the generated code of kernels that were tuned by measurement (selects for
 // the masks' branches, another loop rotation, ring cursors in other registers: profiles/r07_frame), so each kernel keeps them.
 #pragma once
@@ -33,25 +33,6 @@ __device__ __forceinline__ void fetch_run(const Args &a, uint32_t ft, uint32_t f
 	nw[0] = ((uint64_t)v.y << 32) | v.x;
 	nw[1] = ((uint64_t)v.w << 32) | v.z;
 	nw[2] = ((uint64_t)w.y << 32) | w.x;
-}
-
-// the checks every scan entry makes of its streams; `window` = bits of the pattern (64: access code, 40: LE preamble + AA)
-inline int check_scan_args(const char *who, int window, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, uint64_t search_bits)
-{
-	if (n_streams == 0 || n_streams > 65535) {
-		set_error("%s: n_streams must be 1..65535", who);
-		return BTBBX_E_ARG;
-	}
-	if (n_streams > 1 && pitch_words < n_words) {
-		set_error("%s: pitch_words < n_words", who);
-		return BTBBX_E_ARG;
-	}
-	if (n_words > (1ull << 40) || search_bits + (window - 1) > n_words * 64) {
-		set_error("%s: search_bits + %d exceeds the stream (%llu > %llu bits)", who, window - 1,
-			  (unsigned long long)(search_bits + (window - 1)), (unsigned long long)(n_words * 64));
-		return BTBBX_E_ARG;
-	}
-	return BTBBX_OK;
 }
 
 // tiles and grid of one launch: eight workgroups per CU stride over the tiles of all streams

@@ -11,7 +11,7 @@ HALO_BITS = 63            # an access code starting at the last owned offset end
 
 
 def plan_py(total_search_bits, world):
-    """The same arithmetic as btbbx_shard_plan (csrc/scan.hip), in Python: for hosts that plan without a GPU runtime
+    """The same arithmetic as btbbx_shard_plan (csrc/scan_host.cpp), in Python: for hosts that plan without a GPU runtime
     (the C library needs libamdhip64 to load).  tests/test_sharding_gloo.py holds the two against each other."""
     words_total = (total_search_bits + 63) // 64
     per = (words_total + world - 1) // world

@@ -1,4 +1,4 @@
-"""The arithmetic of scan_known_lap_kernel's bit-sliced filter (libbtbb_amd/csrc/scan.hip, second half of round 6), modelled in numpy
+"""The arithmetic of scan_known_lap_kernel's bit-sliced filter (libbtbb_amd/csrc/scan_known.h, second half of round 6), modelled in numpy
 and held against its definition on the CPU -- what the GPU tests can only observe as "same hit list":
 
   * the filter counts mismatches in sync-word bits 24..31 and 56..63 (sixteen planes; twelve -- 28..31 and 56..63 -- for limits 0 / 1);

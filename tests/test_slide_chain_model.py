@@ -1,4 +1,4 @@
-"""The arithmetic of the round-5 survivor pass of scan_slide_kernel (libbtbb_amd/csrc/scan.hip), modelled in numpy and held
+"""The arithmetic of the round-5 survivor pass of scan_slide_kernel (libbtbb_amd/csrc/scan_slide.h), modelled in numpy and held
 against the straightforward form on the CPU -- what the GPU tests can only observe as "same hit list":
 
   * (the two-level form; the one-level form until the third session of round 6) a chain of 32 offsets as a pair of shift registers: the survivor mask and the 64-bit check register are moved down by

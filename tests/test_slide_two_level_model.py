@@ -1,4 +1,4 @@
-"""Round 5's last two changes to scan_slide_kernel (libbtbb_amd/csrc/scan.hip), restated in numpy and held against their definitions on
+"""Round 5's last two changes to scan_slide_kernel (libbtbb_amd/csrc/scan_slide.h), restated in numpy and held against their definitions on
 the CPU -- the GPU tests see them only as "same hit list":
 
   * the tile geometry: a wave owns 63 words of a tile (12 x 63 = 756 words, 16 x 63 = 1008 in the two-level form), its lane 63 works on the

@@ -64,7 +64,7 @@ for name, per_word in (("two chains per word from both ends", two_ended), ("two 
     fixed6 = np.maximum(passes, 6)
     print("%-52s passes/trip %5.2f  with six fixed passes %5.2f  tail in %4.1f %% of the trips  density %.0f %%"
           % (name, passes.mean(), fixed6.mean(), 100 * (passes > 6).mean(), 100 * nw[:len(w) * 128].sum() / (fixed6.sum() * 256.0)))
-# What they cost (csrc/scan.hip, the pass of round 5: 8 vector instructions per chain and pass, 24.8 issue cycles -- v_ffbl 4.2,
+# What they cost (csrc/scan_slide.h, the pass of round 5: 8 vector instructions per chain and pass, 24.8 issue cycles -- v_ffbl 4.2,
 # v_lshrrev_b64 4.2, two shifts and two ands 9.6, v_lshlrev 2.4, v_cmp 4.4; tools/valu_rate.hip):
 #  * a chain that may cross the middle of its word walks a 64-bit survivor mask: the 32-bit shift of the mask becomes a second
 #    v_lshrrev_b64 (+1.8 cycles), and v_ffbl of the low dword alone must not run past an empty dword -- a v_min or a planted
