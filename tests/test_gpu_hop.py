@@ -1,4 +1,4 @@
-"""GPU parity for hop selection and the CLK1-27 reversal (hop.hip, piconet.cpp) against the
+"""GPU parity for hop selection and the CLK1-27 reversal (hop.hip with hop_sequence.h and hop_reversal.h, piconet.cpp) against the
 oracle's materialised 2^27-entry patterns, against the fixture recorded from the reference
 (tests/golden/hop.json), and end to end through btbb_process_packet."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""GPU parity of the batch CLK1-27 reversal (btbbx_hop_reversal_batch_*, hop.hip) with the single-piconet path
+"""GPU parity of the batch CLK1-27 reversal (btbbx_hop_reversal_batch_*, hop_batch.h) with the single-piconet path
 (btbbx_hop_reversal_open / _winnow / _candidates, pinned to the oracle and to the reference's traces by test_gpu_hop.py),
 with the traces recorded from the reference (tests/golden/hop.json), and its handling of rejected jobs, of a job count
 that lives in device memory and of a job whose candidates would not fit any scratch."""
