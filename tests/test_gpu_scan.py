@@ -529,7 +529,10 @@ def test_device_hit_order_with_the_count_in_hbm():
     """btbbx_order_hits_device: the list's length is read from device memory (the scan's own counter), the scratch
     is the caller's, nothing is synchronised in between.  Cases: sparse multi-stream lists, a crowded bucket (runs of
     consecutive offsets: the presence-bitmap path), a short list over a huge key space with more than 48 records in
-    one bucket (the all-pairs path), repeated keys, a count above / below the capacity, empty and one-record lists."""
+    one bucket (the all-pairs path), repeated keys, a count above / below the capacity, empty and one-record lists.
+    (The bitmap cases here have buckets of 2^14 and 2^17 keys: one window, from window 0.  Buckets wider than 2^20 keys -- several
+    windows, skipped and empty ones, the span exit -- and the population edges are test_gpu_order_lattice.py's, on the lattice
+    of _order_model.py.)"""
     lib = bt.lib()
     rng = np.random.default_rng(_libs.seed(11))
 
