@@ -29,6 +29,9 @@
  *                        expects found, dewhitened bytes), lib/src/bluetooth_le_packet.c:282-312
  *   btbbx_survey_*    <- btbb_uap_from_header under the survey mode of btbb_process_packet,
  *                        lib/src/bluetooth_piconet.c:648-750, 807-858
+ *   btbbx_survey_clock_jobs_device, btbbx_acquire_host
+ *                     <- the step from a settled piconet to its hop reversal in btbb_process_packet / try_hop,
+ *                        lib/src/bluetooth_piconet.c:489-490, 510-515, 528-531
  */
 #ifndef INCLUDED_BTBBX_H
 #define INCLUDED_BTBBX_H
@@ -540,6 +543,63 @@ int btbbx_hop_reversal_batch_device(const btbbx_clock_job *d_jobs, const uint32_
 int64_t btbbx_hop_reversal_batch_host(const btbbx_clock_job *jobs, uint32_t n_jobs,
 				      const int32_t *index_offsets, const uint8_t *channels, uint32_t n_obs_total,
 				      btbbx_clock_result *results, uint32_t *candidates, uint32_t cand_cap);
+
+/* ---- clock acquisition from a capture: survey records -> jobs of the batch reversal ------------- */
+/* Builds, on the device, the job table and the two observation arrays btbbx_hop_reversal_batch_device takes from the
+ * records of a survey and the survey's own scratch, so that scan -> survey -> this call -> batch reversal is one chain on one
+ * stream with no synchronisation between the calls.
+ * Record g (g < min(*d_rec_count, rec_cap); d_rec_count == NULL: rec_cap records) gets a job iff it is settled (settled_by != 0),
+ * in record order, that is ascending LAP.  Its observations: with W = the header-bearing packets of the LAP in ascending (offset,
+ * stream), the survey's walk stopped at W[n_walked - 1] with packets_observed packets remembered since the last reset, so the
+ * run btbb_init_hop_reversal + btbb_winnow see when the piconet settles (bluetooth_piconet.c:528-531) is W[n_walked -
+ * packets_observed .. n_walked), and every later packet of W is what try_hop appends (:510-515): the job gets W[n_walked -
+ * packets_observed .. end), cut to its first max_obs.  Observation: index_offset = (int32_t)(clock - first_pkt_time) (:511, :664),
+ * channel = channels[stream] (the stream index when channels is NULL).  Job: clk6 = (clk_offset + first_pkt_time) & 0x3f (:489);
+ * cfg as btbbx_hop_cfg_init(&cfg, (uap << 24 | lap) & 0xfffffff, NULL) leaves it -- with BTBBX_JOBS_AFH as
+ * btbbx_hop_cfg_init(&cfg, address, rec.afh_map) leaves it: AFH over the channels the survey saw; aliased = 1 with
+ * BTBBX_JOBS_ALIASED; obs_first = the exclusive prefix of n_obs over the jobs, so the ranges are disjoint and in job order.
+ *
+ * d_survey_scratch: the scratch of the btbbx_survey_hits_device call that wrote d_recs -- the same cap, not modified since,
+ * this call ordered after that one.  It is READ, never written: several calls (other flags, other max_obs) may follow one
+ * survey.  channels (a HOST pointer, may be NULL) and n_streams as given to the survey.
+ * *d_n_jobs counts ALL settled records; when it exceeds job_cap the first job_cap jobs in record order are stored with their
+ * observations and nothing behind them is written.  d_job_rec (may be NULL): the record index of every stored job.
+ * d_obs_hits (may be NULL): per observation, the index into the survey's d_hits.  *d_n_obs (may be NULL): observations
+ * written.  A packet belongs to one LAP, so obs_cap >= cap entries always suffice.  Two kernels, asynchronous on hip_stream,
+ * nothing is read back; the output with d_n_jobs as its count is a valid input of btbbx_hop_reversal_batch_device
+ * (n_obs_total = obs_cap).
+ * BTBBX_E_ARG before any launch for: d_recs, d_jobs, d_n_jobs, the scratch or one of the two observation arrays NULL,
+ * survey_scratch_bytes < btbbx_survey_scratch_bytes(cap), obs_cap < cap, max_obs 0 or above 1024 (the batch reversal's limit),
+ * job_cap == 0, unknown flag bits, a channel above 78, more than 79 streams without a table (256 with one), a pointer that
+ * is not 4-byte aligned (the scratch: 16; the channels: any). */
+#define BTBBX_JOBS_AFH     1u
+#define BTBBX_JOBS_ALIASED 2u
+int btbbx_survey_clock_jobs_device(const btbbx_survey_rec *d_recs, const uint32_t *d_rec_count, uint32_t rec_cap,
+				   const void *d_survey_scratch, size_t survey_scratch_bytes, uint32_t cap,
+				   const uint8_t *channels, uint32_t n_streams, uint32_t flags, uint32_t max_obs,
+				   btbbx_clock_job *d_jobs, uint32_t job_cap, uint32_t *d_n_jobs, uint32_t *d_job_rec,
+				   int32_t *d_index_offsets, uint8_t *d_channels, uint32_t *d_obs_hits,
+				   uint32_t obs_cap, uint32_t *d_n_obs, void *hip_stream);
+/* Host wrapper: "capture in, (LAP, UAP, CLK1-27) of every piconet out".  Copy in, scan (ordered, repeated with room when the
+ * first buffer was too small, as btbbx_survey_host does), survey, job builder and batch reversal on one stream, copy out.
+ * The first thirteen arguments and the return value are those of btbbx_survey_host (clk6_candidates = its candidates).
+ * job_rec[j] = the record of job j, results[j] its btbbx_clock_result, jobs (may be NULL) the job table itself; *n_jobs counts
+ * all settled piconets among the stored records, min(*n_jobs, job_cap) jobs are written.  candidates (job_cap * cand_cap
+ * words, may be NULL) as in btbbx_hop_reversal_batch_host.  The batch reversal's scratch is about 8 KiB per job, so the wrapper
+ * reads the number of jobs back before it -- in the same transfer and wait in which btbbx_survey_host reads the number of
+ * piconets; that is the only point between the scan and the results where the host waits.  The device entries stay fully
+ * asynchronous.  Safe to call from several host threads at once.
+ * A result with count == 1 gives CLK1-27 of the run's first packet: cand0.  The reference's CLKN offset (what
+ * btbb_piconet_get_clk_offset reports once BTBB_CLK27_VALID is set, bluetooth_piconet.c:598) follows as
+ *     (cand0 << 1) - (first_pkt_time << 1)
+ * with first_pkt_time of the job's record. */
+int64_t btbbx_acquire_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			   uint64_t search_bits, int max_ac_errors, const uint8_t *channels,
+			   uint32_t clkn0, uint32_t clk_div, uint32_t clk_phase,
+			   btbbx_survey_rec *recs, uint64_t rec_cap, int16_t *clk6_candidates,
+			   uint32_t flags, uint32_t max_obs,
+			   btbbx_clock_job *jobs, uint32_t *job_rec, btbbx_clock_result *results, uint64_t job_cap,
+			   uint64_t *n_jobs, uint32_t *candidates, uint32_t cand_cap);
 
 /* piconet introspection for tests and tools: what the reference keeps in struct btbb_piconet
  * (bluetooth_piconet.h:59-85).  field: 0 num_candidates, 1 winnowed, 2 packets_observed,

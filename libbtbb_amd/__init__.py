@@ -169,6 +169,10 @@ SIGNATURES = {
     "btbbx_survey_hits_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp,
                                            _vp, C.c_size_t, _vp]),
     "btbbx_survey_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, C.c_int, _vp, _u32, _u32, _u32, _vp, _u64, _vp]),
+    "btbbx_survey_clock_jobs_device": (C.c_int, [_vp, _vp, _u32, _vp, C.c_size_t, _u32, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp,
+                                                 _vp, _vp, _vp, _u32, _vp, _vp]),
+    "btbbx_acquire_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, C.c_int, _vp, _u32, _u32, _u32, _vp, _u64, _vp, _u32, _u32,
+                                       _vp, _vp, _vp, _u64, _vp, _vp, _u32]),
     # ---- btbb.h
     "btbb_init": (C.c_int, [C.c_int]),
     "btbb_get_release": (C.c_char_p, []),
@@ -714,3 +718,101 @@ def hop_reversal_batch(cfgs, clk6, observations, aliased=False, cand_cap=0):
         return hop_reversal_batch_raw(jobs, offsets, channels)
     results, cand = hop_reversal_batch_raw(jobs, offsets, channels, cand_cap)
     return results, [cand[j, :int(results["n_stored"][j])].copy() for j in range(len(jobs))]
+
+
+# ---- clock acquisition from a capture: survey -> job builder -> batch reversal ---------------
+JOBS_AFH, JOBS_ALIASED = 1, 2
+
+
+def run_survey_clock_jobs(stream_words, hits, entry, channels=None, clk_div=625, clk_phase=0, max_length=MAX_SYMBOLS, count=None,
+                          flags=0, max_obs=1024, rec_cap=None, job_cap=None, rec_count=True, sentinel=0, pitch_words=None,
+                          n_words=None, reversal=False):
+    """btbbx_survey_hits_device and btbbx_survey_clock_jobs_device chained on device buffers (the builder reads the survey's
+    scratch) -> dict(n_recs, recs, n_jobs, n_obs, jobs, job_rec, offsets, channels, obs_hits): the counts as the device left
+    them, every array WHOLE (job_cap jobs, len(hits) observations) over a fill of `sentinel` bytes, so that a caller sees what
+    was not written.  rec_count=False hands the builder a NULL d_rec_count.  reversal=True appends
+    btbbx_hop_reversal_batch_device with the device's job count and adds `results` (job_cap CLOCK_RESULT_DTYPE records)."""
+    stream_words = np.ascontiguousarray(stream_words, dtype=np.uint64)
+    n_streams, pitch = stream_words.shape
+    pitch_words = pitch if pitch_words is None else pitch_words
+    n_words = pitch_words if n_words is None else n_words
+    cap = len(hits)
+    rec_cap = cap if rec_cap is None else rec_cap
+    job_cap = max(rec_cap, 1) if job_cap is None else job_cap
+    table = _channel_table(channels, n_streams)
+    tp = None if table is None else _ptr(table)
+    entry = np.ascontiguousarray(np.asarray(entry, dtype=PKTIN_DTYPE).reshape(1))
+    scratch_bytes = lib().btbbx_survey_scratch_bytes(cap)
+    bufs = []
+
+    def dev(nbytes, fill=None):
+        bufs.append(DeviceBuffer(nbytes))
+        if fill is not None:
+            check(lib().btbbx_memset(bufs[-1].ptr, fill, max(nbytes, 8)), "memset")
+        return bufs[-1]
+    try:
+        d_w = dev(stream_words.nbytes + 16).upload(stream_words)
+        d_h = dev(max(hits.nbytes, 16)).upload(np.ascontiguousarray(hits))
+        d_cnt = dev(8).upload(np.array([0 if count is None else count, 0], dtype=np.uint32))
+        d_recs = dev(max(rec_cap, 1) * SURVEY_DTYPE.itemsize, 0)
+        d_nrec = dev(8, 0)
+        d_scr = dev(scratch_bytes)
+        d_jobs = dev(job_cap * CLOCK_JOB_DTYPE.itemsize, sentinel)
+        d_jrec = dev(job_cap * 4, sentinel)
+        d_off, d_ch, d_oh = dev(max(cap, 1) * 4, sentinel), dev(max(cap, 1), sentinel), dev(max(cap, 1) * 4, sentinel)
+        d_n = dev(8, sentinel)
+        check(lib().btbbx_survey_hits_device(d_w.ptr, n_words, pitch_words, n_streams, d_h.ptr, None if count is None else d_cnt.ptr,
+                                             cap, tp, _ptr(entry), clk_div, clk_phase, max_length, d_recs.ptr, rec_cap, d_nrec.ptr,
+                                             None, d_scr.ptr, scratch_bytes, None), "btbbx_survey_hits_device")
+        check(lib().btbbx_survey_clock_jobs_device(d_recs.ptr, d_nrec.ptr if rec_count else None, rec_cap, d_scr.ptr, scratch_bytes, cap,
+                                                   tp, n_streams, flags, max_obs, d_jobs.ptr, job_cap, d_n.ptr, d_jrec.ptr, d_off.ptr,
+                                                   d_ch.ptr, d_oh.ptr, cap, d_n.ptr + 4, None), "btbbx_survey_clock_jobs_device")
+        out = {}
+        if reversal:
+            sb = lib().btbbx_hop_reversal_batch_scratch_bytes(job_cap, 0)
+            d_bs, d_res = dev(sb), dev(job_cap * CLOCK_RESULT_DTYPE.itemsize, sentinel)
+            check(lib().btbbx_hop_reversal_batch_device(d_jobs.ptr, d_n.ptr, job_cap, d_off.ptr, d_ch.ptr, cap, d_res.ptr, None, 0,
+                                                        d_bs.ptr, sb, None), "btbbx_hop_reversal_batch_device")
+        check(lib().btbbx_sync(None), "sync")
+        if reversal:
+            out["results"] = d_res.download(CLOCK_RESULT_DTYPE, job_cap)
+        n_recs = int(d_nrec.download(np.uint32, 2)[0])
+        n_jobs, n_obs = (int(x) for x in d_n.download(np.uint32, 2))
+        out.update(n_recs=n_recs, recs=d_recs.download(SURVEY_DTYPE, max(rec_cap, 1))[:min(n_recs, rec_cap)], n_jobs=n_jobs, n_obs=n_obs,
+                   jobs=d_jobs.download(CLOCK_JOB_DTYPE, job_cap), job_rec=d_jrec.download(np.uint32, job_cap),
+                   offsets=d_off.download(np.int32, max(cap, 1)), channels=d_ch.download(np.uint8, max(cap, 1)),
+                   obs_hits=d_oh.download(np.uint32, max(cap, 1)))
+        return out
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def acquire(words, search_bits, n_streams=1, pitch_words=None, channels=None, clkn0=0, clk_div=625, clk_phase=0, afh=False,
+            aliased=False, max_obs=1024, cand_cap=0, max_ac_errors=2, rec_cap=1 << 20, n_words=None):
+    """Capture in, (LAP, UAP, CLK1-27) of every piconet out (btbbx_acquire_host): survey() and, for every settled piconet, the
+    CLK1-27 reversal over its packets from the settling run on.  Returns (SURVEY_DTYPE records in ascending LAP order, job_rec =
+    the record index of every job, CLOCK_RESULT_DTYPE records) -- and, with cand_cap > 0, a list with the first min(count,
+    cand_cap) candidates of every job.  A result with count == 1 has CLK1-27 of its run's first packet in cand0."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if pitch_words is None:
+        pitch_words = len(words) // n_streams
+    if n_words is None:
+        n_words = pitch_words
+    assert n_words <= pitch_words and (n_streams - 1) * pitch_words + n_words <= len(words)
+    table = _channel_table(channels, n_streams)
+    k = max(rec_cap, 1)
+    recs = np.zeros(k, dtype=SURVEY_DTYPE)
+    job_rec, results = np.zeros(k, np.uint32), np.zeros(k, dtype=CLOCK_RESULT_DTYPE)
+    cand = np.zeros((k, cand_cap), np.uint32) if cand_cap else None
+    n_jobs = C.c_uint64(0)
+    flags = (JOBS_AFH if afh else 0) | (JOBS_ALIASED if aliased else 0)
+    n = check(lib().btbbx_acquire_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, max_ac_errors,
+                                       None if table is None else _ptr(table), clkn0, clk_div, clk_phase, _ptr(recs), rec_cap, None,
+                                       flags, max_obs, None, _ptr(job_rec), _ptr(results), rec_cap, C.byref(n_jobs),
+                                       None if cand is None else _ptr(cand), cand_cap), "btbbx_acquire_host")
+    nj = min(n_jobs.value, rec_cap)
+    out = (recs[:min(n, rec_cap)], job_rec[:nj], results[:nj])
+    if cand_cap:
+        out += ([cand[j, :int(results["n_stored"][j])].copy() for j in range(nj)],)
+    return out

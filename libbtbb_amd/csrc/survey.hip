@@ -14,6 +14,9 @@
 //   4. survey_walk_kernel   one wave per piconet, lane c = candidate c: the elimination of classify_candidates
 //      (piconet.cpp) as ballots, candidates in a register for the life of the group
 //
+//   5. acquire_slots_kernel / acquire_fill_kernel (survey_jobs.h)   a separate entry, btbbx_survey_clock_jobs_device: from the records
+//      and this scratch (read only) to the job table and observation arrays of the batch CLK1-27 reversal
+//
 // Nothing here synchronises or reads back: the list's length stays in device memory.
 #include "common.h"
 #include "packet_launch.h"
@@ -241,9 +244,9 @@ __global__ __launch_bounds__(SV_THREADS) void survey_mark_kernel(const uint64_t 
 }
 
 // one workgroup: tile counts -> exclusive prefix sums; the number of groups goes to params[1], *rec_count and,
-// as the end of the last group, gstart[groups] = n
+// as the end of the last group, gstart[groups] = n; params[2] = which of the two vals[] the sort ended in (survey_jobs.h)
 __global__ __launch_bounds__(SV_THREADS) void survey_tiles_kernel(uint32_t *tiles, uint32_t n_tiles, uint32_t *params, uint32_t *gstart,
-								    uint32_t *rec_count)
+								    uint32_t *rec_count, uint32_t vals_side)
 {
 	__shared__ uint32_t lds[SV_WAVES];
 	uint32_t carry = 0;
@@ -258,6 +261,7 @@ __global__ __launch_bounds__(SV_THREADS) void survey_tiles_kernel(uint32_t *tile
 	}
 	if (threadIdx.x == 0) {
 		params[1] = carry;
+		params[2] = vals_side;
 		gstart[carry] = params[0];
 		if (rec_count)
 			*rec_count = carry;
@@ -527,6 +531,8 @@ __global__ __launch_bounds__(SV_THREADS) void survey_walk_kernel(const uint32_t 
 	}
 }
 
+#include "survey_jobs.h"
+
 // ---- C ABI ------------------------------------------------------------------------------------------
 
 extern "C" size_t btbbx_survey_scratch_bytes(uint32_t cap)
@@ -641,7 +647,7 @@ extern "C" int btbbx_survey_hits_device(const uint64_t *d_words, uint64_t n_word
 	}
 
 	hipLaunchKernelGGL(survey_mark_kernel, dim3(L.grp_tiles), dim3(SV_THREADS), 0, q, keys[cur], params, tiles);
-	hipLaunchKernelGGL(survey_tiles_kernel, dim3(1), dim3(SV_THREADS), 0, q, tiles, L.grp_tiles, params, gstart, d_rec_count);
+	hipLaunchKernelGGL(survey_tiles_kernel, dim3(1), dim3(SV_THREADS), 0, q, tiles, L.grp_tiles, params, gstart, d_rec_count, (uint32_t)cur);
 	SurveyChannels table;
 	memset(&table, 0, sizeof(table));
 	if (channels)
@@ -669,6 +675,39 @@ extern "C" int btbbx_survey_hits_device(const uint64_t *d_words, uint64_t n_word
 		hipLaunchKernelGGL(survey_walk_kernel, dim3((walkers + SV_WAVES - 1) / SV_WAVES), dim3(SV_THREADS), 0, q, params, rec_cap,
 				   gstart, chan, shits, vals[cur], pin, wpos, widx, (const uint32_t *)trials, d_recs, d_candidates);
 	HIP_TRY(hipGetLastError());
+	return BTBBX_OK;
+}
+
+// The ordered LAP_ANY scan in front of a host-level survey: one hit per 1024 offsets + slack, again with room for every match
+// when more were found (as btbbx_scan_host does); the count is read back, and the survey's scratch is sized from it.
+// *block: the count (word 0; word 1 is free for the piconet count), the hit list 256 bytes behind it.
+static int survey_scan_list(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, uint64_t search_bits,
+			    int max_ac_errors, hipStream_t q, char **block_out, uint32_t *dev_cap_out, uint32_t *count_out)
+{
+	uint64_t guess = search_bits / 1024 * n_streams + 4096;
+	uint32_t dev_cap = guess > 0xfffffff0ULL ? 0xfffffff0u : (uint32_t)guess;
+	uint32_t count = 0;
+	char *block = nullptr;
+	for (int pass = 0; pass < 2; pass++) {
+		const size_t hit_bytes = sv_up((size_t)dev_cap * sizeof(btbbx_hit));
+		const size_t order_bytes = sv_up(btbbx_scan_ordered_scratch_bytes(search_bits, n_streams, BTBBX_LAP_ANY, dev_cap));
+		block = (char *)scope_hits(256 + hit_bytes + order_bytes);
+		if (!block)
+			return BTBBX_E_NOMEM;
+		HIP_TRY(hipMemsetAsync(block, 0, 2 * sizeof(uint32_t), q));
+		int rc = btbbx_scan_ordered_device(d_words, n_words, pitch_words, n_streams, search_bits, BTBBX_LAP_ANY, max_ac_errors,
+						   (btbbx_hit *)(block + 256), dev_cap, (uint32_t *)block, block + 256 + hit_bytes, order_bytes, q);
+		if (rc)
+			return rc;
+		HIP_TRY(hipMemcpyAsync(&count, block, sizeof(count), hipMemcpyDeviceToHost, q));
+		HIP_TRY(hipStreamSynchronize(q));
+		if (count <= dev_cap)
+			break;
+		dev_cap = count;
+	}
+	*block_out = block;
+	*dev_cap_out = dev_cap;
+	*count_out = count;
 	return BTBBX_OK;
 }
 
@@ -703,29 +742,11 @@ extern "C" int64_t btbbx_survey_host(const uint64_t *words, uint64_t n_words, ui
 		return BTBBX_E_NOMEM;
 	HIP_TRY(hipMemcpyAsync(d_words, words, (size_t)cap_words * 8, hipMemcpyHostToDevice, q));
 
-	// Scan first (one hit per 1024 offsets + slack; again with room for every match when more were found, as
-	// btbbx_scan_host does), read the count back, and size the survey's scratch from it.
-	uint64_t guess = search_bits / 1024 * n_streams + 4096;
-	uint32_t dev_cap = guess > 0xfffffff0ULL ? 0xfffffff0u : (uint32_t)guess;
-	uint32_t count = 0;
 	char *block = nullptr;
-	for (int pass = 0; pass < 2; pass++) {
-		const size_t hit_bytes = sv_up((size_t)dev_cap * sizeof(btbbx_hit));
-		const size_t order_bytes = sv_up(btbbx_scan_ordered_scratch_bytes(search_bits, n_streams, BTBBX_LAP_ANY, dev_cap));
-		block = (char *)scope_hits(256 + hit_bytes + order_bytes);
-		if (!block)
-			return BTBBX_E_NOMEM;
-		HIP_TRY(hipMemsetAsync(block, 0, 2 * sizeof(uint32_t), q));
-		rc = btbbx_scan_ordered_device(d_words, n_words, pitch_words, n_streams, search_bits, BTBBX_LAP_ANY, max_ac_errors,
-					       (btbbx_hit *)(block + 256), dev_cap, (uint32_t *)block, block + 256 + hit_bytes, order_bytes, q);
-		if (rc)
-			return rc;
-		HIP_TRY(hipMemcpyAsync(&count, block, sizeof(count), hipMemcpyDeviceToHost, q));
-		HIP_TRY(hipStreamSynchronize(q));
-		if (count <= dev_cap)
-			break;
-		dev_cap = count;
-	}
+	uint32_t dev_cap = 0, count = 0;
+	rc = survey_scan_list(d_words, n_words, pitch_words, n_streams, search_bits, max_ac_errors, q, &block, &dev_cap, &count);
+	if (rc)
+		return rc;
 	const uint32_t have = std::min(count, dev_cap);
 	if (!have)
 		return 0;
@@ -764,5 +785,208 @@ extern "C" int64_t btbbx_survey_host(const uint64_t *words, uint64_t n_words, ui
 		return rc;
 	HIP_TRY(e);
 	HIP_TRY(f);
+	return (int64_t)n_piconets;
+}
+
+// ---- job builder and clock acquisition ----------------------------------------------------------------
+
+extern "C" int btbbx_survey_clock_jobs_device(const btbbx_survey_rec *d_recs, const uint32_t *d_rec_count, uint32_t rec_cap,
+					      const void *d_survey_scratch, size_t survey_scratch_bytes, uint32_t cap,
+					      const uint8_t *channels, uint32_t n_streams, uint32_t flags, uint32_t max_obs,
+					      btbbx_clock_job *d_jobs, uint32_t job_cap, uint32_t *d_n_jobs, uint32_t *d_job_rec,
+					      int32_t *d_index_offsets, uint8_t *d_channels, uint32_t *d_obs_hits,
+					      uint32_t obs_cap, uint32_t *d_n_obs, void *hip_stream)
+{
+	const char *who = "btbbx_survey_clock_jobs_device";
+	const SurveyLayout L = survey_layout(cap);
+	if (!d_recs || !d_jobs || !d_n_jobs || !d_survey_scratch || !d_index_offsets || !d_channels) {
+		set_error("%s: null pointer (records, jobs, job count, scratch or an observation array)", who);
+		return BTBBX_E_ARG;
+	}
+	if (survey_scratch_bytes < L.total || obs_cap < cap) {
+		set_error("%s: the survey's scratch has %zu bytes for %u hits (%zu given), and its observations need %u entries (%u given)", who,
+			  L.total, cap, survey_scratch_bytes, cap, obs_cap);
+		return BTBBX_E_ARG;
+	}
+	if (!max_obs || max_obs > 1024 || !job_cap || (flags & ~(BTBBX_JOBS_AFH | BTBBX_JOBS_ALIASED))) {
+		set_error("%s: max_obs %u outside 1..1024, job_cap %u, or unknown bits in flags 0x%x", who, max_obs, job_cap, flags);
+		return BTBBX_E_ARG;
+	}
+	if (!n_streams || (!channels && n_streams > 79) || (channels && n_streams > SV_CHAN_STREAMS)) {
+		set_error("%s: %u streams (1..79 without a channel table, up to %u with one)", who, n_streams, SV_CHAN_STREAMS);
+		return BTBBX_E_ARG;
+	}
+	for (uint32_t s = 0; channels && s < n_streams; s++)
+		if (channels[s] > 78) {
+			set_error("%s: channels[%u] = %u is not a BR/EDR channel (0..78)", who, s, channels[s]);
+			return BTBBX_E_ARG;
+		}
+	if (((uintptr_t)d_survey_scratch & 15) || ((uintptr_t)d_recs & 3) || ((uintptr_t)d_rec_count & 3) || ((uintptr_t)d_jobs & 3) ||
+	    ((uintptr_t)d_n_jobs & 3) || ((uintptr_t)d_job_rec & 3) || ((uintptr_t)d_index_offsets & 3) || ((uintptr_t)d_obs_hits & 3) ||
+	    ((uintptr_t)d_n_obs & 3)) {
+		set_error("%s: misaligned pointer (scratch 16 bytes, everything else but the channels 4)", who);
+		return BTBBX_E_ARG;
+	}
+	int rc = ctx_require();
+	if (rc)
+		return rc;
+	hipStream_t q = (hipStream_t)hip_stream;
+	if (!cap) {                                             // (the survey of an empty list launched nothing: its scratch is not valid)
+		HIP_TRY(hipMemsetAsync(d_n_jobs, 0, sizeof(uint32_t), q));
+		if (d_n_obs)
+			HIP_TRY(hipMemsetAsync(d_n_obs, 0, sizeof(uint32_t), q));
+		return BTBBX_OK;
+	}
+	const char *s = (const char *)d_survey_scratch;
+	const uint32_t *params = (const uint32_t *)(s + L.params), *gstart = (const uint32_t *)(s + L.gstart);
+	const uint32_t *wpos = (const uint32_t *)(s + L.wpos), *widx = (const uint32_t *)(s + L.widx);
+	SurveyChannels table;
+	memset(&table, 0, sizeof(table));
+	if (channels)
+		memcpy(table.ch, channels, n_streams);
+	hipLaunchKernelGGL(acquire_slots_kernel, dim3(1), dim3(AQ_SLOT_THREADS), 0, q, (const uint32_t *)d_recs, d_rec_count, rec_cap, cap, params,
+			   gstart, wpos, max_obs, d_jobs, job_cap, d_n_jobs, d_job_rec, d_n_obs);
+	// (launched for every job there can be: one per record, one per hit)
+	const uint32_t waves = std::min(job_cap, std::min(rec_cap, cap));
+	if (waves)
+		hipLaunchKernelGGL(acquire_fill_kernel, dim3((waves + SV_WAVES - 1) / SV_WAVES), dim3(SV_THREADS), 0, q, (const uint32_t *)d_recs, cap,
+				   params, gstart, wpos, widx, (const btbbx_pkt_in *)(s + L.pin), (const btbbx_hit *)(s + L.hits),
+				   (const uint32_t *)(s + L.vals[0]), (const uint32_t *)(s + L.vals[1]), table, channels ? 0 : 1, flags, max_obs, d_jobs,
+				   job_cap, d_n_jobs, d_index_offsets, d_channels, d_obs_hits, obs_cap);
+	HIP_TRY(hipGetLastError());
+	return BTBBX_OK;
+}
+
+extern "C" int64_t btbbx_acquire_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				      uint64_t search_bits, int max_ac_errors, const uint8_t *channels,
+				      uint32_t clkn0, uint32_t clk_div, uint32_t clk_phase,
+				      btbbx_survey_rec *recs, uint64_t rec_cap, int16_t *clk6_candidates,
+				      uint32_t flags, uint32_t max_obs,
+				      btbbx_clock_job *jobs, uint32_t *job_rec, btbbx_clock_result *results, uint64_t job_cap,
+				      uint64_t *n_jobs, uint32_t *candidates, uint32_t cand_cap)
+{
+	btbbx_pkt_in entry;
+	memset(&entry, 0, sizeof(entry));
+	entry.clkn = clkn0;
+	entry.flags = 1u << 0;                                  // BTBB_WHITENED: what btbb_find_ac leaves (init_packet)
+	int rc = survey_check_args("btbbx_acquire_host", n_words, n_streams, channels, &entry, clk_div, clk_phase);
+	if (rc)
+		return rc;
+	if (n_streams == 1)
+		pitch_words = n_words;
+	if (!words || (!recs && rec_cap) || pitch_words < n_words || search_bits + 63 > n_words * 64) {
+		set_error("btbbx_acquire_host: null pointer, pitch_words < n_words or search_bits + 63 > 64 n_words");
+		return BTBBX_E_ARG;
+	}
+	if (!n_jobs || (job_cap && (!job_rec || !results)) || !max_obs || max_obs > 1024 || (flags & ~(BTBBX_JOBS_AFH | BTBBX_JOBS_ALIASED))) {
+		set_error("btbbx_acquire_host: no n_jobs, job_rec or results, max_obs %u outside 1..1024, or unknown bits in flags 0x%x", max_obs, flags);
+		return BTBBX_E_ARG;
+	}
+	rc = ctx_require();
+	if (rc)
+		return rc;
+	*n_jobs = 0;
+	if (!search_bits)
+		return 0;
+	CallScope scope;
+	hipStream_t q = scope_stream();
+	const uint64_t cap_words = (uint64_t)(n_streams - 1) * pitch_words + n_words;
+	uint64_t *d_words = (uint64_t *)scope_device((size_t)(cap_words + 2) * 8);
+	if (!d_words)
+		return BTBBX_E_NOMEM;
+	HIP_TRY(hipMemcpyAsync(d_words, words, (size_t)cap_words * 8, hipMemcpyHostToDevice, q));
+	char *block = nullptr;
+	uint32_t dev_cap = 0, count = 0;
+	rc = survey_scan_list(d_words, n_words, pitch_words, n_streams, search_bits, max_ac_errors, q, &block, &dev_cap, &count);
+	if (rc)
+		return rc;
+	const uint32_t have = std::min(count, dev_cap);
+	if (!have)
+		return 0;
+	// One block for the survey's scratch, its records, and the builder's outputs; a second one, once the number of jobs is
+	// known, for the batch reversal (about 8 KiB of scratch per job).
+	const uint32_t dev_recs = (uint32_t)std::min<uint64_t>(rec_cap, have);
+	const uint32_t dev_jobs = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(job_cap, dev_recs));
+	size_t at = 0;
+	auto take = [&](size_t bytes) { const size_t here = at; at += sv_up(bytes); return here; };
+	const size_t survey_bytes = btbbx_survey_scratch_bytes(have);
+	const size_t o_scr = take(survey_bytes), o_recs = take((size_t)dev_recs * sizeof(btbbx_survey_rec));
+	const size_t o_c6 = take(clk6_candidates ? (size_t)dev_recs * 64 * sizeof(int16_t) : 0), o_cnt = take(2 * sizeof(uint32_t));
+	const size_t o_jobs = take((size_t)dev_jobs * sizeof(btbbx_clock_job)), o_jrec = take((size_t)dev_jobs * sizeof(uint32_t));
+	const size_t o_off = take((size_t)have * sizeof(int32_t)), o_ch = take(have);
+	char *work = nullptr, *batch = nullptr;
+	if (hipMalloc((void **)&work, at) != hipSuccess) {
+		(void)hipGetLastError();
+		set_error("btbbx_acquire_host: %zu bytes of device memory for %u hits not available", at, have);
+		return BTBBX_E_NOMEM;
+	}
+	btbbx_survey_rec *d_recs = (btbbx_survey_rec *)(work + o_recs);
+	int16_t *d_c6 = clk6_candidates ? (int16_t *)(work + o_c6) : nullptr;
+	uint32_t *d_rec_count = (uint32_t *)block + 1, *d_n_jobs = (uint32_t *)(work + o_cnt);
+	btbbx_clock_job *d_jobs = (btbbx_clock_job *)(work + o_jobs);
+	uint32_t counts[2] = {0, 0}, n_piconets = 0;             // jobs, observations
+	uint64_t stored = 0;
+	hipError_t e = hipSuccess;
+	rc = btbbx_survey_hits_device(d_words, n_words, pitch_words, n_streams, (const btbbx_hit *)(block + 256), (const uint32_t *)block, have,
+				      channels, &entry, clk_div, clk_phase, BTBBX_MAX_SYMBOLS, d_recs, dev_recs, d_rec_count, d_c6, work + o_scr,
+				      survey_bytes, q);
+	if (!rc && dev_recs) {
+		rc = btbbx_survey_clock_jobs_device(d_recs, d_rec_count, dev_recs, work + o_scr, survey_bytes, have, channels, n_streams, flags,
+						    max_obs, d_jobs, dev_jobs, d_n_jobs, (uint32_t *)(work + o_jrec), (int32_t *)(work + o_off),
+						    (uint8_t *)(work + o_ch), nullptr, have, d_n_jobs + 1, q);
+	}
+	// The one place the chain comes to the host: the batch reversal's scratch follows the number of jobs, which is read back
+	// together with the number of piconets (btbbx_survey_host reads that one at the same point).
+	if (!rc && dev_recs)
+		e = hipMemcpyAsync(counts, d_n_jobs, sizeof(counts), hipMemcpyDeviceToHost, q);
+	if (!rc && e == hipSuccess)
+		e = hipMemcpyAsync(&n_piconets, d_rec_count, sizeof(n_piconets), hipMemcpyDeviceToHost, q);
+	if (!rc && e == hipSuccess)
+		e = hipStreamSynchronize(q);
+	stored = job_cap ? std::min<uint64_t>(counts[0], dev_jobs) : 0;
+	if (!rc && e == hipSuccess && stored) {
+		const uint32_t nj = (uint32_t)stored;
+		const size_t want_cand = candidates ? (size_t)nj * cand_cap * sizeof(uint32_t) : 0;
+		const size_t batch_bytes = btbbx_hop_reversal_batch_scratch_bytes(nj, cand_cap);
+		size_t bat = 0;
+		auto more = [&](size_t bytes) { const size_t here = bat; bat += sv_up(bytes); return here; };
+		const size_t o_bs = more(batch_bytes), o_res = more((size_t)nj * sizeof(btbbx_clock_result)), o_cand = more(want_cand);
+		if (hipMalloc((void **)&batch, bat) != hipSuccess) {
+			(void)hipGetLastError();
+			set_error("btbbx_acquire_host: %zu bytes of device memory for %u jobs not available", bat, nj);
+			rc = BTBBX_E_NOMEM;
+		}
+		// the caller's candidate slots go in first, so that the slots no job writes come back as they were
+		if (!rc && want_cand)
+			e = hipMemcpyAsync(batch + o_cand, candidates, want_cand, hipMemcpyHostToDevice, q);
+		if (!rc && e == hipSuccess)
+			rc = btbbx_hop_reversal_batch_device(d_jobs, d_n_jobs, nj, (const int32_t *)(work + o_off), (const uint8_t *)(work + o_ch), have,
+							     (btbbx_clock_result *)(batch + o_res), want_cand ? (uint32_t *)(batch + o_cand) : nullptr,
+							     cand_cap, batch + o_bs, batch_bytes, q);
+		if (!rc && e == hipSuccess)
+			e = hipMemcpyAsync(results, batch + o_res, (size_t)nj * sizeof(btbbx_clock_result), hipMemcpyDeviceToHost, q);
+		if (!rc && e == hipSuccess && want_cand)
+			e = hipMemcpyAsync(candidates, batch + o_cand, want_cand, hipMemcpyDeviceToHost, q);
+		if (!rc && e == hipSuccess && jobs)
+			e = hipMemcpyAsync(jobs, d_jobs, (size_t)nj * sizeof(btbbx_clock_job), hipMemcpyDeviceToHost, q);
+		if (!rc && e == hipSuccess)
+			e = hipMemcpyAsync(job_rec, work + o_jrec, (size_t)nj * sizeof(uint32_t), hipMemcpyDeviceToHost, q);
+	}
+	if (!rc && e == hipSuccess) {
+		const uint64_t n = std::min<uint64_t>(n_piconets, dev_recs);
+		if (n)
+			e = hipMemcpyAsync(recs, d_recs, (size_t)n * sizeof(btbbx_survey_rec), hipMemcpyDeviceToHost, q);
+		if (e == hipSuccess && n && clk6_candidates)
+			e = hipMemcpyAsync(clk6_candidates, d_c6, (size_t)n * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, q);
+	}
+	const hipError_t f = hipStreamSynchronize(q);
+	(void)hipFree(work);
+	if (batch)
+		(void)hipFree(batch);
+	if (rc)
+		return rc;
+	HIP_TRY(e);
+	HIP_TRY(f);
+	*n_jobs = counts[0];
 	return (int64_t)n_piconets;
 }
