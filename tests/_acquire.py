@@ -19,17 +19,63 @@ from libbtbb_amd import synth
 JOBS_AFH, JOBS_ALIASED = 1, 2
 
 
-def model(engine, cap, hits, recs, clkn0, clk_phase=0, max_length=bt.MAX_SYMBOLS, flags=0, max_obs=1024, job_cap=None):
+class Walked:
+    """The header-bearing packets of every LAP of `hits` (the header_present pass of the oracle port), group by group and only
+    when asked for: group(g) -> (W = hit indices in ascending (offset, stream), {hit index: (stored clock, channel)}).  One
+    Walked serves every rec_cap / job_cap / max_obs / flags variation of model() over the same list."""
+
+    def __init__(self, engine, cap, hits, clkn0, clk_phase=0, max_length=bt.MAX_SYMBOLS):
+        self.engine, self.cap, self.hits = engine, cap, np.asarray(hits)
+        self.clkn0, self.clk_phase, self.max_length = clkn0, clk_phase, max_length
+        hits = self.hits
+        self.order = np.lexsort((hits["stream"], hits["offset"], hits["lap"]))
+        laps = hits["lap"][self.order]
+        self.starts = (np.concatenate([[0], np.nonzero(np.diff(laps.astype(np.int64)))[0] + 1, [len(self.order)]])
+                       if len(self.order) else np.zeros(1, int))
+        self._groups = {}
+
+    def members(self, g):
+        return self.order[self.starts[g]:self.starts[g + 1]]
+
+    def group(self, g):
+        if g not in self._groups:
+            engine, cap, hits = self.engine, self.cap, self.hits
+            walked, clocks = [], {}
+            for k in self.members(g):
+                h = hits[k]
+                st = int(h["stream"])
+                ch = st if cap.channels is None else int(cap.channels[st])
+                clkn = (self.clkn0 + (int(h["offset"]) + self.clk_phase) // cap.clk_div) & 0xFFFFFFFF
+                p = engine.packet(int(h["lap"]), int(h["ac_errors"]), sv.packet_symbols(cap, h, self.max_length), ch, clkn)
+                if engine.header_present(p):
+                    walked.append(int(k))
+                    clocks[int(k)] = (clkn, ch)
+                engine.free_packet(p)
+            self._groups[g] = (walked, clocks)
+        return self._groups[g]
+
+    def present(self):
+        """header_present of every hit, in sorted order (what survey_wmark / wlist compact)"""
+        out = np.zeros(len(self.order), dtype=bool)
+        where = {int(k): i for i, k in enumerate(self.order)}
+        for g in range(len(self.starts) - 1):
+            for k in self.group(g)[0]:
+                out[where[k]] = True
+        return out
+
+
+def model(engine, cap, hits, recs, clkn0, clk_phase=0, max_length=bt.MAX_SYMBOLS, flags=0, max_obs=1024, job_cap=None, walked=None):
     """What the builder leaves for `recs` (the first len(recs) LAPs of `hits` in ascending order): dict(n_jobs = all settled
-    records, jobs / job_rec = the first job_cap of them, offsets / channels / obs_hits = their observations, n_obs)."""
+    records, jobs / job_rec = the first job_cap of them, offsets / channels / obs_hits = their observations, n_obs).
+    walked: a Walked over the same list and arguments, to share the header pass between calls (None: one of this call's own)."""
     hits = np.asarray(hits)
-    order = np.lexsort((hits["stream"], hits["offset"], hits["lap"]))
-    laps = hits["lap"][order]
-    starts = np.concatenate([[0], np.nonzero(np.diff(laps.astype(np.int64)))[0] + 1, [len(order)]]) if len(order) else np.zeros(1, int)
+    lists = Walked(engine, cap, hits, clkn0, clk_phase, max_length) if walked is None else walked
+    assert lists.hits is hits or (len(lists.hits) == len(hits) and lists.hits.tobytes() == hits.tobytes())
+    assert (lists.clkn0, lists.clk_phase, lists.max_length) == (clkn0, clk_phase, max_length)
     cfgs, clk6, obs, job_rec, oh = [], [], [], [], []
     n_jobs = 0
     for g, r in enumerate(recs):
-        group = order[starts[g]:starts[g + 1]]
+        group = lists.members(g)
         lap = int(r["lap"])
         assert int(hits["lap"][group[0]]) == lap and len(group) == r["n_packets"]
         if not r["settled_by"]:
@@ -37,21 +83,11 @@ def model(engine, cap, hits, recs, clkn0, clk_phase=0, max_length=bt.MAX_SYMBOLS
         n_jobs += 1
         if job_cap is not None and n_jobs > job_cap:
             continue
-        walked, clocks = [], {}
-        for k in group:
-            h = hits[k]
-            st = int(h["stream"])
-            ch = st if cap.channels is None else int(cap.channels[st])
-            clkn = (clkn0 + (int(h["offset"]) + clk_phase) // cap.clk_div) & 0xFFFFFFFF
-            p = engine.packet(lap, int(h["ac_errors"]), sv.packet_symbols(cap, h, max_length), ch, clkn)
-            if engine.header_present(p):
-                walked.append(int(k))
-                clocks[int(k)] = (clkn, ch)
-            engine.free_packet(p)
+        walked_g, clocks = lists.group(g)
         first = int(r["n_walked"]) - int(r["packets_observed"])
-        assert 0 <= first < int(r["n_walked"]) <= len(walked)
-        assert walked[int(r["n_walked"]) - 1] == r["settled_hit"]
-        run = walked[first:][:max_obs]
+        assert 0 <= first < int(r["n_walked"]) <= len(walked_g)
+        assert walked_g[int(r["n_walked"]) - 1] == r["settled_hit"]
+        run = walked_g[first:][:max_obs]
         t0 = clocks[run[0]][0]
         assert t0 == r["first_pkt_time"]
         off = np.array([(clocks[k][0] - t0) & 0xFFFFFFFF for k in run], dtype=np.uint32).view(np.int32)

@@ -1,7 +1,8 @@
 """GPU parity of the batch CLK1-27 reversal (btbbx_hop_reversal_batch_*, hop_batch.h) with the single-piconet path
 (btbbx_hop_reversal_open / _winnow / _candidates, pinned to the oracle and to the reference's traces by test_gpu_hop.py),
 with the traces recorded from the reference (tests/golden/hop.json), and its handling of rejected jobs, of a job count
-that lives in device memory and of a job whose candidates would not fit any scratch."""
+that lives in device memory and of a job whose candidates would not fit any scratch; and every tiling of pass 1 (tiles_log2 9
+down to 4) with true clocks on the edges of its tiles."""
 import ctypes as C
 import json
 import os
@@ -256,3 +257,109 @@ def test_flat_scratch_with_every_clock_a_candidate():
     assert cand[1].tolist() == [(heavy[1] & 63) + 64 * i for i in range(cand_cap)]
     for j in (0, 2):
         assert res[j]["count"] == 1 and res[j]["cand0"] == sc[j][1], j
+
+
+# ---- the tiling ladder ----------------------------------------------------------------------------------------------
+
+LADDER_CAPS = (32, 33, 64, 65, 128, 129, 256, 257, 512, 513)
+N_GROUPS = 1 << 21                                              # HOP_GROUPS: the clocks congruent to clk6
+
+
+def _tiles_log2(job_cap):
+    """the rule of btbbx_hop_reversal_batch_device (hop.hip), copied"""
+    t = 9
+    while t > 4 and (job_cap << t) > 16384:
+        t -= 1
+    return t
+
+
+def _edge_scenario(rng, used, alias, n_obs, group):
+    """As _scenario, with the true clock in group `group` of the 2^21 (c0 >> 6) and the hops from btbbx_hop_channels_device,
+    which takes any clock: the observations may pass 2^27."""
+    lap, uap = int(rng.integers(0, 1 << 24)), int(rng.integers(0, 256))
+    cfg = bt.hop_cfg(lap, uap, _hop.afh_map_bytes(rng, used) if used else None)
+    c0 = 64 * group + int(rng.integers(0, 64))
+    off = np.concatenate([[0], np.cumsum(rng.integers(1, 400 if n_obs > 30 else 2000, n_obs - 1))]).astype(np.int64)
+    ch = bt.hop_channels(cfg, (c0 + off) % _hop.SEQ_LEN).tolist()
+    return cfg, c0, off.tolist(), [_hop.aliased(c) for c in ch] if alias else ch
+
+
+def _ladder_call(jobs, n_jobs_word, job_cap, offsets, channels, cand_cap):
+    """btbbx_hop_reversal_batch_device over fill; n_jobs_word None: a NULL d_n_jobs (job_cap jobs)."""
+    lib = bt.lib()
+    scratch_bytes = lib.btbbx_hop_reversal_batch_scratch_bytes(job_cap, cand_cap)
+    bufs = []
+
+    def dev(a):
+        bufs.append(bt.DeviceBuffer(max(a.nbytes, 16)).upload(a))
+        return bufs[-1]
+    try:
+        d_jobs, d_n = dev(jobs), dev(np.array([n_jobs_word or 0, 0], np.uint32))
+        d_off, d_ch = dev(offsets), dev(channels)
+        d_res = dev(np.full(job_cap * 6, FILL, np.uint32))
+        d_cand = dev(np.full(job_cap * cand_cap, FILL, np.uint32))
+        d_scr = dev(np.full(scratch_bytes // 4, FILL, np.uint32))
+        bt.check(lib.btbbx_hop_reversal_batch_device(d_jobs.ptr, None if n_jobs_word is None else d_n.ptr, job_cap, d_off.ptr, d_ch.ptr,
+                                                     len(offsets), d_res.ptr, d_cand.ptr, cand_cap, d_scr.ptr, scratch_bytes, None),
+                 "btbbx_hop_reversal_batch_device")
+        bt.check(lib.btbbx_sync(None), "sync")
+        return (d_res.download(np.uint32, job_cap * 6).view(bt.CLOCK_RESULT_DTYPE),
+                d_cand.download(np.uint32, job_cap * cand_cap).reshape(job_cap, cand_cap))
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def test_tiling_ladder():
+    """Every tiling of pass 1 (tiles_log2 9 down to 4: job_cap on both sides of every step) over the same scenarios, with true
+    clocks on the edges of the tiles: group 0, the last group, and per - 1 / per for the tile length per of every tiling
+    (2^17 - 1 and 2^17 end and open a tile of EVERY tiling).  Eight scenarios cover basic / AFH, aliased or not and 1, 2, 30 and
+    1024 observations; ten more put a clock on per - 1 and per of the five finer tilings."""
+    rng = np.random.default_rng(_libs.seed(6405))
+    cand_cap = 16
+    sc = [_edge_scenario(rng, None, 0, 30, 0) + (0, True),
+          _edge_scenario(rng, None, 1, 1024, (1 << 17) - 1) + (1, True),
+          _edge_scenario(rng, 40, 0, 30, 1 << 17) + (0, True),
+          _edge_scenario(rng, 66, 1, 30, N_GROUPS - 1) + (1, True),
+          _scenario(rng, None, 0, 1) + (0, False),
+          _scenario(rng, 30, 1, 2) + (1, False),
+          _scenario(rng, 5, 0, 1024) + (0, False),
+          _scenario(rng, 79, 0, 2) + (0, False)]
+    edges = {0, (1 << 17) - 1, 1 << 17, N_GROUPS - 1}
+    for t in range(5, 10):
+        per = N_GROUPS >> t
+        for k, group in enumerate((per - 1, per)):
+            sc.append(_edge_scenario(rng, (None, 50)[(t + k) & 1], 0, 30, group) + (0, True))
+            edges.add(group)
+    for t in range(4, 10):                                          # the edge clocks asked for, at every tiling
+        per = N_GROUPS >> t
+        assert {0, per - 1, per, N_GROUPS - 1} <= edges and {s[1] >> 6 for s in sc} >= edges
+    wrap = sc[3]
+    assert wrap[1] + wrap[2][-1] >= _hop.SEQ_LEN > wrap[1]          # candidate + offset passes 2^27
+    assert sorted(len(s[2]) for s in sc[:8]) == [1, 2, 2, 30, 30, 30, 1024, 1024]
+    jobs1, offsets, channels = bt.clock_jobs([s[0] for s in sc], [s[1] & 63 for s in sc], [(s[2], s[3]) for s in sc], [s[4] for s in sc])
+    # the single-piconet path, once per scenario
+    want_res = np.zeros(len(sc), bt.CLOCK_RESULT_DTYPE)
+    want_cand = np.full((len(sc), cand_cap), FILL, np.uint32)
+    for i, s in enumerate(sc):
+        n_initial, stop, count, cand0, cand = _single(s[0], s[1] & 63, s[2], s[3], s[4], cand_cap)
+        want_res[i] = (0, n_initial, stop, count, cand0 if count else 0, min(count, cand_cap))
+        want_cand[i, :len(cand)] = cand
+        assert len(cand) == min(count, cand_cap)
+        if s[5]:                                                    # >= 30 observations on >= 21 channels
+            assert (count, cand0) == (1, s[1]), (i, count, cand0, s[1])
+    assert (want_res["count"] > cand_cap).sum() >= 3 and (want_res["count"] == 1).sum() >= 14
+    seen = set()
+    for n_call, job_cap in enumerate(LADDER_CAPS):
+        seen.add(_tiles_log2(job_cap))
+        which = np.arange(job_cap) % len(sc)
+        jobs = jobs1[which]
+        n = job_cap - 3 if n_call & 1 else None                     # every other call: the count is a device word below job_cap
+        res, cand = _ladder_call(jobs, n, job_cap, offsets, channels, cand_cap)
+        n = job_cap if n is None else n
+        bad = [j for j in range(n) if res[j].tobytes() != want_res[which[j]].tobytes()]
+        assert not bad, (job_cap, bad[:4], res[bad[0]], want_res[which[bad[0]]])
+        bad = np.nonzero((cand[:n] != want_cand[which[:n]]).any(axis=1))[0]
+        assert len(bad) == 0, (job_cap, bad[:4].tolist(), cand[bad[0]], want_cand[which[bad[0]]])
+        assert (res[n:].view(np.uint32) == FILL).all() and (cand[n:] == FILL).all(), job_cap
+    assert seen == {4, 5, 6, 7, 8, 9}
