@@ -601,6 +601,85 @@ int64_t btbbx_acquire_host(const uint64_t *words, uint64_t n_words, uint64_t pit
 			   btbbx_clock_job *jobs, uint32_t *job_rec, btbbx_clock_result *results, uint64_t job_cap,
 			   uint64_t *n_jobs, uint32_t *candidates, uint32_t cand_cap);
 
+/* ---- following: every packet of every acquired piconet with its own UAP and clock ------------------- */
+/* The last stage of btbb_process_packet (bluetooth_piconet.c:851-899: LAP -> UAP/CLK1-6 -> CLK1-27 -> FOLLOWING), for a whole
+ * hit list behind the acquisition chain: every packet of a piconet gets the piconet's UAP and the piconet-aligned clock
+ * (:872-881), is decoded with them, and is checked against the channel the piconet's hop selection gives for that clock --
+ * which tells a real packet from a stray access code and shows lost sync. */
+typedef struct btbbx_follow_pkt {   /* 16 bytes, one per hit */
+	uint32_t piconet;     /* index into d_recs of the hit's LAP, UINT32_MAX when no stored record has it */
+	uint32_t clkn;        /* the clock the packet was decoded with (see the stages below) */
+	uint8_t  stage;       /* 0 LAP only, 1 UAP + CLK1-6, 2 UAP + CLK1-27 */
+	uint8_t  channel;     /* channels[hit.stream] (the stream index without a table) */
+	uint8_t  hop_channel; /* stage 2: the channel the job's hop selection gives for clkn, in aliased form when job.aliased; else 0xff */
+	uint8_t  on_hop;      /* stage 2 and hop_channel == channel */
+	uint32_t job;         /* index into d_jobs / d_results, UINT32_MAX when the record has no stored job */
+} btbbx_follow_pkt;
+
+typedef struct btbbx_follow_sum {   /* 32 bytes, one per survey record */
+	uint32_t stage, job;              /* as in the packets of this record */
+	uint32_t n_hits;                  /* hits of the list with this LAP */
+	uint32_t n_header;                /* ... whose header_rv != 0 */
+	uint32_t n_payload;               /* ... whose payload_rv > 0 */
+	uint32_t n_on_hop, n_off_hop;     /* stage 2 only: on_hop / not on_hop */
+	uint32_t lt_addr_mask;            /* bit a: some hit with header_rv != 0 had LT_ADDR a */
+} btbbx_follow_sum;
+
+/* Follows the first N = min(*d_count, cap) hits of d_hits through the R = min(*d_rec_count, rec_cap) records of a survey and
+ * the J = min(*d_n_jobs, job_cap) jobs and results of btbbx_survey_clock_jobs_device + btbbx_hop_reversal_batch_device; a NULL
+ * count pointer means its cap.  All pointers are DEVICE pointers except channels and entry (HOST pointers, as in the survey).
+ * For hit i < N:
+ *   c = entry->clkn + (offset + clk_phase) / clk_div in uint32_t arithmetic, the stored clock of btbbx_survey_hits_device;
+ *   g = the record with lap == hit.lap among d_recs[0 .. R) (the records are in ASCENDING LAP order: they are searched);
+ *       none: piconet = UINT32_MAX and the hit is stage 0;
+ *   j = the job with d_job_rec[j] == g, j < J (jobs are in record order: d_job_rec ascends); none: job = UINT32_MAX.
+ *   stage 2 iff j exists and d_results[j].status == 0 && d_results[j].count == 1:
+ *       clkn = (cand0 + c - recs[g].first_pkt_time) & 0x7ffffff -- the receiver's clock plus the reference's CLKN offset
+ *       (cand0 << 1) - (first_pkt_time << 1) (:598), halved; a hit before the run's first packet gets a smaller clock through
+ *       the wrap (2^32 is a multiple of 2^27); uap = recs[g].uap; flags = entry->flags | UAP_VALID | CLK6_VALID | CLK27_VALID;
+ *   stage 1 iff not stage 2 and recs[g].settled_by != 0:
+ *       clkn = (recs[g].clk_offset + c) & 0x3f (:489); uap = recs[g].uap; flags = entry->flags | UAP_VALID | CLK6_VALID;
+ *   stage 0 otherwise: clkn = c, uap and flags those of *entry -- the hit comes out exactly as
+ *       btbbx_decode_hits_piconet_phase_device leaves it.
+ *   d_in[i] = {length 0, clkn, flags, uap, entry->type, entry->llid, entry->flow}; d_out[i] and d_lengths[i] (d_lengths may be
+ *   NULL) are what btbbx_decode_hits_counted_device writes for d_in[i] with the same max_length: the decoder is that call's.
+ *   channel = channels[hit.stream], the stream index when channels is NULL (0xff for a stream >= n_streams: the list must come
+ *   from a scan of the same geometry).  hop_channel, stage 2 only, comes from the job's own cfg -- the bank modulo used_channels
+ *   when cfg.afh -- by the device code the reversal's agreement walk uses, so follow and reversal cannot disagree; when
+ *   job.aliased it is ((ch + 24) % 25) + 26.  (0xff, never on hop, for a cfg the batch reversal rejects.)
+ * Every d_sums[g], g < R, is written whole: a record none of whose hits are in the list gets its stage, its job and zeros.
+ * Records and sums behind R are not written; d_in, d_follow, d_out and d_lengths behind N are not written.
+ * job_cap == 0 means no jobs (stages 0 and 1 only); d_jobs, d_job_rec and d_results may be NULL then.
+ * Asynchronous on hip_stream: nothing is synchronised, nothing is read back and no scratch is needed -- d_in is the only
+ * intermediate and belongs to the caller.  Three launches besides the decoder's.
+ * BTBBX_E_ARG before any launch for: d_words, d_hits, d_recs, d_in, d_follow, d_out, d_sums or entry NULL; d_jobs, d_job_rec or
+ * d_results NULL while job_cap != 0; clk_div == 0 or clk_phase >= clk_div; cap == 0 or rec_cap == 0; a channel above 78, no or
+ * more than 79 streams without a table, more than 256 with one; a pointer that is not 4-byte aligned (8 bytes where the
+ * records hold 64-bit fields: d_words, d_hits, d_out). */
+int btbbx_follow_hits_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			     const btbbx_hit *d_hits, const uint32_t *d_count, uint32_t cap,
+			     const btbbx_survey_rec *d_recs, const uint32_t *d_rec_count, uint32_t rec_cap,
+			     const btbbx_clock_job *d_jobs, const uint32_t *d_job_rec, const btbbx_clock_result *d_results,
+			     const uint32_t *d_n_jobs, uint32_t job_cap,
+			     const uint8_t *channels, const btbbx_pkt_in *entry, uint32_t clk_div, uint32_t clk_phase, uint32_t max_length,
+			     btbbx_pkt_in *d_in, btbbx_follow_pkt *d_follow, btbbx_pkt_out *d_out, uint32_t *d_lengths,
+			     btbbx_follow_sum *d_sums, void *hip_stream);
+/* Host wrapper: btbbx_acquire_host with the follow stage appended on the same stream, over the same ordered hit list, the same
+ * entry state (whitened, nothing else known) and max_length = BTBBX_MAX_SYMBOLS.  The return value and recs / job_rec /
+ * results / n_jobs are as in btbbx_acquire_host (every stored record's job is worked, min(*n_jobs, job_cap) of them are
+ * copied out).  *n_hits counts all hits; the first hit_cap of them in (stream, offset) order are copied to hits / follow /
+ * pkts, while the survey and sums (one per stored record) always cover all hits.  pkts, job_rec and results may be NULL: then
+ * they are not copied.  rec_cap == 0, or recs, hits (with hit_cap != 0), follow (with hit_cap != 0), sums, n_jobs or n_hits
+ * NULL: BTBBX_E_ARG.  The only host wait between copy-in and copy-out is the one btbbx_acquire_host already has, where it
+ * reads the counts to size scratch.  Safe to call from several host threads at once. */
+int64_t btbbx_follow_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			  uint64_t search_bits, int max_ac_errors, const uint8_t *channels,
+			  uint32_t clkn0, uint32_t clk_div, uint32_t clk_phase,
+			  btbbx_survey_rec *recs, uint64_t rec_cap, uint32_t flags, uint32_t max_obs,
+			  uint32_t *job_rec, btbbx_clock_result *results, uint64_t job_cap, uint64_t *n_jobs,
+			  btbbx_hit *hits, btbbx_follow_pkt *follow, btbbx_pkt_out *pkts, uint64_t hit_cap, uint64_t *n_hits,
+			  btbbx_follow_sum *sums);
+
 /* piconet introspection for tests and tools: what the reference keeps in struct btbb_piconet
  * (bluetooth_piconet.h:59-85).  field: 0 num_candidates, 1 winnowed, 2 packets_observed,
  * 3 total_packets_observed, 4 first_pkt_time, 5 flags, 6 used_channels */

@@ -97,6 +97,13 @@ SURVEY_DTYPE = np.dtype([("lap", "<u4"), ("flags", "<u4"), ("uap", "u1"), ("clk_
                          ("first_offset", "<u8")])
 assert SURVEY_DTYPE.itemsize == 64 and SURVEY_DTYPE.fields["first_offset"][1] == 56
 
+# the follow stage (include/btbbx.h btbbx_follow_pkt / btbbx_follow_sum; follow.h checks the C layout with static_asserts)
+FOLLOW_PKT_DTYPE = np.dtype([("piconet", "<u4"), ("clkn", "<u4"), ("stage", "u1"), ("channel", "u1"), ("hop_channel", "u1"),
+                             ("on_hop", "u1"), ("job", "<u4")])
+FOLLOW_SUM_DTYPE = np.dtype([("stage", "<u4"), ("job", "<u4"), ("n_hits", "<u4"), ("n_header", "<u4"), ("n_payload", "<u4"),
+                             ("n_on_hop", "<u4"), ("n_off_hop", "<u4"), ("lt_addr_mask", "<u4")])
+assert FOLLOW_PKT_DTYPE.itemsize == 16 and FOLLOW_SUM_DTYPE.itemsize == 32
+
 _vp, _u64, _u32 = C.c_void_p, C.c_uint64, C.c_uint32
 
 # every symbol include/btbbx.h and include/btbb.h declare: (restype, argtypes)
@@ -173,6 +180,10 @@ SIGNATURES = {
                                                  _vp, _vp, _vp, _u32, _vp, _vp]),
     "btbbx_acquire_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, C.c_int, _vp, _u32, _u32, _u32, _vp, _u64, _vp, _u32, _u32,
                                        _vp, _vp, _vp, _u64, _vp, _vp, _u32]),
+    "btbbx_follow_hits_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32,
+                                           _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "btbbx_follow_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, C.c_int, _vp, _u32, _u32, _u32, _vp, _u64, _u32, _u32,
+                                      _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp]),
     # ---- btbb.h
     "btbb_init": (C.c_int, [C.c_int]),
     "btbb_get_release": (C.c_char_p, []),
@@ -816,3 +827,134 @@ def acquire(words, search_bits, n_streams=1, pitch_words=None, channels=None, cl
     if cand_cap:
         out += ([cand[j, :int(results["n_stored"][j])].copy() for j in range(nj)],)
     return out
+
+
+# ---- following: every packet of every acquired piconet with its own UAP and clock ---------------
+NO_PICONET = 0xFFFFFFFF
+
+
+def run_follow_hits(stream_words, hits, entry, channels=None, clk_div=625, clk_phase=0, max_length=MAX_SYMBOLS, count=None, flags=0,
+                    max_obs=1024, sentinel=0, pitch_words=None, n_words=None, recs=None, rec_count="device", rec_cap=None, jobs=None,
+                    job_rec=None, results=None, n_jobs="device", job_cap=None, follow_channels="same", follow_hits=None,
+                    follow_count="same", lengths=True, zero_out=0):
+    """btbbx_follow_hits_device chained behind the calls of run_survey_clock_jobs(..., reversal=True) on device buffers ->
+    dict(n_recs, recs, n_jobs, jobs, job_rec, results = the tables the follow read; pkt_in, follow, pkt_out, lengths, sums = its
+    outputs), every output array WHOLE (one entry per hit, rec_cap sums) over a fill of `sentinel` bytes.  The first zero_out
+    records of d_out are zeroed instead: the decoders read what a record holds on entry as the packet's earlier state.
+    The follow's inputs can be replaced (tests hand it doctored tables): recs / jobs / job_rec / results = arrays uploaded in
+    place of what the chain left; rec_count / n_jobs = "device" (the chain's count), None (a NULL pointer) or a number put into
+    HBM; rec_cap / job_cap = the caps given to the follow (job_cap = 0 passes NULL job pointers); follow_channels = the channel
+    table of the follow alone; follow_hits / follow_count = another list (same capture) and its count for the follow alone
+    (follow_count: "same" = `count`, None = NULL, or a number)."""
+    stream_words = np.ascontiguousarray(stream_words, dtype=np.uint64)
+    n_streams, pitch = stream_words.shape
+    pitch_words = pitch if pitch_words is None else pitch_words
+    n_words = pitch_words if n_words is None else n_words
+    cap = len(hits)
+    table = _channel_table(channels, n_streams)
+    tp = None if table is None else _ptr(table)
+    ftable = table if isinstance(follow_channels, str) else _channel_table(follow_channels, n_streams)
+    ftp = None if ftable is None else _ptr(ftable)
+    entry = np.ascontiguousarray(np.asarray(entry, dtype=PKTIN_DTYPE).reshape(1))
+    scratch_bytes = lib().btbbx_survey_scratch_bytes(cap)
+    chain_recs, chain_jobs = max(cap, 1), max(cap, 1)
+    bufs = []
+
+    def dev(nbytes, fill=None):
+        bufs.append(DeviceBuffer(nbytes))
+        if fill is not None:
+            check(lib().btbbx_memset(bufs[-1].ptr, fill, max(nbytes, 8)), "memset")
+        return bufs[-1]
+
+    def table_of(given, d_chain, dtype):
+        if given is None:
+            return d_chain
+        given = np.ascontiguousarray(given, dtype=dtype)
+        return dev(max(given.nbytes, 8), 0).upload(given)
+
+    def count_of(given, d_chain):
+        if given is None:
+            return None
+        if isinstance(given, str):
+            return d_chain.ptr
+        return dev(8).upload(np.array([given, 0], dtype=np.uint32)).ptr
+    try:
+        d_w = dev(stream_words.nbytes + 16).upload(stream_words)
+        d_h = dev(max(hits.nbytes, 16)).upload(np.ascontiguousarray(hits))
+        d_cnt = dev(8).upload(np.array([0 if count is None else count, 0], dtype=np.uint32))
+        d_recs, d_nrec, d_scr = dev(chain_recs * SURVEY_DTYPE.itemsize, 0), dev(8, 0), dev(scratch_bytes)
+        d_jobs, d_jrec = dev(chain_jobs * CLOCK_JOB_DTYPE.itemsize, 0), dev(chain_jobs * 4, 0)
+        d_off, d_ch, d_n = dev(max(cap, 1) * 4, 0), dev(max(cap, 1), 0), dev(8, 0)
+        sb = lib().btbbx_hop_reversal_batch_scratch_bytes(chain_jobs, 0)
+        d_bs, d_res = dev(sb), dev(chain_jobs * CLOCK_RESULT_DTYPE.itemsize, 0)
+        check(lib().btbbx_survey_hits_device(d_w.ptr, n_words, pitch_words, n_streams, d_h.ptr, None if count is None else d_cnt.ptr,
+                                             cap, tp, _ptr(entry), clk_div, clk_phase, max_length, d_recs.ptr, chain_recs, d_nrec.ptr,
+                                             None, d_scr.ptr, scratch_bytes, None), "btbbx_survey_hits_device")
+        check(lib().btbbx_survey_clock_jobs_device(d_recs.ptr, d_nrec.ptr, chain_recs, d_scr.ptr, scratch_bytes, cap, tp, n_streams, flags,
+                                                   max_obs, d_jobs.ptr, chain_jobs, d_n.ptr, d_jrec.ptr, d_off.ptr, d_ch.ptr, None, cap,
+                                                   d_n.ptr + 4, None), "btbbx_survey_clock_jobs_device")
+        check(lib().btbbx_hop_reversal_batch_device(d_jobs.ptr, d_n.ptr, chain_jobs, d_off.ptr, d_ch.ptr, cap, d_res.ptr, None, 0, d_bs.ptr,
+                                                    sb, None), "btbbx_hop_reversal_batch_device")
+        # the follow's own view of the tables
+        f_recs, f_jobs = table_of(recs, d_recs, SURVEY_DTYPE), table_of(jobs, d_jobs, CLOCK_JOB_DTYPE)
+        f_jrec, f_res = table_of(job_rec, d_jrec, np.uint32), table_of(results, d_res, CLOCK_RESULT_DTYPE)
+        f_rec_cap = (chain_recs if recs is None else max(len(recs), 1)) if rec_cap is None else rec_cap
+        f_job_cap = (chain_jobs if jobs is None and job_rec is None and results is None else
+                     min(len(x) for x in (jobs, job_rec, results) if x is not None)) if job_cap is None else job_cap
+        fh = hits if follow_hits is None else np.ascontiguousarray(follow_hits, dtype=HIT_DTYPE)
+        f_cap = len(fh)
+        d_fh = d_h if follow_hits is None else dev(max(fh.nbytes, 16)).upload(fh)
+        f_count = (None if count is None else d_cnt.ptr) if isinstance(follow_count, str) else count_of(follow_count, None)
+        d_in, d_fol = dev(f_cap * PKTIN_DTYPE.itemsize, sentinel), dev(f_cap * FOLLOW_PKT_DTYPE.itemsize, sentinel)
+        d_out, d_len = dev(f_cap * PKTOUT_DTYPE.itemsize, sentinel), dev(f_cap * 4, sentinel)
+        d_sums = dev(max(f_rec_cap, 1) * FOLLOW_SUM_DTYPE.itemsize, sentinel)
+        if zero_out:
+            check(lib().btbbx_memset(d_out.ptr, 0, min(zero_out, f_cap) * PKTOUT_DTYPE.itemsize), "memset")
+        no_jobs = f_job_cap == 0
+        check(lib().btbbx_follow_hits_device(d_w.ptr, n_words, pitch_words, n_streams, d_fh.ptr, f_count, f_cap, f_recs.ptr,
+                                             count_of(rec_count, d_nrec), f_rec_cap, None if no_jobs else f_jobs.ptr,
+                                             None if no_jobs else f_jrec.ptr, None if no_jobs else f_res.ptr,
+                                             None if no_jobs else count_of(n_jobs, d_n), f_job_cap, ftp, _ptr(entry), clk_div, clk_phase,
+                                             max_length, d_in.ptr, d_fol.ptr, d_out.ptr, d_len.ptr if lengths else None, d_sums.ptr, None),
+              "btbbx_follow_hits_device")
+        check(lib().btbbx_sync(None), "sync")
+        n_recs = int(d_nrec.download(np.uint32, 2)[0])
+        nj = int(d_n.download(np.uint32, 2)[0])
+        return dict(n_recs=n_recs, recs=d_recs.download(SURVEY_DTYPE, chain_recs)[:min(n_recs, chain_recs)], n_jobs=nj,
+                    jobs=d_jobs.download(CLOCK_JOB_DTYPE, chain_jobs)[:nj], job_rec=d_jrec.download(np.uint32, chain_jobs)[:nj],
+                    results=d_res.download(CLOCK_RESULT_DTYPE, chain_jobs)[:nj],
+                    pkt_in=d_in.download(PKTIN_DTYPE, f_cap), follow=d_fol.download(FOLLOW_PKT_DTYPE, f_cap),
+                    pkt_out=d_out.download(PKTOUT_DTYPE, f_cap), lengths=d_len.download(np.uint32, f_cap),
+                    sums=d_sums.download(FOLLOW_SUM_DTYPE, max(f_rec_cap, 1)))
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def follow(words, search_bits, n_streams=1, pitch_words=None, channels=None, clkn0=0, clk_div=625, clk_phase=0, afh=False,
+           aliased=False, max_obs=1024, max_ac_errors=2, rec_cap=1 << 16, hit_cap=1 << 16, packets=True, n_words=None):
+    """Capture in, every packet of every piconet decoded with its piconet's UAP and clock (btbbx_follow_host): acquire() and,
+    behind it, the FOLLOWING stage over the same ordered hit list.  Returns dict(recs, job_rec, results as acquire() returns
+    them; n_hits = all hits; hits / follow / pkts = the first min(n_hits, hit_cap) in (stream, offset) order (pkts None with
+    packets=False); sums = one FOLLOW_SUM_DTYPE per record, over all hits)."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if pitch_words is None:
+        pitch_words = len(words) // n_streams
+    if n_words is None:
+        n_words = pitch_words
+    assert n_words <= pitch_words and (n_streams - 1) * pitch_words + n_words <= len(words)
+    table = _channel_table(channels, n_streams)
+    k, hk = max(rec_cap, 1), max(hit_cap, 1)
+    recs, sums = np.zeros(k, dtype=SURVEY_DTYPE), np.zeros(k, dtype=FOLLOW_SUM_DTYPE)
+    job_rec, results = np.zeros(k, np.uint32), np.zeros(k, dtype=CLOCK_RESULT_DTYPE)
+    hits, fol = np.zeros(hk, dtype=HIT_DTYPE), np.zeros(hk, dtype=FOLLOW_PKT_DTYPE)
+    pkts = np.zeros(hk, dtype=PKTOUT_DTYPE) if packets else None
+    n_jobs, n_hits = C.c_uint64(0), C.c_uint64(0)
+    flags = (JOBS_AFH if afh else 0) | (JOBS_ALIASED if aliased else 0)
+    n = check(lib().btbbx_follow_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, max_ac_errors,
+                                      None if table is None else _ptr(table), clkn0, clk_div, clk_phase, _ptr(recs), rec_cap, flags,
+                                      max_obs, _ptr(job_rec), _ptr(results), rec_cap, C.byref(n_jobs), _ptr(hits), _ptr(fol),
+                                      None if pkts is None else _ptr(pkts), hit_cap, C.byref(n_hits), _ptr(sums)), "btbbx_follow_host")
+    nr, nj, nh = min(n, rec_cap), min(n_jobs.value, rec_cap), min(n_hits.value, hit_cap)
+    return dict(recs=recs[:nr], job_rec=job_rec[:nj], results=results[:nj], n_hits=n_hits.value, hits=hits[:nh], follow=fol[:nh],
+                pkts=None if pkts is None else pkts[:nh], sums=sums[:nr])

@@ -16,6 +16,8 @@
 //
 //   5. acquire_slots_kernel / acquire_fill_kernel (survey_jobs.h)   a separate entry, btbbx_survey_clock_jobs_device: from the records
 //      and this scratch (read only) to the job table and observation arrays of the batch CLK1-27 reversal
+//   6. follow_stage / follow_clock / follow_tally_kernel (follow.h)   a separate entry, btbbx_follow_hits_device: behind the
+//      reversal, every hit decoded with its piconet's UAP and clock and checked against the piconet's hop selection
 //
 // Nothing here synchronises or reads back: the list's length stays in device memory.
 #include "common.h"
@@ -532,6 +534,7 @@ __global__ __launch_bounds__(SV_THREADS) void survey_walk_kernel(const uint32_t 
 }
 
 #include "survey_jobs.h"
+#include "follow.h"
 
 // ---- C ABI ------------------------------------------------------------------------------------------
 
@@ -857,35 +860,50 @@ extern "C" int btbbx_survey_clock_jobs_device(const btbbx_survey_rec *d_recs, co
 	return BTBBX_OK;
 }
 
-extern "C" int64_t btbbx_acquire_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
-				      uint64_t search_bits, int max_ac_errors, const uint8_t *channels,
-				      uint32_t clkn0, uint32_t clk_div, uint32_t clk_phase,
-				      btbbx_survey_rec *recs, uint64_t rec_cap, int16_t *clk6_candidates,
-				      uint32_t flags, uint32_t max_obs,
-				      btbbx_clock_job *jobs, uint32_t *job_rec, btbbx_clock_result *results, uint64_t job_cap,
-				      uint64_t *n_jobs, uint32_t *candidates, uint32_t cand_cap)
+// What btbbx_follow_host appends to the chain of btbbx_acquire_host (null: the chain alone).
+struct FollowOut {
+	btbbx_hit *hits;
+	btbbx_follow_pkt *follow;
+	btbbx_pkt_out *pkts;
+	uint64_t hit_cap;
+	uint64_t *n_hits;
+	btbbx_follow_sum *sums;
+};
+
+// The chain of btbbx_acquire_host / btbbx_follow_host (`who`).  With `fo` every stored record's job is worked, whatever job_cap
+// the caller has room for, job_rec / results may be null, and btbbx_follow_hits_device runs behind the batch reversal.
+static int64_t acquire_run(const char *who, const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			   uint64_t search_bits, int max_ac_errors, const uint8_t *channels,
+			   uint32_t clkn0, uint32_t clk_div, uint32_t clk_phase,
+			   btbbx_survey_rec *recs, uint64_t rec_cap, int16_t *clk6_candidates,
+			   uint32_t flags, uint32_t max_obs,
+			   btbbx_clock_job *jobs, uint32_t *job_rec, btbbx_clock_result *results, uint64_t job_cap,
+			   uint64_t *n_jobs, uint32_t *candidates, uint32_t cand_cap, const FollowOut *fo)
 {
 	btbbx_pkt_in entry;
 	memset(&entry, 0, sizeof(entry));
 	entry.clkn = clkn0;
 	entry.flags = 1u << 0;                                  // BTBB_WHITENED: what btbb_find_ac leaves (init_packet)
-	int rc = survey_check_args("btbbx_acquire_host", n_words, n_streams, channels, &entry, clk_div, clk_phase);
+	int rc = survey_check_args(who, n_words, n_streams, channels, &entry, clk_div, clk_phase);
 	if (rc)
 		return rc;
 	if (n_streams == 1)
 		pitch_words = n_words;
 	if (!words || (!recs && rec_cap) || pitch_words < n_words || search_bits + 63 > n_words * 64) {
-		set_error("btbbx_acquire_host: null pointer, pitch_words < n_words or search_bits + 63 > 64 n_words");
+		set_error("%s: null pointer, pitch_words < n_words or search_bits + 63 > 64 n_words", who);
 		return BTBBX_E_ARG;
 	}
-	if (!n_jobs || (job_cap && (!job_rec || !results)) || !max_obs || max_obs > 1024 || (flags & ~(BTBBX_JOBS_AFH | BTBBX_JOBS_ALIASED))) {
-		set_error("btbbx_acquire_host: no n_jobs, job_rec or results, max_obs %u outside 1..1024, or unknown bits in flags 0x%x", max_obs, flags);
+	if (!n_jobs || (!fo && job_cap && (!job_rec || !results)) || !max_obs || max_obs > 1024 || (flags & ~(BTBBX_JOBS_AFH | BTBBX_JOBS_ALIASED))) {
+		set_error("%s: no n_jobs, job_rec or results, max_obs %u outside 1..1024, or unknown bits in flags 0x%x", who, max_obs, flags);
 		return BTBBX_E_ARG;
 	}
 	rc = ctx_require();
 	if (rc)
 		return rc;
 	*n_jobs = 0;
+	if (fo)
+		*fo->n_hits = 0;
+	const uint64_t work_cap = fo ? rec_cap : job_cap;        // jobs worked on the device
 	if (!search_bits)
 		return 0;
 	CallScope scope;
@@ -901,12 +919,14 @@ extern "C" int64_t btbbx_acquire_host(const uint64_t *words, uint64_t n_words, u
 	if (rc)
 		return rc;
 	const uint32_t have = std::min(count, dev_cap);
+	if (fo)
+		*fo->n_hits = count;
 	if (!have)
 		return 0;
 	// One block for the survey's scratch, its records, and the builder's outputs; a second one, once the number of jobs is
 	// known, for the batch reversal (about 8 KiB of scratch per job).
 	const uint32_t dev_recs = (uint32_t)std::min<uint64_t>(rec_cap, have);
-	const uint32_t dev_jobs = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(job_cap, dev_recs));
+	const uint32_t dev_jobs = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(work_cap, dev_recs));
 	size_t at = 0;
 	auto take = [&](size_t bytes) { const size_t here = at; at += sv_up(bytes); return here; };
 	const size_t survey_bytes = btbbx_survey_scratch_bytes(have);
@@ -914,16 +934,20 @@ extern "C" int64_t btbbx_acquire_host(const uint64_t *words, uint64_t n_words, u
 	const size_t o_c6 = take(clk6_candidates ? (size_t)dev_recs * 64 * sizeof(int16_t) : 0), o_cnt = take(2 * sizeof(uint32_t));
 	const size_t o_jobs = take((size_t)dev_jobs * sizeof(btbbx_clock_job)), o_jrec = take((size_t)dev_jobs * sizeof(uint32_t));
 	const size_t o_off = take((size_t)have * sizeof(int32_t)), o_ch = take(have);
+	// the follow stage's outputs and its one intermediate (d_in)
+	const size_t o_fin = take(fo ? (size_t)have * sizeof(btbbx_pkt_in) : 0), o_ffol = take(fo ? (size_t)have * sizeof(btbbx_follow_pkt) : 0);
+	const size_t o_fout = take(fo ? (size_t)have * sizeof(btbbx_pkt_out) : 0), o_fsum = take(fo ? (size_t)dev_recs * sizeof(btbbx_follow_sum) : 0);
 	char *work = nullptr, *batch = nullptr;
 	if (hipMalloc((void **)&work, at) != hipSuccess) {
 		(void)hipGetLastError();
-		set_error("btbbx_acquire_host: %zu bytes of device memory for %u hits not available", at, have);
+		set_error("%s: %zu bytes of device memory for %u hits not available", who, at, have);
 		return BTBBX_E_NOMEM;
 	}
 	btbbx_survey_rec *d_recs = (btbbx_survey_rec *)(work + o_recs);
 	int16_t *d_c6 = clk6_candidates ? (int16_t *)(work + o_c6) : nullptr;
 	uint32_t *d_rec_count = (uint32_t *)block + 1, *d_n_jobs = (uint32_t *)(work + o_cnt);
 	btbbx_clock_job *d_jobs = (btbbx_clock_job *)(work + o_jobs);
+	btbbx_clock_result *d_res = nullptr;
 	uint32_t counts[2] = {0, 0}, n_piconets = 0;             // jobs, observations
 	uint64_t stored = 0;
 	hipError_t e = hipSuccess;
@@ -943,7 +967,7 @@ extern "C" int64_t btbbx_acquire_host(const uint64_t *words, uint64_t n_words, u
 		e = hipMemcpyAsync(&n_piconets, d_rec_count, sizeof(n_piconets), hipMemcpyDeviceToHost, q);
 	if (!rc && e == hipSuccess)
 		e = hipStreamSynchronize(q);
-	stored = job_cap ? std::min<uint64_t>(counts[0], dev_jobs) : 0;
+	stored = work_cap ? std::min<uint64_t>(counts[0], dev_jobs) : 0;
 	if (!rc && e == hipSuccess && stored) {
 		const uint32_t nj = (uint32_t)stored;
 		const size_t want_cand = candidates ? (size_t)nj * cand_cap * sizeof(uint32_t) : 0;
@@ -953,24 +977,48 @@ extern "C" int64_t btbbx_acquire_host(const uint64_t *words, uint64_t n_words, u
 		const size_t o_bs = more(batch_bytes), o_res = more((size_t)nj * sizeof(btbbx_clock_result)), o_cand = more(want_cand);
 		if (hipMalloc((void **)&batch, bat) != hipSuccess) {
 			(void)hipGetLastError();
-			set_error("btbbx_acquire_host: %zu bytes of device memory for %u jobs not available", bat, nj);
+			set_error("%s: %zu bytes of device memory for %u jobs not available", who, bat, nj);
 			rc = BTBBX_E_NOMEM;
 		}
+		if (!rc)
+			d_res = (btbbx_clock_result *)(batch + o_res);
 		// the caller's candidate slots go in first, so that the slots no job writes come back as they were
 		if (!rc && want_cand)
 			e = hipMemcpyAsync(batch + o_cand, candidates, want_cand, hipMemcpyHostToDevice, q);
 		if (!rc && e == hipSuccess)
 			rc = btbbx_hop_reversal_batch_device(d_jobs, d_n_jobs, nj, (const int32_t *)(work + o_off), (const uint8_t *)(work + o_ch), have,
-							     (btbbx_clock_result *)(batch + o_res), want_cand ? (uint32_t *)(batch + o_cand) : nullptr,
+							     d_res, want_cand ? (uint32_t *)(batch + o_cand) : nullptr,
 							     cand_cap, batch + o_bs, batch_bytes, q);
-		if (!rc && e == hipSuccess)
-			e = hipMemcpyAsync(results, batch + o_res, (size_t)nj * sizeof(btbbx_clock_result), hipMemcpyDeviceToHost, q);
+		const size_t nj_out = (size_t)std::min<uint64_t>(nj, job_cap);           // (= nj without the follow stage)
+		if (!rc && e == hipSuccess && results && nj_out)
+			e = hipMemcpyAsync(results, d_res, nj_out * sizeof(btbbx_clock_result), hipMemcpyDeviceToHost, q);
 		if (!rc && e == hipSuccess && want_cand)
 			e = hipMemcpyAsync(candidates, batch + o_cand, want_cand, hipMemcpyDeviceToHost, q);
 		if (!rc && e == hipSuccess && jobs)
 			e = hipMemcpyAsync(jobs, d_jobs, (size_t)nj * sizeof(btbbx_clock_job), hipMemcpyDeviceToHost, q);
-		if (!rc && e == hipSuccess)
-			e = hipMemcpyAsync(job_rec, work + o_jrec, (size_t)nj * sizeof(uint32_t), hipMemcpyDeviceToHost, q);
+		if (!rc && e == hipSuccess && job_rec && nj_out)
+			e = hipMemcpyAsync(job_rec, work + o_jrec, nj_out * sizeof(uint32_t), hipMemcpyDeviceToHost, q);
+	}
+	if (fo && !rc && e == hipSuccess) {
+		// behind the reversal on the same stream: no job stored means no job table at all (stages 0 and 1)
+		const uint32_t nj = (uint32_t)stored;
+		btbbx_pkt_out *d_out = (btbbx_pkt_out *)(work + o_fout);
+		e = hipMemsetAsync(d_out, 0, (size_t)have * sizeof(btbbx_pkt_out), q);  // (the decoder leaves alone what it does not assign)
+		if (e == hipSuccess)
+			rc = btbbx_follow_hits_device(d_words, n_words, pitch_words, n_streams, (const btbbx_hit *)(block + 256), (const uint32_t *)block,
+						      have, d_recs, d_rec_count, dev_recs, nj ? d_jobs : nullptr,
+						      nj ? (const uint32_t *)(work + o_jrec) : nullptr, nj ? d_res : nullptr, nj ? d_n_jobs : nullptr, nj,
+						      channels, &entry, clk_div, clk_phase, BTBBX_MAX_SYMBOLS, (btbbx_pkt_in *)(work + o_fin),
+						      (btbbx_follow_pkt *)(work + o_ffol), d_out, nullptr, (btbbx_follow_sum *)(work + o_fsum), q);
+		const size_t n_out = (size_t)std::min<uint64_t>(have, fo->hit_cap), n_sums = (size_t)std::min<uint64_t>(n_piconets, dev_recs);
+		if (!rc && e == hipSuccess && n_out)
+			e = hipMemcpyAsync(fo->hits, block + 256, n_out * sizeof(btbbx_hit), hipMemcpyDeviceToHost, q);
+		if (!rc && e == hipSuccess && n_out)
+			e = hipMemcpyAsync(fo->follow, work + o_ffol, n_out * sizeof(btbbx_follow_pkt), hipMemcpyDeviceToHost, q);
+		if (!rc && e == hipSuccess && n_out && fo->pkts)
+			e = hipMemcpyAsync(fo->pkts, d_out, n_out * sizeof(btbbx_pkt_out), hipMemcpyDeviceToHost, q);
+		if (!rc && e == hipSuccess && n_sums)
+			e = hipMemcpyAsync(fo->sums, work + o_fsum, n_sums * sizeof(btbbx_follow_sum), hipMemcpyDeviceToHost, q);
 	}
 	if (!rc && e == hipSuccess) {
 		const uint64_t n = std::min<uint64_t>(n_piconets, dev_recs);
@@ -989,4 +1037,99 @@ extern "C" int64_t btbbx_acquire_host(const uint64_t *words, uint64_t n_words, u
 	HIP_TRY(f);
 	*n_jobs = counts[0];
 	return (int64_t)n_piconets;
+}
+
+extern "C" int64_t btbbx_acquire_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				      uint64_t search_bits, int max_ac_errors, const uint8_t *channels,
+				      uint32_t clkn0, uint32_t clk_div, uint32_t clk_phase,
+				      btbbx_survey_rec *recs, uint64_t rec_cap, int16_t *clk6_candidates,
+				      uint32_t flags, uint32_t max_obs,
+				      btbbx_clock_job *jobs, uint32_t *job_rec, btbbx_clock_result *results, uint64_t job_cap,
+				      uint64_t *n_jobs, uint32_t *candidates, uint32_t cand_cap)
+{
+	return acquire_run("btbbx_acquire_host", words, n_words, pitch_words, n_streams, search_bits, max_ac_errors, channels, clkn0, clk_div,
+			   clk_phase, recs, rec_cap, clk6_candidates, flags, max_obs, jobs, job_rec, results, job_cap, n_jobs, candidates, cand_cap,
+			   nullptr);
+}
+
+// ---- following ------------------------------------------------------------------------------------------
+
+extern "C" int btbbx_follow_hits_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+					const btbbx_hit *d_hits, const uint32_t *d_count, uint32_t cap,
+					const btbbx_survey_rec *d_recs, const uint32_t *d_rec_count, uint32_t rec_cap,
+					const btbbx_clock_job *d_jobs, const uint32_t *d_job_rec, const btbbx_clock_result *d_results,
+					const uint32_t *d_n_jobs, uint32_t job_cap,
+					const uint8_t *channels, const btbbx_pkt_in *entry, uint32_t clk_div, uint32_t clk_phase,
+					uint32_t max_length, btbbx_pkt_in *d_in, btbbx_follow_pkt *d_follow, btbbx_pkt_out *d_out,
+					uint32_t *d_lengths, btbbx_follow_sum *d_sums, void *hip_stream)
+{
+	const char *who = "btbbx_follow_hits_device";
+	if (!d_words || !d_hits || !d_recs || !d_in || !d_follow || !d_out || !d_sums || !entry) {
+		set_error("%s: null pointer (words, hits, records, entry state or an output)", who);
+		return BTBBX_E_ARG;
+	}
+	if (job_cap && (!d_jobs || !d_job_rec || !d_results)) {
+		set_error("%s: job_cap = %u without jobs, their records or their results", who, job_cap);
+		return BTBBX_E_ARG;
+	}
+	if (!cap || !rec_cap) {
+		set_error("%s: cap = %u, rec_cap = %u", who, cap, rec_cap);
+		return BTBBX_E_ARG;
+	}
+	int rc = survey_check_args(who, n_words, n_streams, channels, entry, clk_div, clk_phase);
+	if (rc)
+		return rc;
+	if (((uintptr_t)d_words & 7) || ((uintptr_t)d_hits & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_count & 3) || ((uintptr_t)d_recs & 3) ||
+	    ((uintptr_t)d_rec_count & 3) || ((uintptr_t)d_jobs & 3) || ((uintptr_t)d_job_rec & 3) || ((uintptr_t)d_results & 3) ||
+	    ((uintptr_t)d_n_jobs & 3) || ((uintptr_t)d_in & 3) || ((uintptr_t)d_follow & 3) || ((uintptr_t)d_lengths & 3) || ((uintptr_t)d_sums & 3)) {
+		set_error("%s: misaligned pointer (words, hits and decoded packets 8 bytes, everything else 4)", who);
+		return BTBBX_E_ARG;
+	}
+	if (n_streams > 1 && pitch_words < n_words) {
+		set_error("%s: pitch_words < n_words", who);
+		return BTBBX_E_ARG;
+	}
+	rc = ctx_require();
+	if (rc)
+		return rc;
+	hipStream_t q = (hipStream_t)hip_stream;
+	SurveyChannels table;
+	memset(&table, 0, sizeof(table));
+	if (channels)
+		memcpy(table.ch, channels, n_streams);
+	// (launched for the caps, worked for the counts)
+	const uint32_t rec_blocks = (uint32_t)(((uint64_t)rec_cap + FW_THREADS - 1) / FW_THREADS);
+	const uint32_t hit_blocks = (uint32_t)(((uint64_t)cap + FW_THREADS - 1) / FW_THREADS);
+	hipLaunchKernelGGL(follow_stage_kernel, dim3(rec_blocks), dim3(FW_THREADS), 0, q, (const uint32_t *)d_recs, d_rec_count, rec_cap, d_job_rec,
+			   d_results, d_n_jobs, job_cap, d_sums);
+	hipLaunchKernelGGL(follow_clock_kernel, dim3(hit_blocks), dim3(FW_THREADS), 0, q, d_hits, d_count, cap, (const uint32_t *)d_recs, d_rec_count,
+			   rec_cap, d_jobs, d_results, (const btbbx_follow_sum *)d_sums, table, channels ? 0 : 1, n_streams, *entry, clk_div, clk_phase,
+			   d_in, d_follow);
+	HIP_TRY(hipGetLastError());
+	// the decoder is btbbx_decode_hits_counted_device's; without a count in HBM its form for cap packets
+	rc = d_count ? btbbx_decode_hits_counted_device(d_words, n_words, pitch_words, d_hits, d_in, d_count, cap, max_length, d_out, d_lengths, q)
+		     : btbbx_decode_hits_device(d_words, n_words, pitch_words, d_hits, d_in, cap, max_length, d_out, d_lengths, q);
+	if (rc)
+		return rc;
+	hipLaunchKernelGGL(follow_tally_kernel, dim3(hit_blocks), dim3(FW_THREADS), 0, q, (const btbbx_follow_pkt *)d_follow,
+			   (const btbbx_pkt_out *)d_out, d_count, cap, d_sums);
+	HIP_TRY(hipGetLastError());
+	return BTBBX_OK;
+}
+
+extern "C" int64_t btbbx_follow_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				     uint64_t search_bits, int max_ac_errors, const uint8_t *channels,
+				     uint32_t clkn0, uint32_t clk_div, uint32_t clk_phase,
+				     btbbx_survey_rec *recs, uint64_t rec_cap, uint32_t flags, uint32_t max_obs,
+				     uint32_t *job_rec, btbbx_clock_result *results, uint64_t job_cap, uint64_t *n_jobs,
+				     btbbx_hit *hits, btbbx_follow_pkt *follow, btbbx_pkt_out *pkts, uint64_t hit_cap, uint64_t *n_hits,
+				     btbbx_follow_sum *sums)
+{
+	if (!rec_cap || !recs || !sums || !n_jobs || !n_hits || (hit_cap && (!hits || !follow))) {
+		set_error("btbbx_follow_host: rec_cap = 0, or no recs, sums, n_jobs, n_hits, hits or follow");
+		return BTBBX_E_ARG;
+	}
+	const FollowOut fo = {hits, follow, pkts, hit_cap, n_hits, sums};
+	return acquire_run("btbbx_follow_host", words, n_words, pitch_words, n_streams, search_bits, max_ac_errors, channels, clkn0, clk_div,
+			   clk_phase, recs, rec_cap, nullptr, flags, max_obs, nullptr, job_rec, results, job_cap, n_jobs, nullptr, 0, &fo);
 }
