@@ -7,6 +7,9 @@ registers in their reflected software form; here the positions 0..6 and 0..23 ar
 * match_all: brute-force sliding 40-bit matcher over every offset
 * decode: what btbbx_le_decode_hits_device derives for one hit, as a dict keyed like LE_PKT_DTYPE
 * lell_fields: what lell_allocate_and_decode (reference bluetooth_le_packet.c:282-312) derives from bytes + MHz
+* Rules: the model's own branch points as options; the default is the model, any other value a deliberately wrong
+  decoder (tests/test_le_lattice_model.py shows that the lattice of tests/_le_lattice.py tells each from the right one)
+* mhz_of / pack / compare: helpers shared by the GPU test files
 """
 import ctypes as C
 import functools
@@ -17,6 +20,7 @@ ADV_AA = 0x8E89BED6
 ADV_CRC_INIT = 0x555555
 MAX_BYTES = 64
 CRC_TAPS = (1, 3, 4, 6, 9, 10)          # x^24 + x^10 + x^9 + x^6 + x^4 + x^3 + x + 1: the feedback enters these positions
+_CRC_TAP_MASK = sum(1 << t for t in CRC_TAPS)
 
 
 # ---- registers ---------------------------------------------------------------------------------------------------
@@ -43,14 +47,13 @@ def _whitening_2080(chan):
 def crc24_register(bits, crc_init):
     """The CRC register after the data bits (Vol 6 Part B 3.1.1, figure 3.4): positions 0..23 preset with CRCInit (LSB in
     position 0); per bit the feedback = position 23 XOR the data bit enters position 0 and is XORed into CRC_TAPS."""
-    pos = [(crc_init >> i) & 1 for i in range(24)]
-    for b in bits:
-        fb = pos[23] ^ int(b)
-        new = [fb] + pos[:23]
-        for t in CRC_TAPS:
-            new[t] ^= fb
-        pos = new
-    return pos
+    pos = crc_init & 0xFFFFFF                       # bit i = position i
+    for b in np.asarray(bits, np.uint8).tolist():
+        fb = (pos >> 23) ^ b
+        pos = ((pos << 1) & 0xFFFFFF) | fb          # every position moves up by one, the feedback enters position 0
+        if fb:
+            pos ^= _CRC_TAP_MASK
+    return [(pos >> i) & 1 for i in range(24)]
 
 
 def crc24_tx_bits(bits, crc_init):
@@ -105,16 +108,18 @@ def c_div(a, b):
     return q if (a >= 0) == (b > 0) else -q
 
 
-def channel_index(mhz):
-    """le_channel_index of the reference, its integer arithmetic and unsigned-char conversion included."""
+def channel_index(mhz, wrap=True):
+    """le_channel_index of the reference, its integer arithmetic and unsigned-char conversion included (wrap=False: the
+    value before that conversion)."""
+    m = 0xFF if wrap else -1
     if mhz == 2402:
         return 37
     if mhz < 2426:
-        return c_div(mhz - 2404, 2) & 0xFF
+        return c_div(mhz - 2404, 2) & m
     if mhz == 2426:
         return 38
     if mhz < 2480:
-        return (11 + c_div(mhz - 2428, 2)) & 0xFF
+        return (11 + c_div(mhz - 2428, 2)) & m
     return 39
 
 
@@ -130,26 +135,54 @@ def _max_run(v, n):
     return best
 
 
+def omitted_windows():
+    """The 38 windows with a run of seven or more equal bits that the reference's case list does not name, as its five
+    groups: a run of exactly seven ones at bits 0..6 or 5..11 with anything else in the window, seven ones at 4..10 with
+    bit 2 clear, nine zeros at 0..8 unless bits 9..11 are ones, and 0x401."""
+    return (frozenset(0x07F | (x << 8) for x in range(1, 16)), frozenset(0xFE0 | x for x in range(1, 16)),
+            frozenset(0x7F0 | x for x in range(4)), frozenset(0x200 | (x << 10) for x in range(3)), frozenset([0x401]))
+
+
+OMITTED_WINDOWS = frozenset().union(*omitted_windows())
+assert len(OMITTED_WINDOWS) == 38
+
+
 def _reference_run_windows():
     """The 12-bit windows the reference counts as an offense: those with a run of seven or more equal bits, minus the
-    38 its case list does not name (a run of exactly seven ones at bits 0..6 or 5..11 with anything else in the window,
-    seven ones at 4..10 with bit 2 clear, nine zeros at 0..8 unless bits 9..11 are ones, and 0x401)."""
-    missing = set()
-    missing |= {0x07F | (x << 8) for x in range(1, 16)}
-    missing |= {0xFE0 | x for x in range(1, 16)}
-    missing |= {0x7F0 | x for x in range(4)}
-    missing |= {0x200 | (x << 10) for x in range(3)}
-    missing.add(0x401)
-    return frozenset(v for v in range(4096) if _max_run(v, 12) >= 7 and v not in missing)
+    38 its case list does not name (omitted_windows)."""
+    return frozenset(v for v in range(4096) if _max_run(v, 12) >= 7 and v not in OMITTED_WINDOWS)
 
 
 RUN_WINDOWS = _reference_run_windows()
 
 
-def data_offenses(aa):
+class Rules:
+    """The branch points of the model as options.  Rules() is the model; every other value is a wrong decoder, used only
+    to show that a set of test cases tells it from the right one."""
+
+    def __init__(self, **kw):
+        self.run_windows = RUN_WINDOWS      # the 12-bit windows that count as an offense
+        self.transition_positions = 31      # bit pairs (i, i + 1) the transition count looks at (32: bit 31 against a zero)
+        self.data_mask = 0x1F               # `length` on a data channel
+        self.adv_mask = 0x3F                # `length` on an advertising channel
+        self.truncated_ge = False           # truncated when the packet's end is at (not only behind) the stream's end
+        self.read_past_end = False          # bits behind the stream's end come from the words that follow in memory
+        self.second_word_above = 56         # an octet at bit phase > this takes its upper bits from the next word
+        self.crc_init_mask = True           # CRCInit cut to 24 bits (False: the upper bits stay in a 32-bit reflected register)
+        self.uchar_wrap = True              # the channel index goes through the reference's unsigned char
+        self.seed_mask = True               # whitening seed = channel index & 0x3f (False: all eight bits enter the register)
+        for k, v in kw.items():
+            assert hasattr(self, k), k
+            setattr(self, k, v)
+
+
+MODEL = Rules()
+
+
+def data_offenses(aa, rules=MODEL):
     """aa_data_channel_offenses of the reference (bluetooth_le_packet.c:100-242), from its rules as listed there."""
-    bits = [(aa >> i) & 1 for i in range(32)]
-    transitions = sum(bits[i] != bits[i + 1] for i in range(31))
+    bits = [(aa >> i) & 1 for i in range(32)] + [0]
+    transitions = sum(bits[i] != bits[i + 1] for i in range(rules.transition_positions))
     n = max(transitions - 24, 0)
     top = bits[26:]
     n += 1 if sum(top[i] != top[i + 1] for i in range(5)) < 2 else 0
@@ -157,23 +190,23 @@ def data_offenses(aa):
     n += 1 if len(set(octs)) == 1 else 0
     n += 1 if aa == ADV_AA else 0
     n += 1 if bin(aa ^ ADV_AA).count("1") == 1 else 0
-    n += sum(1 for s in range(0, 21, 4) if (aa >> s) & 0xFFF in RUN_WINDOWS)
+    n += sum(1 for s in range(0, 21, 4) if (aa >> s) & 0xFFF in rules.run_windows)
     return n
 
 
-def lell_fields(bytes64, mhz):
+def lell_fields(bytes64, mhz, rules=MODEL):
     """What lell_allocate_and_decode(bytes64, mhz, 0, &p) leaves in p."""
     b = bytes(bytes64)
     aa = int.from_bytes(b[:4], "little")
-    ci = channel_index(mhz)
-    f = dict(access_address=aa, channel_idx=ci, channel_k=channel_k(mhz), is_data=int(ci < 37))
+    ci = channel_index(mhz, rules.uchar_wrap)
+    f = dict(access_address=aa, channel_idx=ci & 0xFF, channel_k=channel_k(mhz), is_data=int(ci < 37))
     if ci < 37:
-        off = data_offenses(aa)
-        f.update(length=b[5] & 0x1F, adv_type=0, adv_tx_add=0, adv_rx_add=0, access_address_offenses=off,
+        off = data_offenses(aa, rules)
+        f.update(length=b[5] & rules.data_mask, adv_type=0, adv_tx_add=0, adv_rx_add=0, access_address_offenses=off,
                  access_address_ok=int(off == 0))
     else:
         ok = aa == ADV_AA
-        f.update(length=b[5] & 0x3F, adv_type=b[4] & 0xF, adv_tx_add=int(bool(b[4] & 0x40)), adv_rx_add=int(bool(b[4] & 0x80)),
+        f.update(length=b[5] & rules.adv_mask, adv_type=b[4] & 0xF, adv_tx_add=int(bool(b[4] & 0x40)), adv_rx_add=int(bool(b[4] & 0x80)),
                  access_address_ok=int(ok), access_address_offenses=0 if ok else (1 if bin(aa ^ ADV_AA).count("1") == 1 else 32))
     return f
 
@@ -196,10 +229,10 @@ def match_all(words, n_words, search_bits, aa, max_errors):
     return keep.astype(np.uint64), err[keep], ((win[keep] >> np.uint64(8)) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
 
 
-def stream_bits(words, n_words, first, n):
-    """n bits of a packed stream from bit `first`, zeros past the stream's end."""
+def stream_bits(words, n_words, first, n, past_end=False):
+    """n bits of a packed stream from bit `first`, zeros past the stream's end (past_end: zeros only past len(words))."""
     out = np.zeros(n, np.uint8)
-    end = min(first + n, n_words * 64)
+    end = min(first + n, (len(words) if past_end else n_words) * 64)
     if end > first:
         w0, w1 = first // 64, (end + 63) // 64
         bits = np.unpackbits(np.asarray(words[w0:w1], np.uint64).view(np.uint8), bitorder="little")
@@ -207,26 +240,75 @@ def stream_bits(words, n_words, first, n):
     return out
 
 
-def decode(words, n_words, stream, offset, errors, mhz, crc_init):
-    """The record btbbx_le_decode_hits_device writes for a hit at `offset` (a dict keyed like LE_PKT_DTYPE)."""
-    ci = channel_index(mhz)
-    chan = ci & 0x3F
-    head = stream_bits(words, n_words, offset, 56)
+def _reverse24(x):
+    return int("{:024b}".format(x & 0xFFFFFF)[::-1], 2)
+
+
+_CRC_REFLECTED = _reverse24(_CRC_TAP_MASK | 1)         # 0xda6000
+
+
+def _crc24_unmasked(pdu_bits, crc_init):
+    """Rules(crc_init_mask=False): the reflected register (bit j = position 23 - j, shifted down) held in 32 bits, with
+    CRCInit's bits 24..31 left above it: they move down into the register as it shifts."""
+    s = _reverse24(crc_init) | (crc_init & 0xFF000000)
+    for b in np.asarray(pdu_bits, np.uint8).tolist():
+        fb = (s ^ b) & 1
+        s >>= 1
+        if fb:
+            s ^= _CRC_REFLECTED
+    return s
+
+
+def _whitening_unmasked(state, n):
+    """Rules(seed_mask=False): the reflected whitening register (bit j = position 6 - j) started from all eight bits of
+    channel index | 0x40."""
+    out = np.zeros(n, np.uint8)
+    for k in range(n):
+        o = state & 1
+        out[k] = o
+        if o:
+            state ^= 0x88
+        state >>= 1
+    return out
+
+
+def decode(words, n_words, stream, offset, errors, mhz, crc_init, rules=MODEL):
+    """The record btbbx_le_decode_hits_device writes for a hit at `offset` (a dict keyed like LE_PKT_DTYPE).  `words` is
+    the stream's row; only Rules(read_past_end=True) looks at what it holds behind n_words."""
+    ci = channel_index(mhz, rules.uchar_wrap)
+    past = rules.read_past_end
+    head = stream_bits(words, n_words, offset, 56, past)
     aa = bits_value(head[8:40])
-    wh = _whitening_2080(chan)
-    hdr = head[40:56] ^ wh[:16]
+    if rules.seed_mask:
+        wh = _whitening_2080(ci & 0x3F)
+    else:
+        wh = _whitening_unmasked((ci & 0xFF) | 0x40, 8 * 260)
+
+    def body_bits(n_octets):
+        raw = stream_bits(words, n_words, offset + 40, 8 * n_octets, past)
+        for k in range(n_octets):                   # an octet's upper bits lie in the next word at bit phases above 56
+            sh = (offset + 40 + 8 * k) & 63
+            if 56 < sh <= rules.second_word_above:
+                raw[8 * k + 64 - sh:8 * k + 8] = 0
+        return raw ^ wh[:8 * n_octets]
+
+    hdr = body_bits(2)
     L = bits_value(hdr[8:16])
     pdu_n = 2 + L
-    body = stream_bits(words, n_words, offset + 40, 8 * (pdu_n + 3)) ^ wh[:8 * (pdu_n + 3)]
+    body = body_bits(pdu_n + 3)
     pdu_b, crc_b = body[:8 * pdu_n], body[8 * pdu_n:]
-    crc_calc = bits_value(crc24_tx_bits(pdu_b, crc_init))
+    if rules.crc_init_mask:
+        crc_calc = bits_value(crc24_tx_bits(pdu_b, crc_init & 0xFFFFFF))
+    else:
+        crc_calc = _crc24_unmasked(pdu_b, crc_init)
     crc_rx = bits_value(crc_b)
-    truncated = offset + 40 + 8 * (pdu_n + 3) > n_words * 64
+    end = offset + 40 + 8 * (pdu_n + 3)
+    truncated = end >= n_words * 64 if rules.truncated_ge else end > n_words * 64
     raw = (int(aa).to_bytes(4, "little") + bits_octets(body))[:MAX_BYTES]
     raw = raw + bytes(MAX_BYTES - len(raw))
     rec = dict(offset=offset, stream=stream, aa_errors=errors, crc_ok=int(not truncated and crc_calc == crc_rx), crc_rx=crc_rx,
                crc_calc=crc_calc, pdu_bytes=pdu_n, truncated=int(truncated), bytes=raw)
-    rec.update(lell_fields(raw, mhz))
+    rec.update(lell_fields(raw, mhz, rules))
     return rec
 
 
@@ -239,6 +321,32 @@ def record_dict(r):
     d = {k: int(r[k]) for k in FIELDS}
     d["bytes"] = bytes(np.asarray(r["bytes"], np.uint8))
     return d
+
+
+# ---- shared by the GPU test files -------------------------------------------------------------------------------------
+ADV_MHZ = (2402, 2426, 2480)
+
+
+def mhz_of(n_streams):
+    """Stream s: channels 37 / 38 / 39 first, then the data channels' MHz."""
+    data = [m for m in range(2404, 2480, 2) if m != 2426]
+    return np.array([(list(ADV_MHZ) + data)[s % 40] for s in range(n_streams)], np.uint16)
+
+
+def pack(sym):
+    sym = np.asarray(sym, np.uint8)
+    pad = (-len(sym)) % 64
+    return np.packbits(np.concatenate([sym, np.zeros(pad, np.uint8)]), bitorder="little").view(np.uint64)
+
+
+def compare(got, want, phys, ref=None):
+    assert len(got) == len(want), (len(got), len(want))
+    for g, w in zip(got, want):
+        gd = record_dict(g)
+        assert gd == w, (gd, w)
+        if ref is not None:
+            rf = ref_lell_fields(ref, gd["bytes"], int(phys[gd["stream"]]))
+            assert {k: gd[k] for k in rf} == rf
 
 
 # ---- the compiled reference ------------------------------------------------------------------------------------------

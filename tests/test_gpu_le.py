@@ -13,7 +13,7 @@ import libbtbb_amd as bt
 
 pytestmark = pytest.mark.gpu
 
-ADV_MHZ = (2402, 2426, 2480)
+ADV_MHZ = _le.ADV_MHZ
 CONN_AA = 0x50654C3B
 
 
@@ -25,10 +25,7 @@ def _init():
     bt.init(2)
 
 
-def _mhz_of(n_streams):
-    """Stream s: channels 37 / 38 / 39 first, then the data channels' MHz."""
-    data = [m for m in range(2404, 2480, 2) if m != 2426]
-    return np.array([(list(ADV_MHZ) + data)[s % 40] for s in range(n_streams)], np.uint16)
+_mhz_of, _pack, _compare = _le.mhz_of, _le.pack, _le.compare        # (shared with tests/test_gpu_le_lattice.py)
 
 
 @functools.lru_cache(maxsize=None)
@@ -50,12 +47,6 @@ def _packet_bits(rng, mhz, adv, length=None, errors=0, corrupt=False, crc_init=_
     return bits
 
 
-def _pack(sym):
-    sym = np.asarray(sym, np.uint8)
-    pad = (-len(sym)) % 64
-    return np.packbits(np.concatenate([sym, np.zeros(pad, np.uint8)]), bitorder="little").view(np.uint64)
-
-
 def _model(words2d, n_words, search_bits, phys, aa, crc_init, max_errors, cache):
     out = []
     for s in range(words2d.shape[0]):
@@ -71,16 +62,6 @@ def _model(words2d, n_words, search_bits, phys, aa, crc_init, max_errors, cache)
                 cache[key] = _le.decode(words2d[s], n_words, s, int(o), int(e), int(phys[s]), crc_init)
             out.append(cache[key])
     return out
-
-
-def _compare(got, want, phys, ref=None):
-    assert len(got) == len(want), (len(got), len(want))
-    for g, w in zip(got, want):
-        gd = _le.record_dict(g)
-        assert gd == w, (gd, w)
-        if ref is not None:
-            rf = _le.ref_lell_fields(ref, gd["bytes"], int(phys[gd["stream"]]))
-            assert {k: gd[k] for k in rf} == rf
 
 
 @pytest.fixture(scope="module")
