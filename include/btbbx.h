@@ -453,6 +453,65 @@ int64_t btbbx_le_scan_host(const uint64_t *words, uint64_t n_words, uint64_t pit
 			   uint64_t search_bits, const uint16_t *phys_channel, uint32_t aa, uint32_t crc_init,
 			   int max_errors, btbbx_le_pkt *pkts, uint64_t cap);
 
+/* ---- promiscuous LE connection discovery: access address and CRCInit ------------------------- */
+/* On the 37 data channels every connection has an AA and a CRCInit of its own; these entries find both without being
+ * told either.  Offset o of stream s is a CANDIDATE iff
+ *   1. le_channel_index(phys_channel[s]) < 37 (an advertising channel yields no candidates);
+ *   2. bits o .. o+7 alternate and bit o equals bit o+8 (the preamble of the AA behind it), no error allowed;
+ *   3. the AA = bits o+8 .. o+39 has no data-channel offense (aa_data_channel_offenses, bluetooth_le_packet.c:100-242);
+ *   4. the two dewhitened header octets have (h0 & 3) != 0, (h0 & 0xe0) == 0 and h1 <= max_len;
+ *   5. the packet lies in the stream: o + 40 + 8 * (2 + h1 + 3) <= 64 * n_words;
+ *   6. o < search_bits.
+ * Its CRCInit is the one 24-bit preset with which the CRC over the 2 + h1 PDU octets equals the received CRC: the value to
+ * hand to btbbx_le_decode_hits_device.  Noise yields candidates as well (2.7e-5 of the offsets at max_len 27); a connection
+ * shows as the same (AA, CRCInit) again and again, on several channels. */
+typedef struct btbbx_le_cand {   /* 24 bytes */
+	uint64_t offset;         /* first preamble bit */
+	uint32_t access_address;
+	uint32_t crc_init;       /* as btbbx_le_decode_hits_device takes it */
+	uint16_t stream;
+	uint8_t  header0, length; /* dewhitened h0, h1 */
+	uint32_t conn;           /* from the scan: the data channel index (0..36); after grouping: index into the connection
+	                          * list, 0xffffffff = none */
+} btbbx_le_cand;
+typedef struct btbbx_le_conn {   /* 32 bytes */
+	uint32_t access_address, crc_init;
+	uint32_t n_packets, n_empty; /* members; members with length 0 */
+	uint64_t channel_mask;   /* bit ch set iff a member lies on data channel index ch */
+	uint64_t first;          /* index of its first member in the sorted candidate list */
+} btbbx_le_conn;
+
+/* Stage 1: every candidate of offsets [0, search_bits) of every stream, in no particular order.  Arguments and their check as
+ * btbbx_le_scan_device (search_bits + 39 <= 64 * n_words); d_phys_channel: one uint16 per stream, the RF frequency in MHz;
+ * max_len 0..255 (27: the 4.0 / 4.1 maximum, 0: empty PDUs only).  *d_cand_count (zeroed by the caller) counts every candidate,
+ * also those past cand_cap, which are dropped.  d_cands: 8-byte aligned. */
+int btbbx_le_discover_scan_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				  uint64_t search_bits, const uint16_t *d_phys_channel, uint32_t max_len,
+				  btbbx_le_cand *d_cands, uint32_t cand_cap, uint32_t *d_cand_count, void *hip_stream);
+
+/* Stage 2: the first min(*d_cand_count, cand_cap) candidates are sorted stably by (AA << 24 | CRCInit, stream, offset) in
+ * place; every group of equal (AA, CRCInit) with at least min_count members becomes one btbbx_le_conn, in ascending (AA, CRCInit)
+ * order; every candidate's conn (on entry its channel index) becomes the index of its connection or 0xffffffff.
+ * *d_conn_count counts every such group; the conn_cap smallest are stored.  Nothing is read back: both counts stay in device
+ * memory.  d_scratch: btbbx_le_discover_scratch_bytes(cand_cap) bytes, 16-byte aligned.
+ * A list that does not come from the scan must keep the scan's promises: conn = the data channel index of the candidate's
+ * stream (only its low six bits are read, nothing is validated: a wrong value gives a wrong channel_mask), and offsets
+ * below 2^48 (the sort keys carry 48 offset bits; the scan's argument check keeps its own offsets below 2^46). */
+size_t btbbx_le_discover_scratch_bytes(uint32_t cand_cap);
+int btbbx_le_discover_group_device(btbbx_le_cand *d_cands, const uint32_t *d_cand_count, uint32_t cand_cap, uint32_t min_count,
+				   btbbx_le_conn *d_conns, uint32_t conn_cap, uint32_t *d_conn_count,
+				   void *d_scratch, size_t scratch_bytes, void *hip_stream);
+
+/* Host wrapper: copy in, scan (repeated with room for every candidate when the first buffer was too small, as
+ * btbbx_scan_host does), group, copy out.  Returns the number of connections or a negative BTBBX_E_*; when that exceeds
+ * conn_cap the conn_cap smallest (AA, CRCInit) are returned.  cands may be NULL (cand_cap 0); otherwise it receives the first
+ * cand_cap candidates of the sorted list.  *n_cands_out (may be NULL) = all candidates found.  Safe to call from several host
+ * threads at once. */
+int64_t btbbx_le_discover_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			       uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+			       btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+			       uint64_t *n_cands_out);
+
 /* ---- hop selection and CLK1-27 reversal ------------------------- */
 #define BTBBX_SEQUENCE_LENGTH 134217728u   /* values of CLK1-27, bluetooth_piconet.h:102 */
 

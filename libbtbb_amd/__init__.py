@@ -89,6 +89,14 @@ LE_PKT_DTYPE = np.dtype([("offset", "<u8"), ("stream", "<u2"), ("aa_errors", "u1
                          ("pad", "u1", (4,))])
 assert LE_PKT_DTYPE.itemsize == 104 and LE_PKT_DTYPE.fields["bytes"][1] == 36
 
+# LE connection discovery (include/btbbx.h btbbx_le_cand / btbbx_le_conn; le_discover.h checks the C layout with static_asserts)
+LE_CAND_DTYPE = np.dtype([("offset", "<u8"), ("access_address", "<u4"), ("crc_init", "<u4"), ("stream", "<u2"),
+                          ("header0", "u1"), ("length", "u1"), ("conn", "<u4")])
+LE_CONN_DTYPE = np.dtype([("access_address", "<u4"), ("crc_init", "<u4"), ("n_packets", "<u4"), ("n_empty", "<u4"),
+                          ("channel_mask", "<u8"), ("first", "<u8")])
+LE_NO_CONN = 0xFFFFFFFF
+assert LE_CAND_DTYPE.itemsize == 24 and LE_CONN_DTYPE.itemsize == 32
+
 # one surveyed piconet (include/btbbx.h btbbx_survey_rec; survey.hip checks the C layout with static_asserts)
 SURVEY_DTYPE = np.dtype([("lap", "<u4"), ("flags", "<u4"), ("uap", "u1"), ("clk_offset", "u1"), ("used_channels", "u1"),
                          ("settled_by", "u1"), ("afh_map", "u1", (10,)), ("first_stream", "<u2"), ("n_packets", "<u4"),
@@ -172,6 +180,10 @@ SIGNATURES = {
     "btbbx_le_scan_device": (C.c_int, [_vp, _u64, _u64, _u32, _u64, _u32, C.c_int, _vp, _u32, _vp, _vp]),
     "btbbx_le_decode_hits_device": (C.c_int, [_vp, _u64, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp]),
     "btbbx_le_scan_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, C.c_int, _vp, _u64]),
+    "btbbx_le_discover_scan_device": (C.c_int, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _vp, _u32, _vp, _vp]),
+    "btbbx_le_discover_scratch_bytes": (C.c_size_t, [_u32]),
+    "btbbx_le_discover_group_device": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _vp, C.c_size_t, _vp]),
+    "btbbx_le_discover_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp]),
     "btbbx_survey_scratch_bytes": (C.c_size_t, [_u32]),
     "btbbx_survey_hits_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp,
                                            _vp, C.c_size_t, _vp]),
@@ -373,6 +385,32 @@ def le_scan(words, search_bits, phys_channels, aa=LE_ADV_AA, crc_init=LE_ADV_CRC
     if n > cap and not truncate:
         raise BtbbError("packet buffer too small: %d > %d" % (n, cap))
     return pkts[:min(n, cap)]
+
+
+def le_discover(words, search_bits, phys_channels, max_len=27, min_count=2, n_streams=1, pitch_words=None, n_words=None,
+                conn_cap=1 << 16, cand_cap=1 << 20, truncate=False):
+    """The Bluetooth LE connections of a data-channel capture, neither access address nor CRCInit given: every candidate
+    packet (include/btbbx.h: preamble rule, an access address without offense, a plausible header of length <= max_len, the
+    CRCInit that makes its CRC come out) grouped by (access address, CRCInit).  words / n_streams / pitch_words / n_words /
+    phys_channels as le_scan.  Returns (conns, cands): LE_CONN_DTYPE records of the groups with at least min_count members in
+    ascending (AA, CRCInit) order, and the LE_CAND_DTYPE candidates sorted by (AA, CRCInit, stream, offset), each with the index
+    of its connection in `conn` (LE_NO_CONN: none).  With truncate=True the first conn_cap / cand_cap records are returned when
+    more were found."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if pitch_words is None:
+        pitch_words = len(words) // n_streams
+    if n_words is None:
+        n_words = pitch_words
+    assert n_words <= pitch_words and (n_streams - 1) * pitch_words + n_words <= len(words)
+    phys = np.ascontiguousarray(np.broadcast_to(np.asarray(phys_channels, dtype=np.uint16), (n_streams,)))
+    conns = np.empty(max(conn_cap, 1), dtype=LE_CONN_DTYPE)          # (not zeroed: only the records returned are ever touched)
+    cands = np.empty(max(cand_cap, 1), dtype=LE_CAND_DTYPE)
+    n_cands = C.c_uint64(0)
+    n = check(lib().btbbx_le_discover_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, _ptr(phys), max_len, min_count,
+                                           _ptr(conns), conn_cap, _ptr(cands), cand_cap, C.byref(n_cands)), "btbbx_le_discover_host")
+    if (n > conn_cap or n_cands.value > cand_cap) and not truncate:
+        raise BtbbError("buffers too small: %d connections > %d or %d candidates > %d" % (n, conn_cap, n_cands.value, cand_cap))
+    return conns[:min(n, conn_cap)].copy(), cands[:min(n_cands.value, cand_cap)].copy()
 
 
 class DeviceBuffer:

@@ -535,3 +535,5 @@ extern "C" int64_t btbbx_le_scan_host(const uint64_t *words, uint64_t n_words, u
 	}
 	return (int64_t)count;
 }
+
+#include "le_discover.h"

@@ -23,12 +23,13 @@
 #include "common.h"
 #include "packet_launch.h"
 #include "wave_scan.h"
+#include "radix_sort.h"
 #include <algorithm>
 #include <string.h>
 
 #define SV_THREADS     256
 #define SV_WAVES       (SV_THREADS / 64)
-#define SV_SORT_TILE   4096u               // keys a workgroup ranks per pass (16 rounds of 256)
+#define SV_SORT_TILE   RADIX_SORT_TILE     // keys a workgroup ranks per pass (16 rounds of 256)
 #define SV_GRP_TILE    2048u               // records a workgroup flags and lays out (8 rounds of 256)
 #define SV_BATCH       16                  // trial rows a walking wave keeps in flight
 #define SV_MAX_PATTERN 1000                // MAX_PATTERN_LENGTH, bluetooth_piconet.h
@@ -60,7 +61,7 @@ static SurveyLayout survey_layout(uint32_t cap)
 {
 	SurveyLayout L;
 	const size_t c = cap ? cap : 1;
-	L.sort_blocks = (uint32_t)((c + SV_SORT_TILE - 1) / SV_SORT_TILE);
+	L.sort_blocks = radix_sort_blocks(c);
 	L.grp_tiles = (uint32_t)((c + SV_GRP_TILE - 1) / SV_GRP_TILE);
 	size_t at = 0;
 	auto take = [&](size_t bytes) { const size_t here = at; at += sv_up(bytes); return here; };
@@ -219,6 +220,21 @@ __global__ __launch_bounds__(SV_THREADS) void survey_scatter_kernel(const uint64
 		run[tid] += s;
 		__syncthreads();
 	}
+}
+
+// the passes as launches (radix_sort.h): what every list sorted on the device goes through
+int radix_sort_passes(const RadixBufs &b, const btbbx_hit *hits, const RadixPass *passes, int n_passes, int cur, hipStream_t q)
+{
+	const uint32_t blocks = radix_sort_blocks(b.cap);
+	for (int p = 0; p < n_passes; p++) {
+		hipLaunchKernelGGL(survey_hist_kernel, dim3(blocks), dim3(SV_THREADS), 0, q, b.keys[cur], b.vals[cur], hits, b.params, blocks,
+				   passes[p].by_stream, passes[p].shift, b.hist);
+		hipLaunchKernelGGL(survey_rows_kernel, dim3(256), dim3(SV_THREADS), 0, q, b.hist, blocks, b.tot);
+		hipLaunchKernelGGL(survey_scatter_kernel, dim3(blocks), dim3(SV_THREADS), 0, q, b.keys[cur], b.vals[cur], hits, b.params, b.cap,
+				   blocks, passes[p].by_stream, passes[p].shift, b.hist, b.tot, b.keys[cur ^ 1], b.vals[cur ^ 1]);
+		cur ^= 1;
+	}
+	return cur;
 }
 
 // ---- 2. group table, sorted records, channel maps ------------------------------------------------------
@@ -631,7 +647,7 @@ extern "C" int btbbx_survey_hits_device(const uint64_t *d_words, uint64_t n_word
 	hipLaunchKernelGGL(survey_key_kernel, dim3(cap_blocks), dim3(SV_THREADS), 0, q, d_hits, d_count, cap, params, keys[0], vals[0]);
 
 	// digits from the least significant: stream, offset, LAP -- only those that can differ
-	struct Pass { int by_stream; uint32_t shift; } passes[12];
+	RadixPass passes[12];
 	int n_passes = 0;
 	for (uint32_t b = 0; b < bits_of(n_streams - 1); b += 8)
 		passes[n_passes++] = {1, b};
@@ -639,15 +655,8 @@ extern "C" int btbbx_survey_hits_device(const uint64_t *d_words, uint64_t n_word
 		passes[n_passes++] = {0, b};
 	for (uint32_t b = 40; b < 64; b += 8)
 		passes[n_passes++] = {0, b};
-	int cur = 0;
-	for (int p = 0; p < n_passes; p++) {
-		hipLaunchKernelGGL(survey_hist_kernel, dim3(L.sort_blocks), dim3(SV_THREADS), 0, q, keys[cur], vals[cur], d_hits, params,
-				   L.sort_blocks, passes[p].by_stream, passes[p].shift, hist);
-		hipLaunchKernelGGL(survey_rows_kernel, dim3(256), dim3(SV_THREADS), 0, q, hist, L.sort_blocks, tot);
-		hipLaunchKernelGGL(survey_scatter_kernel, dim3(L.sort_blocks), dim3(SV_THREADS), 0, q, keys[cur], vals[cur], d_hits, params, cap,
-				   L.sort_blocks, passes[p].by_stream, passes[p].shift, hist, tot, keys[cur ^ 1], vals[cur ^ 1]);
-		cur ^= 1;
-	}
+	const RadixBufs bufs = {{keys[0], keys[1]}, {vals[0], vals[1]}, hist, tot, params, cap};
+	const int cur = radix_sort_passes(bufs, d_hits, passes, n_passes, 0, q);
 
 	hipLaunchKernelGGL(survey_mark_kernel, dim3(L.grp_tiles), dim3(SV_THREADS), 0, q, keys[cur], params, tiles);
 	hipLaunchKernelGGL(survey_tiles_kernel, dim3(1), dim3(SV_THREADS), 0, q, tiles, L.grp_tiles, params, gstart, d_rec_count, (uint32_t)cur);
