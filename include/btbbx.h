@@ -477,7 +477,8 @@ typedef struct btbbx_le_cand {   /* 24 bytes */
 typedef struct btbbx_le_conn {   /* 32 bytes */
 	uint32_t access_address, crc_init;
 	uint32_t n_packets, n_empty; /* members; members with length 0 */
-	uint64_t channel_mask;   /* bit ch set iff a member lies on data channel index ch */
+	uint64_t channel_mask;   /* bit ch set iff a member lies on data channel index ch (a shifted alias of a connection shows the
+	                          * same mask: btbbx_le_track_device ranks aliases away by the hop check) */
 	uint64_t first;          /* index of its first member in the sorted candidate list */
 } btbbx_le_conn;
 
@@ -511,6 +512,85 @@ int64_t btbbx_le_discover_host(const uint64_t *words, uint64_t n_words, uint64_t
 			       uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
 			       btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
 			       uint64_t *n_cands_out);
+
+/* ---- LE connection tracking: interval, event counters, hop increment and hop check ----------- */
+/* Behind the grouping, for every stored connection: its packets in time order, its connection events, the connection interval,
+ * the event counter of every event, the hop increment of channel selection algorithm #1, and for every packet whether it lies
+ * on the channel that selection predicts -- the check that tells a connection from its shifted aliases, whose groups hop with
+ * it only by accident.  All arithmetic is integer arithmetic.  With N = min(*d_cand_count, cand_cap), K = min(*d_conn_count,
+ * conn_cap), and bit o of every stream received at the same instant (the survey's premise), unit_bits bits being 1.25 ms (1250
+ * at one sample per symbol):
+ *   1. MEMBERS.  Candidate i < N is a member of connection g < K iff conn == g, stream < n_streams and
+ *      ch = le_channel_index(d_phys_channel[stream]) < 37; any other candidate gets sixteen 0xff bytes as its record.
+ *   2. TIME ORDER.  The members of g by ascending (offset, stream), ties by list index; rank = the position in that order.
+ *   3. EVENTS.  end_m = offset_m + 80 + 8 * length_m.  In time order member m opens a new event iff it is the first member, or
+ *      ch_m != ch_(m-1), or offset_m > end_(m-1) + ifs_bits.  Event e has the anchor A_e (the offset of its first member) and the
+ *      channel C_e; first_anchor = A_0, map_mask = OR of 1 << C_e, n_used its popcount.
+ *   4. INTERVAL.  D_e = A_(e+1) - A_e, q_e = (D_e + unit_bits / 2) / unit_bits; the pair FITS iff q_e >= 1 and
+ *      |D_e - q_e * unit_bits| <= jitter_bits; n_fit counts the fitting pairs, interval = the gcd of their q_e (64 bits; 0 when
+ *      none fits).  TIMED iff 6 <= interval <= 3200.
+ *   5. COUNTERS (TIMED).  P = interval * unit_bits, k_e = (D_e + P / 2) / P, n_0 = 0, n_(e+1) = n_e + k_e in 64 bits.
+ *   6. HOP INCREMENT (TIMED).  used[] = the channels of map_mask, ascending.  V(c) = {c}; with BTBBX_LE_TRACK_REMAP also every v
+ *      in 0..36 outside map_mask with used[v mod n_used] == c (the remapping, with the observed map taken as the connection's).
+ *      S(h, u), h in 5..16, u in 0..36 = the number of events with (u + h * n_e) mod 37 in V(C_e).  The pair with the largest S
+ *      wins, ties to the smallest h, then the smallest u; n_second = the largest S of any other pair; HOPPING iff
+ *      S(winner) > n_second.
+ *   7. PREDICTION (TIMED).  unmapped_e = (first_unmapped + hop_increment * n_e) mod 37; expected_e = unmapped_e if map_mask
+ *      holds it, else with REMAP used[unmapped_e mod n_used], else 0xff; on_hop = expected_e == C_e.  n_on_hop and n_off_hop
+ *      count EVENTS (an unknown prediction in neither), so n_on_hop == S(winner).  Every packet carries its event's values.
+ * Not TIMED: hop_increment, first_unmapped, n_on_hop, n_off_hop, n_second and every packet's counter and on_hop are 0, unmapped
+ * and expected 0xff; everything else is written all the same.  A connection without a member: a record of zeros.
+ * LIMITS, which follow from the rules: the counter is relative to the first event SEEN; an interval whose visible event spacings
+ * are all multiples of k comes out k times too large (two events two intervals apart: doubled); a used channel that never shows
+ * makes the remapping wrong; a parameter or channel map update inside the capture is not followed. */
+#define BTBBX_LE_TRACK_REMAP   1u   /* flags: score and predict through the remapping of the observed channel map */
+#define BTBBX_LE_TRACK_TIMED   1u   /* btbbx_le_track.flags: 6 <= interval <= 3200 */
+#define BTBBX_LE_TRACK_HOPPING 2u   /* btbbx_le_track.flags: TIMED and n_on_hop > n_second */
+
+typedef struct btbbx_le_track {      /* 48 bytes, one per stored connection */
+	uint64_t first_anchor;       /* offset of the first event's first packet */
+	uint64_t map_mask;           /* bit c: some event lies on data channel index c */
+	uint32_t n_events, n_fit;    /* events; consecutive event pairs that fit the 1.25 ms grid */
+	uint32_t interval;           /* in units of 1.25 ms; 0: no fitting pair; a gcd >= 2^32 is stored as 0xffffffff */
+	uint32_t n_on_hop, n_off_hop;/* TIMED: events whose channel is / is not the predicted one (unknown predictions count in neither) */
+	uint32_t n_second;           /* TIMED: the best score of any other (hop increment, first unmapped channel) pair */
+	uint8_t  hop_increment, first_unmapped, n_used, flags;
+	uint32_t reserved;           /* written as 0 */
+} btbbx_le_track;
+
+typedef struct btbbx_le_track_pkt {  /* 16 bytes, one per candidate, parallel to the sorted candidate list */
+	uint32_t rank;               /* position among its connection's members in time order */
+	uint32_t event;              /* index of its event within the connection */
+	uint32_t counter;            /* low 32 bits of the event counter relative to the first event seen; 0 unless TIMED */
+	uint8_t  channel;            /* data channel index of its stream */
+	uint8_t  unmapped, expected; /* TIMED: unmappedChannel of its event, the channel predicted for it; else 0xff */
+	uint8_t  on_hop;             /* expected == channel */
+} btbbx_le_track_pkt;              /* a candidate that is no member of a stored connection: sixteen 0xff bytes */
+
+/* The input is what btbbx_le_discover_group_device leaves: the sorted list, every candidate's conn, the connection count.  A
+ * list from elsewhere must keep its promises: the members of g are exactly the candidates [conns[g].first, first + n_packets),
+ * and offsets lie below 2^48 (the sort keys carry 48 offset bits).  d_tracks[0 .. K) and d_pkts[0 .. N) are written, every byte
+ * of them, nothing behind them; nothing is read back and the call is asynchronous on hip_stream.  d_scratch:
+ * btbbx_le_track_scratch_bytes(cand_cap, conn_cap) bytes (about 48 per candidate and 1.8 KiB per connection).  BTBBX_E_ARG,
+ * before any launch: a null pointer, a record or scratch pointer that is not 8-byte aligned (the counters: 4, the channels: 2),
+ * n_streams == 0, unit_bits < 2, jitter_bits >= unit_bits / 2, a scratch that is too small.  cand_cap == 0 or conn_cap == 0
+ * succeeds and writes nothing. */
+size_t btbbx_le_track_scratch_bytes(uint32_t cand_cap, uint32_t conn_cap);
+int btbbx_le_track_device(const btbbx_le_cand *d_cands, const uint32_t *d_cand_count, uint32_t cand_cap,
+			  const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
+			  const uint16_t *d_phys_channel, uint32_t n_streams,
+			  uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+			  btbbx_le_track *d_tracks, btbbx_le_track_pkt *d_pkts,
+			  void *d_scratch, size_t scratch_bytes, void *hip_stream);
+
+/* Host wrapper: btbbx_le_discover_host, then the tracking on the same stream, copy out.  The discovery's arguments and return
+ * value; tracks: conn_cap records, parallel to conns; pkts (may be NULL): cand_cap records, parallel to cands.  Safe to call from
+ * several host threads at once. */
+int64_t btbbx_le_track_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			    uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+			    btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+			    uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+			    btbbx_le_track *tracks, btbbx_le_track_pkt *pkts);
 
 /* ---- hop selection and CLK1-27 reversal ------------------------- */
 #define BTBBX_SEQUENCE_LENGTH 134217728u   /* values of CLK1-27, bluetooth_piconet.h:102 */

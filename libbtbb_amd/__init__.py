@@ -96,6 +96,14 @@ LE_CONN_DTYPE = np.dtype([("access_address", "<u4"), ("crc_init", "<u4"), ("n_pa
                           ("channel_mask", "<u8"), ("first", "<u8")])
 LE_NO_CONN = 0xFFFFFFFF
 assert LE_CAND_DTYPE.itemsize == 24 and LE_CONN_DTYPE.itemsize == 32
+# LE connection tracking (include/btbbx.h btbbx_le_track / btbbx_le_track_pkt; le_track.h checks the C layout with static_asserts)
+LE_TRACK_REMAP, LE_TRACK_TIMED, LE_TRACK_HOPPING = 1, 1, 2
+LE_TRACK_DTYPE = np.dtype([("first_anchor", "<u8"), ("map_mask", "<u8"), ("n_events", "<u4"), ("n_fit", "<u4"), ("interval", "<u4"),
+                           ("n_on_hop", "<u4"), ("n_off_hop", "<u4"), ("n_second", "<u4"), ("hop_increment", "u1"),
+                           ("first_unmapped", "u1"), ("n_used", "u1"), ("flags", "u1"), ("reserved", "<u4")])
+LE_TRACK_PKT_DTYPE = np.dtype([("rank", "<u4"), ("event", "<u4"), ("counter", "<u4"), ("channel", "u1"), ("unmapped", "u1"),
+                               ("expected", "u1"), ("on_hop", "u1")])
+assert LE_TRACK_DTYPE.itemsize == 48 and LE_TRACK_PKT_DTYPE.itemsize == 16
 
 # one surveyed piconet (include/btbbx.h btbbx_survey_rec; survey.hip checks the C layout with static_asserts)
 SURVEY_DTYPE = np.dtype([("lap", "<u4"), ("flags", "<u4"), ("uap", "u1"), ("clk_offset", "u1"), ("used_channels", "u1"),
@@ -184,6 +192,10 @@ SIGNATURES = {
     "btbbx_le_discover_scratch_bytes": (C.c_size_t, [_u32]),
     "btbbx_le_discover_group_device": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _vp, C.c_size_t, _vp]),
     "btbbx_le_discover_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp]),
+    "btbbx_le_track_scratch_bytes": (C.c_size_t, [_u32, _u32]),
+    "btbbx_le_track_device": (C.c_int, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "btbbx_le_track_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
+                                        _vp, _vp]),
     "btbbx_survey_scratch_bytes": (C.c_size_t, [_u32]),
     "btbbx_survey_hits_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp,
                                            _vp, C.c_size_t, _vp]),
@@ -411,6 +423,34 @@ def le_discover(words, search_bits, phys_channels, max_len=27, min_count=2, n_st
     if (n > conn_cap or n_cands.value > cand_cap) and not truncate:
         raise BtbbError("buffers too small: %d connections > %d or %d candidates > %d" % (n, conn_cap, n_cands.value, cand_cap))
     return conns[:min(n, conn_cap)].copy(), cands[:min(n_cands.value, cand_cap)].copy()
+
+
+def le_track(words, search_bits, phys_channels, max_len=27, min_count=2, n_streams=1, pitch_words=None, n_words=None,
+             unit_bits=1250, ifs_bits=200, jitter_bits=50, flags=LE_TRACK_REMAP, conn_cap=1 << 12, cand_cap=1 << 20, truncate=False):
+    """le_discover, then the tracking of every connection it stored (include/btbbx.h btbbx_le_track_device): events, connection
+    interval, event counters, hop increment and the hop check of every packet.  unit_bits: the bits of 1.25 ms; ifs_bits: the
+    longest gap between the packets of one connection event; jitter_bits: how far an event spacing may lie from the 1.25 ms
+    grid.  Returns (conns, cands, tracks, pkts): le_discover's two arrays, LE_TRACK_DTYPE records parallel to conns and
+    LE_TRACK_PKT_DTYPE records parallel to cands."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if pitch_words is None:
+        pitch_words = len(words) // n_streams
+    if n_words is None:
+        n_words = pitch_words
+    assert n_words <= pitch_words and (n_streams - 1) * pitch_words + n_words <= len(words)
+    phys = np.ascontiguousarray(np.broadcast_to(np.asarray(phys_channels, dtype=np.uint16), (n_streams,)))
+    conns = np.empty(max(conn_cap, 1), dtype=LE_CONN_DTYPE)
+    tracks = np.empty(max(conn_cap, 1), dtype=LE_TRACK_DTYPE)
+    cands = np.empty(max(cand_cap, 1), dtype=LE_CAND_DTYPE)
+    pkts = np.empty(max(cand_cap, 1), dtype=LE_TRACK_PKT_DTYPE)
+    n_cands = C.c_uint64(0)
+    n = check(lib().btbbx_le_track_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, _ptr(phys), max_len, min_count,
+                                        _ptr(conns), conn_cap, _ptr(cands), cand_cap, C.byref(n_cands), unit_bits, ifs_bits, jitter_bits,
+                                        flags, _ptr(tracks), _ptr(pkts)), "btbbx_le_track_host")
+    if (n > conn_cap or n_cands.value > cand_cap) and not truncate:
+        raise BtbbError("buffers too small: %d connections > %d or %d candidates > %d" % (n, conn_cap, n_cands.value, cand_cap))
+    nc, nk = min(n, conn_cap), min(n_cands.value, cand_cap)
+    return conns[:nc].copy(), cands[:nk].copy(), tracks[:nc].copy(), pkts[:nk].copy()
 
 
 class DeviceBuffer:

@@ -649,8 +649,85 @@ extern "C" int btbbx_le_discover_group_device(btbbx_le_cand *d_cands, const uint
 	return le_disc_launch_group(d_cands, d_cand_count, cand_cap, min_count, d_conns, conn_cap, d_conn_count, d_scratch, q);
 }
 
-// Host wrapper: copy in, scan (again with room for every candidate when the first guess was too small, as btbbx_scan_host does),
-// group, copy out.
+// What the host chain leaves on the device, inside the caller's CallScope: the counters, the sorted candidates, the connection
+// records and, behind them, `tail` (tail_bytes(dev_cap, dev_conns) bytes for what a caller runs next on the same stream).
+struct LeDiscHostRun {
+	uint32_t dev_cap, dev_conns;                   // what the device buffers hold
+	uint32_t count, have, n_conns;                 // candidates found, candidates kept (min(count, dev_cap)), connections found
+	uint32_t *d_count, *d_conn_count;
+	btbbx_le_cand *d_cands;
+	btbbx_le_conn *d_conns;
+	const uint16_t *d_phys;
+	char *tail;
+};
+
+// copy in, scan (again with room for every candidate when the first guess was too small, as btbbx_scan_host does), group; both
+// counts read back.  have == 0: nothing was grouped and nothing but count is set
+static int le_disc_host_chain(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, uint64_t search_bits,
+			      const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count, uint64_t conn_cap,
+			      size_t (*tail_bytes)(uint32_t, uint32_t), LeDiscHostRun *r)
+{
+	int rc;
+	if (n_streams == 1)
+		pitch_words = n_words;
+	hipStream_t q = scope_stream();
+	const uint64_t cap_words = (uint64_t)(n_streams - 1) * pitch_words + n_words;
+	const size_t words_bytes = ((size_t)(cap_words + 1) * 8 + 255) & ~(size_t)255;
+	char *dblock = (char *)scope_device(words_bytes + 2 * (size_t)n_streams);
+	if (!dblock)
+		return BTBBX_E_NOMEM;
+	const uint64_t *d_words = (const uint64_t *)dblock;
+	uint16_t *d_phys = (uint16_t *)(dblock + words_bytes);
+	HIP_TRY(hipMemcpyAsync(dblock, words, (size_t)cap_words * 8, hipMemcpyHostToDevice, q));
+	HIP_TRY(hipMemcpyAsync(d_phys, phys_channel, 2 * (size_t)n_streams, hipMemcpyHostToDevice, q));
+	// first guess: one candidate per 4096 offsets + slack (noise yields one per 37 000 at max_len 27, one per 4000 at 255)
+	uint64_t guess = search_bits / 4096 * n_streams + 4096;
+	uint32_t dev_cap = guess > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)guess;
+	uint32_t count = 0;
+	char *block = nullptr;
+	size_t cand_bytes = 0, scratch_bytes = 0, conn_bytes = 0;
+	uint32_t dev_conns = 0;
+	for (int pass = 0; pass < 2; pass++) {
+		cand_bytes = ld_up((size_t)dev_cap * sizeof(btbbx_le_cand));
+		scratch_bytes = ld_up(btbbx_le_discover_scratch_bytes(dev_cap));
+		dev_conns = (uint32_t)std::min<uint64_t>(conn_cap, dev_cap);
+		conn_bytes = ld_up((size_t)dev_conns * sizeof(btbbx_le_conn));
+		block = (char *)scope_hits(256 + cand_bytes + scratch_bytes + conn_bytes + (tail_bytes ? tail_bytes(dev_cap, dev_conns) : 0));
+		if (!block)
+			return BTBBX_E_NOMEM;
+		HIP_TRY(hipMemsetAsync(block, 0, 2 * sizeof(uint32_t), q));
+		rc = le_disc_launch_scan(d_words, n_words, pitch_words, n_streams, search_bits, d_phys, max_len, (btbbx_le_cand *)(block + 256),
+					 dev_cap, (uint32_t *)block, q);
+		if (rc)
+			return rc;
+		HIP_TRY(hipMemcpyAsync(&count, block, sizeof(count), hipMemcpyDeviceToHost, q));
+		HIP_TRY(hipStreamSynchronize(q));
+		if (count <= dev_cap)
+			break;
+		dev_cap = count;
+	}
+	r->dev_cap = dev_cap;
+	r->dev_conns = dev_conns;
+	r->count = count;
+	r->have = std::min(count, dev_cap);
+	r->n_conns = 0;
+	r->d_count = (uint32_t *)block;
+	r->d_conn_count = (uint32_t *)block + 1;
+	r->d_cands = (btbbx_le_cand *)(block + 256);
+	r->d_conns = (btbbx_le_conn *)(block + 256 + cand_bytes + scratch_bytes);
+	r->d_phys = d_phys;
+	r->tail = block + 256 + cand_bytes + scratch_bytes + conn_bytes;
+	if (!r->have)
+		return BTBBX_OK;
+	rc = le_disc_launch_group(r->d_cands, r->d_count, dev_cap, min_count, r->d_conns, dev_conns, r->d_conn_count, block + 256 + cand_bytes, q);
+	if (rc)
+		return rc;
+	HIP_TRY(hipMemcpyAsync(&r->n_conns, r->d_conn_count, sizeof(uint32_t), hipMemcpyDeviceToHost, q));
+	HIP_TRY(hipStreamSynchronize(q));
+	return BTBBX_OK;
+}
+
+// Host wrapper: the chain above, copy out.
 extern "C" int64_t btbbx_le_discover_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
 					  uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
 					  btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
@@ -667,65 +744,23 @@ extern "C" int64_t btbbx_le_discover_host(const uint64_t *words, uint64_t n_word
 	rc = ctx_require();
 	if (rc)
 		return rc;
-	if (n_streams == 1)
-		pitch_words = n_words;
 	if (n_cands_out)
 		*n_cands_out = 0;
 	CallScope scope;
 	hipStream_t q = scope_stream();
-	const uint64_t cap_words = (uint64_t)(n_streams - 1) * pitch_words + n_words;
-	const size_t words_bytes = ((size_t)(cap_words + 1) * 8 + 255) & ~(size_t)255;
-	char *dblock = (char *)scope_device(words_bytes + 2 * (size_t)n_streams);
-	if (!dblock)
-		return BTBBX_E_NOMEM;
-	const uint64_t *d_words = (const uint64_t *)dblock;
-	uint16_t *d_phys = (uint16_t *)(dblock + words_bytes);
-	HIP_TRY(hipMemcpyAsync(dblock, words, (size_t)cap_words * 8, hipMemcpyHostToDevice, q));
-	HIP_TRY(hipMemcpyAsync(d_phys, phys_channel, 2 * (size_t)n_streams, hipMemcpyHostToDevice, q));
-	// first guess: one candidate per 4096 offsets + slack (noise yields one per 37 000 at max_len 27, one per 4000 at 255)
-	uint64_t guess = search_bits / 4096 * n_streams + 4096;
-	uint32_t dev_cap = guess > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)guess;
-	uint32_t count = 0;
-	char *block = nullptr;
-	size_t cand_bytes = 0, scratch_bytes = 0;
-	uint32_t dev_conns = 0;
-	for (int pass = 0; pass < 2; pass++) {
-		cand_bytes = ld_up((size_t)dev_cap * sizeof(btbbx_le_cand));
-		scratch_bytes = ld_up(btbbx_le_discover_scratch_bytes(dev_cap));
-		dev_conns = (uint32_t)std::min<uint64_t>(conn_cap, dev_cap);
-		block = (char *)scope_hits(256 + cand_bytes + scratch_bytes + (size_t)dev_conns * sizeof(btbbx_le_conn));
-		if (!block)
-			return BTBBX_E_NOMEM;
-		HIP_TRY(hipMemsetAsync(block, 0, 2 * sizeof(uint32_t), q));
-		rc = le_disc_launch_scan(d_words, n_words, pitch_words, n_streams, search_bits, d_phys, max_len, (btbbx_le_cand *)(block + 256),
-					 dev_cap, (uint32_t *)block, q);
-		if (rc)
-			return rc;
-		HIP_TRY(hipMemcpyAsync(&count, block, sizeof(count), hipMemcpyDeviceToHost, q));
-		HIP_TRY(hipStreamSynchronize(q));
-		if (count <= dev_cap)
-			break;
-		dev_cap = count;
-	}
-	const uint32_t have = std::min(count, dev_cap);
-	if (n_cands_out)
-		*n_cands_out = count;
-	if (!have)
-		return 0;
-	uint32_t *d_count = (uint32_t *)block, *d_conn_count = (uint32_t *)block + 1;
-	btbbx_le_cand *d_cands = (btbbx_le_cand *)(block + 256);
-	btbbx_le_conn *d_conns = (btbbx_le_conn *)(block + 256 + cand_bytes + scratch_bytes);
-	rc = le_disc_launch_group(d_cands, d_count, dev_cap, min_count, d_conns, dev_conns, d_conn_count, block + 256 + cand_bytes, q);
+	LeDiscHostRun r;
+	rc = le_disc_host_chain(words, n_words, pitch_words, n_streams, search_bits, phys_channel, max_len, min_count, conn_cap, nullptr, &r);
 	if (rc)
 		return rc;
-	uint32_t n_conns = 0;
-	HIP_TRY(hipMemcpyAsync(&n_conns, d_conn_count, sizeof(n_conns), hipMemcpyDeviceToHost, q));
-	HIP_TRY(hipStreamSynchronize(q));
-	const uint64_t nc = std::min<uint64_t>(n_conns, dev_conns), nk = std::min<uint64_t>(have, cand_cap);
+	if (n_cands_out)
+		*n_cands_out = r.count;
+	if (!r.have)
+		return 0;
+	const uint64_t nc = std::min<uint64_t>(r.n_conns, r.dev_conns), nk = std::min<uint64_t>(r.have, cand_cap);
 	if (nc)
-		HIP_TRY(hipMemcpyAsync(conns, d_conns, (size_t)nc * sizeof(btbbx_le_conn), hipMemcpyDeviceToHost, q));
+		HIP_TRY(hipMemcpyAsync(conns, r.d_conns, (size_t)nc * sizeof(btbbx_le_conn), hipMemcpyDeviceToHost, q));
 	if (nk)
-		HIP_TRY(hipMemcpyAsync(cands, d_cands, (size_t)nk * sizeof(btbbx_le_cand), hipMemcpyDeviceToHost, q));
+		HIP_TRY(hipMemcpyAsync(cands, r.d_cands, (size_t)nk * sizeof(btbbx_le_cand), hipMemcpyDeviceToHost, q));
 	HIP_TRY(hipStreamSynchronize(q));
-	return (int64_t)n_conns;
+	return (int64_t)r.n_conns;
 }

@@ -1,6 +1,7 @@
 // radix_sort.h -- the stable LSD radix passes of survey.hip (survey_hist / rows / scatter_kernel: eight bits per pass over an array
 // of 64-bit keys that travels with an array of record indices), for every list that is ordered on the device: the survey's hits
-// by (LAP, offset, stream) and the LE discovery's candidates by (AA, CRCInit, stream, offset) (le_discover.h).
+// by (LAP, offset, stream), the LE discovery's candidates by (AA, CRCInit, stream, offset) (le_discover.h) and the LE tracking's
+// slots by (connection, offset, stream) (le_track.h).
 #pragma once
 #include "common.h"
 
