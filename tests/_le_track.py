@@ -7,6 +7,8 @@ unmapped channel) pairs --, not from the kernels (le_track.h sorts by radix pass
 * csa1: the FORWARD channel selection algorithm #1 (Core v5.x Vol 6 Part B 4.5.8.2), written from the specification, one
   event after the other; it shares nothing with the model's inverse
 * synth / lattice / seam_list / chain_capture: the lists and the capture the CPU and GPU tests share
+* align_list / crowd_list / long_event_list: lists laid out on the kernels' waves, workgroups and tiles, for the path model of
+  tests/_le_track_paths.py
 """
 import collections
 import functools
@@ -43,6 +45,8 @@ class Rules:
         self.remap_descending = False    # the table of used channels in descending order
         self.second_other_h = False      # n_second over pairs with another h only
         self.count_packets = False       # scores and tallies count packets, not events
+        self.tie_unstable = False        # members at one (offset, stream) in descending order of their index
+        self.hop_truncated = False       # rule 7's unmapped channel from the counter as it is stored, 32 bits of it
         for k, v in kw.items():
             assert hasattr(self, k), k
             setattr(self, k, v)
@@ -54,7 +58,8 @@ VARIANTS = dict(event_ge=dict(event_ge=True), event_no_channel=dict(event_channe
                 valid_to_3199=dict(valid=(6, 3199)), k_floor=dict(k_floor=True), h_0_36=dict(h_range=(0, 36)),
                 tie_h_largest=dict(tie_h_largest=True), tie_u_largest=dict(tie_u_largest=True), remap_mod37=dict(remap_mod37=True),
                 remap_descending=dict(remap_descending=True), second_other_h=dict(second_other_h=True),
-                count_packets=dict(count_packets=True))
+                count_packets=dict(count_packets=True), tie_unstable=dict(tie_unstable=True),
+                hop_from_truncated_counter=dict(hop_truncated=True))
 
 
 def _remap(v, used, rules):
@@ -77,7 +82,7 @@ def track(cands, n_conns, mhz, n_streams, unit_bits, ifs_bits, jitter_bits, flag
     pkts = [None] * len(cands)
     tracks = []
     for g in range(n_conns):
-        order = sorted(members[g], key=lambda i: (cands[i].offset, cands[i].stream, i))      # rule 2
+        order = sorted(members[g], key=lambda i: (cands[i].offset, cands[i].stream, -i if rules.tie_unstable else i))   # rule 2
         events = []                                                        # rule 3: [anchor, channel, [members]]
         for r, i in enumerate(order):
             c = cands[i]
@@ -137,7 +142,7 @@ def track(cands, n_conns, mhz, n_streams, unit_bits, ifs_bits, jitter_bits, flag
             n_second = max(s for k, s in S.items() if (k[0] != hop if rules.second_other_h else k != (hop, u0)))
             tflags = TIMED | (HOPPING if best > n_second else 0)
             for e, ev in enumerate(events):                                # rule 7
-                unmapped[e] = (u0 + hop * n[e]) % 37
+                unmapped[e] = (u0 + hop * (n[e] & 0xFFFFFFFF if rules.hop_truncated else n[e])) % 37
                 if (map_mask >> unmapped[e]) & 1:
                     expected[e] = unmapped[e]
                 elif flags & REMAP:
@@ -166,12 +171,13 @@ def track_array(tracks, dtype):
 
 def pkt_array(pkts, dtype):
     a = np.zeros(len(pkts), dtype)
-    raw = a.view(np.uint8).reshape(len(pkts), dtype.itemsize)
-    for i, p in enumerate(pkts):
-        if p is None:
-            raw[i] = 0xFF
-        else:
-            a[i] = tuple(p)
+    if not len(pkts):
+        return a
+    none = np.array([p is None for p in pkts], bool)
+    rows = np.array([(0,) * len(Pkt._fields) if p is None else p for p in pkts], np.int64)
+    for k, name in enumerate(Pkt._fields):
+        a[name] = rows[:, k]
+    a.view(np.uint8).reshape(len(pkts), dtype.itemsize)[none] = 0xFF
     return a
 
 
@@ -183,6 +189,16 @@ def csa1(u0, h, n, chmap):
     unmapped = u0
     for _ in range(n):
         unmapped = (unmapped + h) % 37
+    if (chmap >> unmapped) & 1:
+        return unmapped
+    table = [c for c in range(37) if (chmap >> c) & 1]
+    return table[unmapped % len(table)]
+
+
+def csa1_at(u0, h, n, chmap):
+    """csa1 without the walk over the events, for counters the walk cannot reach (tests/test_le_track_paths_model.py holds the
+    two against each other)."""
+    unmapped = (u0 + h * n) % 37
     if (chmap >> unmapped) & 1:
         return unmapped
     table = [c for c in range(37) if (chmap >> c) & 1]
@@ -227,6 +243,8 @@ N_STREAMS = 40
 UNIT, IFS, JITTER = 1250, 200, 50
 
 Case = collections.namedtuple("Case", "name cands")
+TIE_CASES = ("tie at one offset, long packet first", "tie at one offset, short packet first")
+BEYOND_32 = (0, 1, 2, 3, (1 << 32) + 5, (1 << 32) + 6, (1 << 32) + 7, (1 << 32) + 9)
 
 
 def _conn_ids():
@@ -308,6 +326,13 @@ def lattice():
     add("foreign streams among the members", hop_events(7, full, 6, 10, 5) + [(3000 + 2 * 6 * UNIT + 90, 40, 0), (3000 + 3 * 6 * UNIT + 90, 37, 0),
                                                                               (3000 + 4 * 6 * UNIT + 90, 39, 0), (3000 + 5 * 6 * UNIT, 65535, 0)])
     add("only foreign streams", [(100, 37, 0), (100 + 6 * UNIT, 41, 0)])
+    # rule 2: two members at one (offset, stream) stand in list order.  The packet behind them lies within ifs of the end of the long
+    # one and beyond ifs of the end of the short one: one event where the long one is the later of the two, two where it is not
+    # (lattice_list keeps the order the case names, whatever its shuffle does)
+    add(TIE_CASES[0], [(9000, 6, 27), (9000, 6, 0), (9000 + 80 + 216 + IFS, 6, 0)])
+    add(TIE_CASES[1], [(9000, 6, 0), (9000, 6, 27), (9000 + 80 + 216 + IFS, 6, 0)])
+    # rule 5 / 7: event counters beyond 2^32 (2^32 mod 37 = 7: the hop needs the whole count, the record stores 32 bits of it)
+    add("counter beyond 2^32", [(3000 + n * 6 * UNIT, csa1_at(29, 7, n, full), 0) for n in BEYOND_32])
     return tuple(cases)
 
 
@@ -325,6 +350,11 @@ def lattice_list(min_count=1, noise=40, seed=3):
                            int(rng.integers(0, 37)), 1, 0, 0))
         raw[-1] = raw[-1]._replace(channel=raw[-1].stream)
     raw = [raw[i] for i in rng.permutation(len(raw))]
+    for case in lattice():                                                 # the tied pairs: in the order their case lists them
+        if case.name in TIE_CASES:
+            i, j = raw.index(case.cands[0]), raw.index(case.cands[1])
+            if i > j:
+                raw[i], raw[j] = raw[j], raw[i]
     conns, cands = ld.group(raw, min_count)
     return conns, cands, [by_key.get((c.access_address, c.crc_init)) for c in conns]
 
@@ -403,3 +433,166 @@ def chain_model():
     """(conns, cands) of the discovery's model on the chain capture, min_count 2."""
     cap, _ = chain_capture()
     return ld.group(ld.capture_candidates(cap, 27), 2)
+
+
+# ---- lists on the alignments of the kernels' waves, workgroups and tiles ------------------------------------------------------
+# tests/_le_track_paths.py works out, from the model's own slot and event numbering, which paths of le_track.h a list drives.
+# The grouping numbers the connections by (access address, CRCInit) and the tracking lays their slots and events out in that order,
+# so a builder that hands out ascending access addresses decides where every connection begins.
+FULL_MAP = (1 << 37) - 1
+FIVE_MAP = (1 << 1) | (1 << 8) | (1 << 19) | (1 << 25) | (1 << 33)
+OFF_HOP_EVENTS = 400
+LT_SCORE_ALIGN = 1024                      # LT_SCORE_TILE of le_track.h (tests/test_le_track_paths_model.py holds the two together)
+
+
+def off_hop_plan(slot0):
+    """The events of the "off hop" connection of align_list (OFF_HOP_EVENTS events of two packets, the first at slot slot0) that are
+    put one channel up: one in its first wave of slots and up to two in its last, which it shares with others; five in its second
+    wave, one in its third, none in the rest, which are its own."""
+    s, last = slot0 % 64, (slot0 % 64 + 2 * OFF_HOP_EVENTS - 1) // 64
+    assert 0 < s <= 62 and (s + 2 * OFF_HOP_EVENTS) % 64 > 1 and last >= 5
+    first_of = lambda k: (64 * k - s + 1) // 2                                  # noqa: E731  (the first event that opens in wave k)
+    return (0,) + tuple(first_of(1) + i for i in (2, 5, 9, 20, 30)) + (first_of(2) + 7,) + tuple(range(max(first_of(last), OFF_HOP_EVENTS - 2), OFF_HOP_EVENTS))
+
+
+class _Laid:
+    """Connections laid back to back: conn() plants the next one (interval 6, stream = data channel index), on the next access
+    address; self.ev and self.slot are the event and the slot it will begin at (stream c of LATTICE_MHZ is data channel c)."""
+
+    def __init__(self, seed):
+        self.rng = np.random.default_rng(seed)
+        self.raw, self.names, self.ev, self.slot, self.k = [], {}, 0, 0, 0
+
+    def conn(self, name, counters, chmap=FULL_MAP, interval=6, h=7, u0=0, per_event=1, off_hop=(), jitter=20, gap=150, base=None):
+        """Events with these counters, per_event packets `gap` bits apart in each; the events whose place in `counters` is in off_hop
+        lie one channel up."""
+        if isinstance(counters, int):
+            counters = range(counters)
+        self.k += 1
+        aa, ci = 0x20000000 + 0x1000 * self.k, (0x0A0B0C + 0x010203 * self.k) & 0xFFFFFF
+        self.names[(aa, ci)] = name
+        base = 4000 + 97 * self.k if base is None else base
+        for e, n in enumerate(counters):
+            ch = csa1_at(u0, h, n, chmap)
+            if e in off_hop:
+                ch = (ch + 1) % 37
+            at = base + n * interval * UNIT + (int(self.rng.integers(-jitter, jitter + 1)) if jitter else 0)
+            for j in range(per_event):
+                length = (0, 3)[(e + j) % 2]
+                self.raw.append(ld.Cand(at, aa, ci, ch, 1 if length == 0 else 2, length, ch))
+                at += 80 + 8 * length + gap
+        self.ev += len(counters)
+        self.slot += len(counters) * per_event
+        return self
+
+    def pad(self, unit, rest=0):
+        """A filler connection that ends with the event count at `rest` modulo `unit` (two packets per event)."""
+        n = (rest - self.ev) % unit
+        if n:
+            self.conn("filler", n, h=5 + self.k % 12, u0=self.k % 37, per_event=2)
+        return self
+
+    def lone(self, n):
+        """n candidates with an access address of their own each: no members of anything (min_count 2); in front of all connections."""
+        for k in range(n):
+            ch = int(self.rng.integers(0, 37))
+            self.raw.append(ld.Cand(int(self.rng.integers(0, 1 << 24)), 0x10000000 + 0x31 * k, 0x777 + k, ch, 1, 0, ch))
+        return self
+
+    def grouped(self):
+        raw = [self.raw[i] for i in self.rng.permutation(len(self.raw))]
+        conns, cands = ld.group(raw, 2)
+        return conns, cands, [self.names[(c.access_address, c.crc_init)] for c in conns]
+
+
+def _steps(*runs):
+    """Event counters from runs of (pairs, counter step)."""
+    out = [0]
+    for pairs, step in runs:
+        for _ in range(pairs):
+            out.append(out[-1] + step)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def align_list(variant):
+    """Connections whose first and last events lie on, one before and one behind the boundaries of a wave (64), a workgroup
+    (256), a score tile (1024) and a scan tile (2048) of events -- sizes of one unit less one, the unit and the unit plus one, each
+    group behind a filler that ends on a multiple of the unit; 127, 128 and 129 events, each from a multiple of 64; 3 071 and 1 --, with one and two packets per event in turn and a five-channel map on every third;
+    among them the connections that the tags of tests/_le_track_paths.py name:
+    * "beyond 2^32", first of all: every later connection rides on a step sum of 2^32 + 9;
+    * "several a / b / c": three connections of three to four events in one wave of event pairs, with missed events;
+    * "three waves": 193 events from a multiple of 64, the q of its three waves of pairs 36, 60 and 90: every two have a gcd above 6;
+    * "lane 63" / "thread 255": all q 12 but the one of the pair at lane 63 of wave 0 / at thread 255 of a workgroup, which is 18;
+    * "off hop": 400 events of two packets, those of off_hop_plan() one channel up: in its first and last wave of slots, which it
+      shares with others, five in one wave of its own, one in another, none in the rest.
+    variant "A" ends with the number of events at a multiple of 1024, "B" has one connection of one event more.
+    -> (conns, cands, names)"""
+    assert variant in ("A", "B")
+    b = _Laid(31).lone(5)
+    b.conn("beyond 2^32", BEYOND_32, h=7, u0=29, jitter=0)
+    b.pad(64).conn("several a", (0, 2, 5)).conn("several b", (0, 1, 2, 3)).conn("several c", (0, 3, 5, 6))
+    k = 0
+    for unit in (64, 256, 1024, 2048):
+        b.pad(unit)
+        for n in (unit - 1, 2, unit, unit + 1) + ((-127, -128, -129) if unit == 64 else (3071, 1) if unit == 2048 else ()):
+            if n < 0:                                                      # two waves less one, two waves, two waves and one: each from a
+                n = -n                                                     # multiple of 64, so that they end one before, on and one
+                b.pad(64)                                                  # behind the second wave boundary
+            k += 1
+            b.conn("%d events" % n, n, chmap=FIVE_MAP if k % 3 == 0 else FULL_MAP, interval=6 + k % 5, h=5 + k % 12, u0=(5 * k) % 37,
+                   per_event=2 if n == 1 else 1 + k % 2)
+    b.pad(64).conn("three waves", _steps((64, 6), (64, 10), (64, 15)), h=11, u0=3)
+    b.pad(256).conn("lane 63", _steps((63, 2), (1, 3), (6, 2)), h=9, u0=20)
+    b.pad(256).conn("thread 255", _steps((255, 2), (1, 3), (4, 2)), h=13, u0=1)
+    b.conn("foreign", 3, per_event=2)
+    b.raw += [b.raw[-1]._replace(offset=b.raw[-1].offset + 9 * UNIT, stream=37), b.raw[-1]._replace(offset=b.raw[-1].offset + 12 * UNIT, stream=39)]
+    b.conn("off hop", OFF_HOP_EVENTS, h=10, u0=17, per_event=2, off_hop=off_hop_plan(b.slot))
+    b.pad(LT_SCORE_ALIGN)
+    if variant == "B":
+        b.conn("one more", 1, per_event=2)
+    return b.grouped()
+
+
+CROWD = (1 << 16) + 4
+
+
+@functools.lru_cache(maxsize=None)
+def crowd_list():
+    """More connections than sixteen bits number, 65 544 in all: CROWD = 65 540, the first eight of ten events, the others of one
+    event of two packets, and behind them four that hop, in the same stretch of time as the first eight.  The connection indices from 65 536 on
+    differ from the indices 65 536 below them in the third byte alone, so a sort of the connection index that stops after two radix
+    passes leaves the members of connection 65 540 + i between those of connection 4 + i, in time order.
+    -> (conns, cands, names)"""
+    b = _Laid(51).lone(3)
+    for k in range(CROWD):
+        if k < 8:
+            b.conn("front", 10, h=5 + k, u0=k, base=5000 + 40 * k)
+        else:
+            b.conn("one event", 1, per_event=2, jitter=0)
+    b.conn("behind a", 12, h=6, u0=11, base=5013).conn("behind b", 9, per_event=2, h=16, u0=3, base=5450)
+    b.conn("behind c", (0, 1, 2, 4, 7, 8), chmap=FIVE_MAP, h=12, u0=9, base=5777).conn("behind d", 70, h=9, u0=30, base=6000)
+    return b.grouped()
+
+
+@functools.lru_cache(maxsize=None)
+def long_event_list():
+    """More slots than 256 scan tiles hold, with few events: one connection of 40 events at interval 3200, each a train of 13 300
+    empty packets 230 bits apart (3.06 Mbit of the 4 Mbit to the next event; the default ifs keeps a train in one event), and three
+    small connections behind it, whose slots and events lie beyond tile 256.  -> (conns, cands, names, cand_arr): the candidate
+    list as tuples for the model and, built with numpy, as the fields of the device's records (offset, access_address, crc_init,
+    stream, header0, length, conn)."""
+    b = _Laid(41).lone(3)
+    n_events, train, spacing = 40, 13300, 230
+    aa, ci = 0x20000000, 0x5A5A5A
+    b.names[(aa, ci)] = "trains"
+    anchors = 7000 + np.arange(n_events, dtype=np.int64) * (3200 * UNIT) + b.rng.integers(-20, 21, n_events)
+    chans = np.array([csa1_at(5, 6, n, FULL_MAP) for n in range(n_events)], np.int64)
+    off = (anchors[:, None] + spacing * np.arange(train, dtype=np.int64)[None, :]).reshape(-1)
+    st = np.repeat(chans, train)
+    b.raw += [ld.Cand(o, aa, ci, s, 1, 0, s) for o, s in zip(off.tolist(), st.tolist())]
+    b.conn("behind a", 30, h=8, u0=2).conn("behind b", 5, per_event=2, h=15, u0=30).conn("behind c", (0, 1, 2, 4, 7), chmap=FIVE_MAP, h=12, u0=9)
+    conns, cands = ld.group(b.raw, 2)                                       # (unshuffled: the grouping sorts the list anyway)
+    names = [b.names[(c.access_address, c.crc_init)] for c in conns]
+    fields = np.array(cands, dtype=np.int64)
+    return conns, cands, names, fields

@@ -3,7 +3,15 @@ tests/_le_track.py -- one connection per branch point of the seven rules --, on 
 tile, many waves, more connections than one workgroup's worth), and the chain discover -> track on a capture with four planted
 connections, once through the host wrapper and once device-resident.  Every expectation is the model's (tests/_le_track.py),
 byte for byte.  Output buffers start as 0xA5 and are one record longer than their caps, so a byte a kernel leaves unwritten, or
-writes where it should not, shows."""
+writes where it should not, shows.
+
+The runs of tests/_le_track_paths.py (RUNS) pin the decomposition: lists whose connections begin and end on, one before and one
+behind every boundary of a wave, a workgroup, a score tile and a scan tile, with values in them that a mistake in the wave-wide
+tally, the merge of the waves' gcd, the 64-bit sums or the tile prefix would change.  tests/test_le_track_paths_model.py shows on
+the CPU that each run carries its tags and that the runs carry all of them.  Two paths are left out on purpose: a fourth radix
+pass over the connection index needs conn_cap >= 2^24, about 30 GB of scratch; a second round of the 64-bit tile prefix with
+steps in it needs more than 524 288 EVENTS, too many for the plain model (the second round of the 32-bit prefix runs on the long
+trains, that of the 64-bit prefix with zeros only)."""
 import functools
 
 import numpy as np
@@ -11,6 +19,7 @@ import pytest
 
 import _le_discover as ld
 import _le_track as lt
+import _le_track_paths as lp
 import libbtbb_amd as bt
 
 pytestmark = pytest.mark.gpu
@@ -62,15 +71,17 @@ def _track_device(cand_arr, conn_arr, mhz, n_streams, flags, unit=lt.UNIT, ifs=l
     return (d_tracks.cpu().numpy()[:(conn_cap + 1) * TRACK.itemsize].view(TRACK), d_pkts.cpu().numpy()[:(cand_cap + 1) * PKT.itemsize].view(PKT))
 
 
-def _check(conns, cands, mhz, n_streams, flags, want=None, **kw):
-    """The device against the model (want: the model's (tracks, pkts) when the caller has them already)."""
+def _check(conns, cands, mhz, n_streams, flags, want=None, cand_arr=None, **kw):
+    """The device against the model (want: the model's (tracks, pkts), cand_arr: the candidates' records, when the caller has
+    them already)."""
     n, k = len(cands), len(conns)
     work = min(kw.get("count", n) if kw.get("count") is not None else n, kw.get("cand_cap", n) if kw.get("cand_cap") is not None else n)
     kept = min(kw.get("conn_count", k) if kw.get("conn_count") is not None else k,
                kw.get("conn_cap", k) if kw.get("conn_cap") is not None else k)
     if want is None:
         want = lt.track(cands[:work], kept, mhz, n_streams, kw.get("unit", lt.UNIT), kw.get("ifs", lt.IFS), kw.get("jitter", lt.JITTER), flags)
-    tracks, pkts = _track_device(ld.cand_array(cands, CAND), ld.conn_array(conns, CONN), mhz, n_streams, flags, **kw)
+    tracks, pkts = _track_device(ld.cand_array(cands, CAND) if cand_arr is None else cand_arr, ld.conn_array(conns, CONN), mhz, n_streams,
+                                 flags, **kw)
     if kw.get("conn_cap") == 0 or kw.get("cand_cap") == 0:
         work = kept = 0
     want_t, want_p = lt.track_array(want[0][:kept], TRACK), lt.pkt_array(want[1][:work], PKT)
@@ -173,6 +184,48 @@ def test_beyond_one_sort_tile_and_one_workgroup():
 def test_seam_list_cut_by_the_caps():
     conns, cands = lt.seam_list()
     _check(conns, cands, lt.LATTICE_MHZ, lt.N_STREAMS, lt.REMAP, conn_cap=2000, cand_cap=len(cands) - 4097)
+
+
+# ---- the waves, workgroups and tiles a connection begins and ends on ------------------------------------------------------
+@pytest.mark.parametrize("run", [r for r in lp.RUNS if r.build == "align_list"], ids=lambda r: r.name)
+def test_track_on_the_alignment_lists(run):
+    """Connections of 63 to 3 071 events back to back, each group from a multiple of its unit; counters beyond 2^32 in front of
+    all others; a gcd that needs the merge of three waves, and one that needs the pair at lane 63 / at thread 255; events planted
+    off the hop in waves of one connection and in shared ones.  Once more with three radix passes over the connection index, with
+    a capacity of more than 256 scan tiles, and with a count that ends mid-wave inside the connection with the planted events."""
+    conns, cands, names = lp.run_list(run)
+    assert set(run.tags) <= lp.run_tags(run)
+    want = _check(conns, cands, lt.LATTICE_MHZ, lt.N_STREAMS, run.flags, want=lp.run_model(run), **lp.run_kw(run))
+    off = want[0][names.index("off hop")]
+    print("%s: %d connections, %d candidates, %d events, %d planted off the hop" % (
+        run.name, len(conns), len(cands), sum(t.n_events for t in want[0]), off.n_off_hop))
+    assert off.n_off_hop >= 1
+
+
+def test_more_connections_than_sixteen_bits_number():
+    """65 544 connections: 65 540, most of one event, and four that hop behind them, at indices that differ from those of
+    connections 4 to 7 in the third byte alone, and at the same time as these."""
+    (run,) = [r for r in lp.RUNS if r.build == "crowd_list"]
+    conns, cands, names = lp.run_list(run)
+    assert len(conns) == lt.CROWD + 4 and names[-4:] == ["behind a", "behind b", "behind c", "behind d"] and set(run.tags) <= lp.run_tags(run)
+    want = _check(conns, cands, lt.LATTICE_MHZ, lt.N_STREAMS, run.flags, want=lp.run_model(run))
+    assert [(t.n_events, t.interval) for t in want[0][-4:]] == [(12, 6), (9, 6), (6, 6), (70, 6)]
+
+
+def test_more_slots_than_one_round_of_the_tile_prefix():
+    """Forty events of 13 300 packets each -- 532 000 slots, 260 scan tiles, most of which open no event -- and three small
+    connections whose slots and events lie behind tile 256."""
+    (run,) = [r for r in lp.RUNS if r.build == "long_event_list"]
+    conns, cands, names, fields = lt.long_event_list()
+    assert len(cands) > lp.PREFIX_ROUND * lp.LT_TILE and set(run.tags) <= lp.run_tags(run)
+    arr = np.zeros(len(cands), CAND)
+    for k, name in enumerate(("offset", "access_address", "crc_init", "stream", "header0", "length", "conn")):
+        arr[name] = fields[:, k]
+    assert arr[:50].tobytes() == ld.cand_array(cands[:50], CAND).tobytes() and arr[-50:].tobytes() == ld.cand_array(cands[-50:], CAND).tobytes()
+    for name, field in (("offset", "offset"), ("stream", "stream"), ("length", "length"), ("conn", "channel")):       # every record
+        assert np.array_equal(arr[name].astype(np.int64), np.fromiter((getattr(c, field) for c in cands), np.int64, len(cands))), name
+    want = _check(conns, cands, lt.LATTICE_MHZ, lt.N_STREAMS, run.flags, want=lp.run_model(run), cand_arr=arr)
+    assert [t.n_events for t in want[0]] == [40, 30, 5, 5] and want[0][0].interval == 3200
 
 
 # ---- the chain ----------------------------------------------------------------------------------------------------------

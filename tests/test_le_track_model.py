@@ -42,6 +42,11 @@ def test_lattice_tells_the_model_from_wrong_variants(variant):
         told += ["packets"] if right_pkts != wrong_pkts else []
     print(variant, sorted(set(t for t in told if t)))
     assert told, variant
+    # the two variants that one case each was built for: that case, and no other connection, tells them
+    if variant == "tie_unstable":
+        assert set(told) == set(lt.TIE_CASES) | {"packets"}, told
+    if variant == "hop_from_truncated_counter":
+        assert set(told) == {"counter beyond 2^32", "packets"}, told
 
 
 def test_lattice_holds_what_it_was_built_to_hold():
@@ -69,6 +74,13 @@ def test_lattice_holds_what_it_was_built_to_hold():
     assert by["offsets near 2^46"].first_anchor > (1 << 45) and by["offsets near 2^46"].flags == lt.TIMED | lt.HOPPING
     assert by["foreign streams among the members"].n_events == 7 and by["only foreign streams"] == lt.Track(*([0] * 12))
     assert sum(p is None for p in pkts) >= 40 + 6
+    assert [by[n].n_events for n in lt.TIE_CASES] == [2, 1]                                   # the tie goes by list order
+    t = by["counter beyond 2^32"]
+    assert (t.interval, t.n_events, t.n_fit, t.flags, t.n_off_hop) == (6, 8, 7, lt.TIMED | lt.HOPPING, 0)
+    conns, cands, _ = lt.lattice_list(2)
+    g = names.index("counter beyond 2^32")
+    assert max(c.offset for c in cands if c.channel == g) < 1 << 45
+    assert sorted((p.event, p.counter) for c, p in zip(cands, pkts) if c.channel == g)[4:] == [(4, 5), (5, 6), (6, 7), (7, 9)]
     _, plain, _ = lt.lattice_tracks(0)
     assert dict(zip(names, plain))["map of 3"].n_on_hop < by["map of 3"].n_on_hop            # without REMAP most predictions are unknown
 
@@ -143,6 +155,18 @@ def test_chain_capture_holds_the_planted_connections():
     for c, t in aliases:
         assert c.access_address == (planted[1].aa >> 2) | (1 << 31) and c.channel_mask == 1 << 3 and c.n_packets >= 2
         assert not t.flags & lt.HOPPING, t
+
+
+def test_packet_records_as_bytes():
+    """pkt_array builds the records field by field with numpy: the same bytes as one record after the other, 0xFF for no member."""
+    import libbtbb_amd as bt
+    dtype = bt.LE_TRACK_PKT_DTYPE
+    _, _, pkts = lt.lattice_tracks(lt.REMAP)
+    pkts = [None] + pkts + [lt.Pkt(0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFF, 36, 0xFF, 0xFF, 0), None]
+    assert sum(p is None for p in pkts) >= 3 and any(p is not None and p.counter > 1 << 31 for p in pkts)
+    want = b"".join(b"\xff" * dtype.itemsize if p is None else np.array([tuple(p)], dtype).tobytes() for p in pkts)
+    assert lt.pkt_array(pkts, dtype).tobytes() == want and lt.pkt_array([], dtype).tobytes() == b""
+    assert lt.pkt_array([None], dtype).tobytes() == b"\xff" * 16
 
 
 def test_layouts_and_loud_failure_without_a_device():
