@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import _libs
+import _seams
 import libbtbb_amd as bt
 from libbtbb_amd import synth
 
@@ -801,9 +802,8 @@ def test_hits_at_the_seams_of_lanes_segments_waves_and_tiles(lap):
     lib = bt.lib()
     olap = _libs.LAP_ANY if lap == bt.LAP_ANY else lap
     rng = np.random.default_rng(77)
-    deltas = (-65, -64, -63, -33, -32, -31, -1, 0, 1, 31, 32, 33, 63, 64)
-    bounds = (1, 2, 63, 64, 126, 128, 189, 256, 512, 756, 1024, 1512)                 # in words
-    n_streams, nwords, pitch = len(deltas), 2 * 512 + 2 * 756 + 37, 2 * 512 + 2 * 756 + 64
+    deltas, bounds = _seams.DELTAS, _seams.BOUNDS                                      # bounds in words
+    n_streams, nwords, pitch = len(deltas), _seams.N_WORDS, _seams.N_WORDS + 27
     nbits = nwords * 64 - 63 - 5
     rows, want, planted = [], [], 0
     for ch in range(n_streams):
