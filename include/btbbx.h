@@ -592,6 +592,77 @@ int64_t btbbx_le_track_host(const uint64_t *words, uint64_t n_words, uint64_t pi
 			    uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
 			    btbbx_le_track *tracks, btbbx_le_track_pkt *pkts);
 
+/* ---- LE channel selection algorithm #2: event counter recovery and hop check ----------------- */
+/* Two Bluetooth 5 devices hop by channel selection algorithm #2 (Core Vol 6 Part B 4.5.8.3), which the tracking above reports as
+ * TIMED but not HOPPING.  #2 has no increment to fit: the channel of an event is a function of the absolute 16-bit
+ * connEventCounter, the channel identifier chId = (AA >> 16) ^ (AA & 0xffff) and the channel map.  The tracking gives every
+ * event a counter relative to the first event seen, so one unknown is left, the absolute counter of that first event; this stage
+ * tries all 65 536 and reports the one that explains most events, the prediction for every packet, and which of the two
+ * algorithms explains the connection.  It runs behind the tracking, on what the tracking wrote.  All arithmetic is integer
+ * arithmetic.  With N = min(*d_cand_count, cand_cap), K = min(*d_conn_count, conn_cap), and cands, tracks and pkts exactly what
+ * btbbx_le_discover_group_device and btbbx_le_track_device left:
+ *   1. MEMBERS.  Candidate i < N is a member of g < K iff cands[i].conn == g and pkts[i].rank != 0xffffffff; every other
+ *      candidate gets eight 0xff bytes as its record.  A member's event is pkts[i].event, its channel C_e = pkts[i].channel, its
+ *      relative counter n_e = pkts[i].counter mod 2^16 (the stored low 32 bits suffice: 2^16 divides 2^32); all members of an
+ *      event carry the same values.  The map is tracks[g].map_mask, n_used its popcount (tracks[g].n_used), used[] its channels
+ *      in ascending order.
+ *   2. EVALUATED iff the track is TIMED.  Otherwise the record is channel_id with every other field 0, and the members get
+ *      counter 0, prn 0, unmapped = expected = 0xff, on_hop 0.
+ *   3. PRN.  prn_e(c): x = c ^ chId; three times: reverse the bits within each of the two bytes of x, then
+ *      x = (17 * x + chId) mod 2^16; prn_e = x ^ chId.
+ *   4. PREDICTION.  unmapped(c) = prn_e(c) mod 37; expected(c) = unmapped(c) if the map holds it, else with BTBBX_LE_CSA2_REMAP
+ *      used[(n_used * prn_e(c)) >> 16], else 0xff (unknown).
+ *   5. SCORE.  For c0 in 0..65535, S(c0) = the number of EVENTS with expected((c0 + n_e) mod 2^16) == C_e.  The largest S wins,
+ *      ties to the smallest c0: counter0 = the winner, n_on = S(winner), n_second = the largest S of any other c0, n_off = the
+ *      events whose prediction under the winner is known and differs.
+ *   6. PACKETS.  A member packet of an EVALUATED connection gets counter = (counter0 + n_e) mod 2^16, that counter's prn,
+ *      unmapped and expected, and on_hop = (expected == channel).
+ * LIMITS, which follow from the rules: the observed map stands in for the connection's, so a used channel that never shows makes
+ * the remapping wrong; with few events, or a map of one or two channels, many hypotheses tie (full map, REMAP, 200 random draws:
+ * the winner was unique and right in 22 of them at 6 events, 197 at 8, 200 at 12); a channel map update inside the capture is not
+ * followed; the tracking's limits on the relative counters carry over. */
+#define BTBBX_LE_CSA2_REMAP     1u  /* flags argument: as BTBBX_LE_TRACK_REMAP */
+#define BTBBX_LE_CSA2_EVALUATED 1u  /* btbbx_le_csa2.flags: the connection's track is TIMED */
+#define BTBBX_LE_CSA2_UNIQUE    2u  /* EVALUATED and n_on > n_second */
+#define BTBBX_LE_CSA2_PREFERRED 4u  /* UNIQUE and n_on > the track's n_on_hop: algorithm #2 explains more events than #1 */
+
+typedef struct btbbx_le_csa2 {       /* 24 bytes, one per stored connection, parallel to conns / tracks */
+	uint32_t n_on, n_off;        /* events on / off the predicted channel (unknown predictions in neither) */
+	uint32_t n_second;           /* the best score of any other counter hypothesis */
+	uint16_t channel_id;         /* (AA >> 16) ^ (AA & 0xffff) */
+	uint16_t counter0;           /* connEventCounter of the first event seen */
+	uint32_t flags;
+	uint32_t reserved;           /* written as 0 */
+} btbbx_le_csa2;
+
+typedef struct btbbx_le_csa2_pkt {   /* 8 bytes, one per candidate, parallel to the sorted candidate list */
+	uint16_t counter;            /* connEventCounter of its event */
+	uint16_t prn;                /* prn_e of that counter */
+	uint8_t  unmapped, expected, on_hop, reserved;  /* reserved written as 0 */
+} btbbx_le_csa2_pkt;                 /* a candidate that is no member of a stored connection: eight 0xff bytes */
+
+/* d_sel[0 .. K) and d_sel_pkts[0 .. N) are written, every byte of them, nothing behind them; nothing is read back and the call is
+ * asynchronous on hip_stream.  Only bit 0 of flags is read.  d_scratch: btbbx_le_csa2_scratch_bytes(cand_cap, conn_cap) bytes =
+ * 256 + 4 * (conn_cap + 1) + 4 * cand_cap + 1024 * conn_cap, each term rounded up to a multiple of 256 (a cap of 0 counts as 1):
+ * the counts, the event bases, the event table and 64 partial results per connection.  BTBBX_E_ARG, before any launch: a null
+ * pointer, a record or scratch pointer that is not 8-byte aligned (the counters: 4), a scratch that is too small.  cand_cap == 0
+ * or conn_cap == 0 succeeds and writes nothing. */
+size_t btbbx_le_csa2_scratch_bytes(uint32_t cand_cap, uint32_t conn_cap);
+int btbbx_le_csa2_device(const btbbx_le_cand *d_cands, const uint32_t *d_cand_count, uint32_t cand_cap,
+			 const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
+			 const btbbx_le_track *d_tracks, const btbbx_le_track_pkt *d_pkts, uint32_t flags,
+			 btbbx_le_csa2 *d_sel, btbbx_le_csa2_pkt *d_sel_pkts,
+			 void *d_scratch, size_t scratch_bytes, void *hip_stream);
+
+/* Host wrapper: btbbx_le_track_host's chain with this stage queued behind the tracking on the same stream, copy out.  Its
+ * arguments (flags & 1 serves both stages) and return value; sel: conn_cap records, parallel to conns; sel_pkts (may be NULL):
+ * cand_cap records, parallel to cands.  Safe to call from several host threads at once. */
+int64_t btbbx_le_csa2_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			   uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+			   btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+			   uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+			   btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_csa2 *sel, btbbx_le_csa2_pkt *sel_pkts);
+
 /* ---- hop selection and CLK1-27 reversal ------------------------- */
 #define BTBBX_SEQUENCE_LENGTH 134217728u   /* values of CLK1-27, bluetooth_piconet.h:102 */
 

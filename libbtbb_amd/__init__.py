@@ -104,6 +104,13 @@ LE_TRACK_DTYPE = np.dtype([("first_anchor", "<u8"), ("map_mask", "<u8"), ("n_eve
 LE_TRACK_PKT_DTYPE = np.dtype([("rank", "<u4"), ("event", "<u4"), ("counter", "<u4"), ("channel", "u1"), ("unmapped", "u1"),
                                ("expected", "u1"), ("on_hop", "u1")])
 assert LE_TRACK_DTYPE.itemsize == 48 and LE_TRACK_PKT_DTYPE.itemsize == 16
+# LE channel selection #2 (include/btbbx.h btbbx_le_csa2 / btbbx_le_csa2_pkt; le_csa2.h checks the C layout with static_asserts)
+LE_CSA2_REMAP, LE_CSA2_EVALUATED, LE_CSA2_UNIQUE, LE_CSA2_PREFERRED = 1, 1, 2, 4
+LE_CSA2_DTYPE = np.dtype([("n_on", "<u4"), ("n_off", "<u4"), ("n_second", "<u4"), ("channel_id", "<u2"), ("counter0", "<u2"),
+                          ("flags", "<u4"), ("reserved", "<u4")])
+LE_CSA2_PKT_DTYPE = np.dtype([("counter", "<u2"), ("prn", "<u2"), ("unmapped", "u1"), ("expected", "u1"), ("on_hop", "u1"),
+                              ("reserved", "u1")])
+assert LE_CSA2_DTYPE.itemsize == 24 and LE_CSA2_PKT_DTYPE.itemsize == 8
 
 # one surveyed piconet (include/btbbx.h btbbx_survey_rec; survey.hip checks the C layout with static_asserts)
 SURVEY_DTYPE = np.dtype([("lap", "<u4"), ("flags", "<u4"), ("uap", "u1"), ("clk_offset", "u1"), ("used_channels", "u1"),
@@ -196,6 +203,10 @@ SIGNATURES = {
     "btbbx_le_track_device": (C.c_int, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, C.c_size_t, _vp]),
     "btbbx_le_track_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
                                         _vp, _vp]),
+    "btbbx_le_csa2_scratch_bytes": (C.c_size_t, [_u32, _u32]),
+    "btbbx_le_csa2_device": (C.c_int, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "btbbx_le_csa2_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
+                                       _vp, _vp, _vp, _vp]),
     "btbbx_survey_scratch_bytes": (C.c_size_t, [_u32]),
     "btbbx_survey_hits_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp,
                                            _vp, C.c_size_t, _vp]),
@@ -451,6 +462,35 @@ def le_track(words, search_bits, phys_channels, max_len=27, min_count=2, n_strea
         raise BtbbError("buffers too small: %d connections > %d or %d candidates > %d" % (n, conn_cap, n_cands.value, cand_cap))
     nc, nk = min(n, conn_cap), min(n_cands.value, cand_cap)
     return conns[:nc].copy(), cands[:nk].copy(), tracks[:nc].copy(), pkts[:nk].copy()
+
+
+def le_csa2(words, search_bits, phys_channels, max_len=27, min_count=2, n_streams=1, pitch_words=None, n_words=None,
+            unit_bits=1250, ifs_bits=200, jitter_bits=50, flags=LE_CSA2_REMAP, conn_cap=1 << 12, cand_cap=1 << 20, truncate=False):
+    """le_track, then channel selection algorithm #2 for every connection it timed (include/btbbx.h btbbx_le_csa2_device): the
+    absolute connEventCounter of the first event seen, the channel predicted for every packet, and whether #2 explains the
+    connection better than #1.  le_track's parameters; bit 0 of flags serves both stages.  Returns (conns, cands, tracks, pkts, sel,
+    sel_pkts): le_track's four arrays, LE_CSA2_DTYPE records parallel to conns and LE_CSA2_PKT_DTYPE records parallel to cands."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if pitch_words is None:
+        pitch_words = len(words) // n_streams
+    if n_words is None:
+        n_words = pitch_words
+    assert n_words <= pitch_words and (n_streams - 1) * pitch_words + n_words <= len(words)
+    phys = np.ascontiguousarray(np.broadcast_to(np.asarray(phys_channels, dtype=np.uint16), (n_streams,)))
+    conns = np.empty(max(conn_cap, 1), dtype=LE_CONN_DTYPE)
+    tracks = np.empty(max(conn_cap, 1), dtype=LE_TRACK_DTYPE)
+    sel = np.empty(max(conn_cap, 1), dtype=LE_CSA2_DTYPE)
+    cands = np.empty(max(cand_cap, 1), dtype=LE_CAND_DTYPE)
+    pkts = np.empty(max(cand_cap, 1), dtype=LE_TRACK_PKT_DTYPE)
+    sel_pkts = np.empty(max(cand_cap, 1), dtype=LE_CSA2_PKT_DTYPE)
+    n_cands = C.c_uint64(0)
+    n = check(lib().btbbx_le_csa2_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, _ptr(phys), max_len, min_count,
+                                       _ptr(conns), conn_cap, _ptr(cands), cand_cap, C.byref(n_cands), unit_bits, ifs_bits, jitter_bits,
+                                       flags, _ptr(tracks), _ptr(pkts), _ptr(sel), _ptr(sel_pkts)), "btbbx_le_csa2_host")
+    if (n > conn_cap or n_cands.value > cand_cap) and not truncate:
+        raise BtbbError("buffers too small: %d connections > %d or %d candidates > %d" % (n, conn_cap, n_cands.value, cand_cap))
+    nc, nk = min(n, conn_cap), min(n_cands.value, cand_cap)
+    return conns[:nc].copy(), cands[:nk].copy(), tracks[:nc].copy(), pkts[:nk].copy(), sel[:nc].copy(), sel_pkts[:nk].copy()
 
 
 class DeviceBuffer:
