@@ -9,6 +9,7 @@ rules of the contract, not from the kernels (le_csa2.h splits the hypotheses int
 * csa2: the FORWARD channel selection algorithm #2 (Core v5.x Vol 6 Part B 4.5.8.3), written from the specification; it shares
   nothing with the model
 * lattice / lattice_list / seam_list / crowd_list / chain_capture: the lists and the capture the CPU and GPU tests share
+* pair_list / wide_list: the lists that put winner and runner-up where the kernels split the work (tests/_le_csa2_paths.py)
 """
 import collections
 import functools
@@ -474,3 +475,202 @@ def chain_model():
     """(conns, cands) of the discovery's model on the chain capture, min_count 2."""
     cap, _ = chain_capture()
     return ld.group(ld.capture_candidates(cap, 27), 2)
+
+
+# ---- lists that pin how the kernels split the work (tests/_le_csa2_paths.py holds the conditions) ------------------------------
+# Hypothesis c0 is block c0 / 1024, thread (c0 mod 1024) / 4, register c0 mod 4 of le_csa2_score_kernel; the numbers below are
+# written out, tests/test_le_csa2_paths_model.py holds them against the constants of the header.
+def at(block, thread, r=0):
+    return 1024 * block + 4 * thread + r
+
+
+PAIR_AA = 0x5A17C3E9
+PAIR_EVENTS = 32
+# name -> (A, B, tie): PAIR_EVENTS events at the counters from 0 on (pair_counters), 18 of them on csa2(PAIR_AA, A + e) and 14 on csa2(PAIR_AA, B + e)
+# -- A wins, B is the runner-up, wherever the two lie --, or 16 and 16 for an exact tie, which the smaller of the two wins
+PAIRS = collections.OrderedDict([
+    ("same lane, runner-up at the smaller r", (at(9, 77, 3), at(9, 77, 0), False)),
+    ("same lane, runner-up at the larger r", (at(40, 200, 1), at(40, 200, 2), False)),
+    ("same lane, high block, r 0 and 3", (at(61, 3, 0), at(61, 3, 3), False)),
+    ("same wave, lanes 0 and 63, runner-up above", (at(12, 64, 2), at(12, 127, 1), False)),
+    ("same wave, lanes 63 and 0, runner-up below", (at(45, 255, 0), at(45, 192, 3), False)),
+    ("same wave, lanes 31 and 32", (at(33, 128 + 31, 1), at(33, 128 + 32, 1), False)),
+    ("same wave, lanes 32 and 31", (at(20, 64 + 32, 0), at(20, 64 + 31, 2), False)),
+    ("same wave 0, lanes 5 and 6", (at(3, 5, 3), at(3, 6, 0), False)),
+    ("threads 63 and 64", (at(7, 63, 3), at(7, 64, 0), False)),
+    ("threads 64 and 63", (at(50, 64, 0), at(50, 63, 3), False)),
+    ("threads 127 and 128", (at(26, 127, 2), at(26, 128, 2), False)),
+    ("threads 192 and 191", (at(58, 192, 1), at(58, 191, 0), False)),
+    ("waves 0 and 3", (at(5, 10, 1), at(5, 250, 2), False)),
+    ("waves 3 and 0", (at(37, 230, 0), at(37, 0, 0), False)),
+    ("waves 1 and 2", (at(44, 100, 2), at(44, 150, 3), False)),
+    ("waves 2 and 1", (at(18, 140, 3), at(18, 70, 1), False)),
+    ("waves 3 and 3 beside wave 0", (at(62, 201, 1), at(62, 254, 3), False)),
+    ("blocks 0 and 63", (at(0, 17, 1), at(63, 200, 2), False)),
+    ("blocks 63 and 0", (at(63, 255, 3), at(0, 0, 0), False)),
+    ("blocks 31 and 32, j 1023 beside j 0", (at(31, 255, 3), at(32, 0, 0), False)),
+    ("blocks 32 and 31, j 0 beside j 1023", (at(32, 0, 0), at(31, 255, 3), False)),
+    ("blocks 10 and 11, j 1023 beside j 0", (at(10, 255, 3), at(11, 0, 0), False)),
+    ("blocks 0 and 1, lanes alike", (at(0, 31, 2), at(1, 31, 2), False)),
+    ("blocks 47 and 15", (at(47, 129, 0), at(15, 66, 1), False)),
+    ("tie in one lane", (at(22, 91, 0), at(22, 91, 3), True)),
+    ("tie in one lane, r 1 and 2, high block", (at(55, 160, 1), at(55, 160, 2), True)),
+    ("tie in one wave, lanes 0 and 63", (at(1, 192, 1), at(1, 255, 1), True)),
+    ("tie in wave 1, lanes 31 and 32", (at(39, 95, 3), at(39, 96, 0), True)),
+    ("tie at threads 63 and 64", (at(14, 63, 3), at(14, 64, 0), True)),
+    ("tie at threads 63 and 64, high block", (at(48, 63, 0), at(48, 64, 3), True)),
+    ("tie in waves 0 and 3", (at(29, 1, 0), at(29, 255, 3), True)),
+    ("tie in waves 1 and 2", (at(60, 65, 2), at(60, 190, 1), True)),
+    ("tie in waves 0 and 1, high block", (at(35, 40, 1), at(35, 80, 1), True)),
+    ("tie in blocks 0 and 63", (at(0, 0, 0), at(63, 255, 3), True)),
+    ("tie in blocks 16 and 17, j 1023 beside j 0", (at(16, 255, 3), at(17, 0, 0), True)),
+    ("tie in blocks 62 and 63, j 1023 beside j 0", (at(62, 255, 3), at(63, 0, 0), True)),
+    ("tie in blocks 8 and 40", (at(8, 120, 2), at(40, 120, 2), True)),
+])
+
+
+def pair_counters(a, b):
+    """The counters of a pair's events: the first PAIR_EVENTS from 0 on at which the predictions of A and B differ (where they
+    agree -- one counter in 37 -- an event would lie on both, and no draw could give the planted scores)."""
+    counters = [n for n in range(3 * PAIR_EVENTS) if csa2(PAIR_AA, a + n, FULL_MAP) != csa2(PAIR_AA, b + n, FULL_MAP)][:PAIR_EVENTS]
+    assert counters[0] == 0, "choose another placement: the tracking counts from the first event it sees"
+    return counters
+
+
+def pair_events(a, b, tie, seed):
+    """(counter, channel) of each of the PAIR_EVENTS events of a pair: a seeded subset of 18 (16 for a tie) on A's prediction, the
+    rest on B's."""
+    n_a = PAIR_EVENTS // 2 if tie else PAIR_EVENTS // 2 + 2
+    on_a = set(np.random.default_rng(seed).choice(PAIR_EVENTS, n_a, replace=False).tolist())
+    return [(n, csa2(PAIR_AA, (a if e in on_a else b) + n, FULL_MAP)) for e, n in enumerate(pair_counters(a, b))]
+
+
+def pair_is_clean(a, b, tie, events):
+    """Whether, with and without REMAP on the map the events show, A and B score exactly what was planted -- no event of the one
+    lies on the other's prediction through the remapping -- and every third hypothesis scores at least 2 below B."""
+    n_a = PAIR_EVENTS // 2 if tie else PAIR_EVENTS // 2 + 2
+    for flags in (0, REMAP):
+        scores, _ = scores_np(PAIR_AA, [(n, ch, 1) for n, ch in events], mask_of(ch for _, ch in events), flags)
+        if (scores[a], scores[b]) != (n_a, PAIR_EVENTS - n_a):
+            return False
+        scores[[a, b]] = 0
+        if scores.max() > PAIR_EVENTS - n_a - 2:
+            return False
+    return True
+
+
+@functools.lru_cache(maxsize=None)
+def pair_plan():
+    """name -> (A, B, tie, seed, events): for every pair the first seed (from a base of its own) whose draw is clean."""
+    plan = collections.OrderedDict()
+    for k, (name, (a, b, tie)) in enumerate(PAIRS.items()):
+        for seed in range(1000 * k, 1000 * k + 200):
+            events = pair_events(a, b, tie, seed)
+            if pair_is_clean(a, b, tie, events):
+                plan[name] = (a, b, tie, seed, tuple(events))
+                break
+        else:
+            raise AssertionError("no clean draw for the pair %r" % name)
+    return plan
+
+
+@functools.lru_cache(maxsize=None)
+def pair_list():
+    """The pairs as one candidate list: one access address -- one chId --, consecutive CRCInits, 20 non-members between them:
+    (conns, cands, names)."""
+    raw, by_key = [], {}
+    for k, (name, (a, b, tie, seed, events)) in enumerate(pair_plan().items()):
+        raw += plant(PAIR_AA, 0x700000 + k, 0, [n for n, _ in events], FULL_MAP, interval=6 + k % 5, base=3000 + 977 * k,
+                     channel_of=dict(events).get)
+        by_key[(PAIR_AA, 0x700000 + k)] = name
+    return _grouped(raw, by_key, np.random.default_rng(61), 20)
+
+
+TWENTY_MAP = mask_of((0, 1, 3, 4, 6, 9, 10, 12, 15, 16, 19, 21, 22, 25, 27, 28, 30, 33, 34, 36))
+Wide = collections.namedtuple("Wide", "name counter0 counters chmap moved b on_b")
+
+
+def _wide(name, counter0, counters, chmap=FULL_MAP, moved=(), b=None, on_b=()):
+    return Wide(name, counter0, tuple(counters), chmap, frozenset(moved), b, frozenset(on_b))
+
+
+def _split(n, n_b, seed, keep=()):
+    """n_b of the events 0 .. n - 1, seeded, none of `keep` among them."""
+    free = [e for e in range(n) if e not in set(keep)]
+    return np.random.default_rng(seed).choice(free, n_b, replace=False).tolist()
+
+
+# The connections with gaps and many events.  Every one keeps adjacent counters, or the tracking's gcd would take a stride for the
+# interval.  moved: events whose packets lie one used channel up, off every prediction; b / on_b: a second planted hypothesis and
+# the events that lie on ITS prediction.  What each is for: tests/_le_csa2_paths.py's tags and WIDE_RUNS.
+WINDOWS = (
+    # the last byte of the window, 1023 + span, and the first: winners at j = 1023 and j = 0 of adjacent blocks; two tiles each
+    _wide("tail, span 1711", at(20, 255, 3), list(range(300)) + [1500 + i for i in range(301)]),
+    _wide("tail, span cut", at(52, 255, 3), list(range(511)) + [3072] + [3073 + i for i in range(102)]),
+    _wide("head, span 1711", at(21, 0, 0), list(range(300)) + [1500 + i for i in range(301)]),
+    _wide("head, span cut", at(53, 0, 0), list(range(511)) + [3072] + [3073 + i for i in range(102)]),
+    # a tile that spans more than 2^16 counters; winners in block 63, where every window wraps
+    _wide("tile spans 2^16", 65535, [0, 1] + [130 * i for i in range(2, 600)]),
+    # (... and ten events behind a gap of 4 800 in the same tile: the second loop runs over a tile whose near events wrap)
+    _wide("n_e wraps in tile two", 64512, list(range(512)) + [65400 + i for i in range(200)] + [70400 + i for i in range(10)]),
+    # d_last around the cut
+    _wide("d_last cut - 1", at(6, 63, 2), list(range(30)) + [3071]),
+    _wide("d_last cut", at(6, 64, 1), list(range(30)) + [3072]),
+    _wide("d_last cut + 1", at(41, 128, 3), list(range(30)) + [3072, 3073]),
+    # far events alone lift A above B: 12 adjacent events, 4 on A and 8 on B, and 12 behind a gap of 5 000, all on A
+    _wide("far decides, thread 0", at(13, 0, 1), list(range(12)) + [5000 + i for i in range(12)], b=at(30, 9, 0), on_b=_split(12, 8, 1)),
+    _wide("far decides, thread 63", at(34, 63, 2), list(range(12)) + [5000 + i for i in range(12)], b=at(2, 99, 1), on_b=_split(12, 8, 2)),
+    _wide("far decides, thread 64", at(57, 64, 0), list(range(12)) + [5000 + i for i in range(12)], b=at(57, 11, 3), on_b=_split(12, 8, 3)),
+    _wide("far decides, thread 255", at(63, 255, 2), list(range(12)) + [5000 + i for i in range(12)], b=at(19, 255, 2), on_b=_split(12, 8, 4)),
+)
+COUNTS = (
+    _wide("511 events", at(25, 100, 0), range(511)),
+    _wide("512 events", at(38, 17, 3), range(512)),
+    _wide("513 events", at(4, 63, 1), range(513)),
+    _wide("1024 events", at(59, 64, 2), range(1024)),
+    # (d_last on the cut in tile one, a third tile of one event)
+    _wide("1025 events", 1023, list(range(511)) + [3072] + [3073 + i for i in range(513)], moved=(63, 64, 100, 511, 512, 513)),
+    # a map of 20 channels: without REMAP 17 of 37 predictions are unknown, those of the moved events (the last among them) are not
+    _wide("map of 20, last event off", at(46, 45, 1), range(603), chmap=TWENTY_MAP, moved=(70, 400, 602)),
+    # B's events lie in the second tile alone
+    _wide("second only in tile two", at(27, 180, 2), range(602), b=at(27, 20, 1), on_b=[512 + e for e in _split(90, 60, 5)]),
+)
+WIDE_AA = 0x8E5A3C00
+
+
+def _wide_cands(k, w):
+    used = [c for c in range(37) if (w.chmap >> c) & 1]
+    event_of = {n: e for e, n in enumerate(w.counters)}
+
+    def channel_of(n):
+        e = event_of[n]
+        ch = csa2(WIDE_AA + 0x10001 * k, (w.b if e in w.on_b else w.counter0) + n, w.chmap)
+        return used[(used.index(ch) + 1) % len(used)] if e in w.moved else ch
+
+    return plant(WIDE_AA + 0x10001 * k, 0x5EED00 + k, w.counter0, w.counters, w.chmap, base=3500 + 411 * k, channel_of=channel_of)
+
+
+@functools.lru_cache(maxsize=None)
+def wide_list(group):
+    """WINDOWS or COUNTS ("windows", "counts") as one candidate list with 10 non-members: (conns, cands, names)."""
+    raw, by_key = [], {}
+    for k, w in enumerate(dict(windows=WINDOWS, counts=COUNTS)[group]):
+        k += 32 * (group == "counts")
+        raw += _wide_cands(k, w)
+        by_key[(WIDE_AA + 0x10001 * k, 0x5EED00 + k)] = w.name
+    return _grouped(raw, by_key, np.random.default_rng(71), 10)
+
+
+@functools.lru_cache(maxsize=None)
+def list_model(build, arg, flags):
+    """(tracks, pkts, (sels, sel_pkts)) of the models on pair_list() or wide_list(arg), whole."""
+    conns, cands, _ = globals()[build]() if arg is None else globals()[build](arg)
+    tracks, pkts = tracked(conns, cands, flags)
+    return tracks, pkts, select(conns, cands, tracks, pkts, flags)
+
+
+def without_last_connection(conns, cands, want):
+    """The model's (sels, sel_pkts) when the last connection is cut off: the others are unchanged (no rule looks across
+    connections), its candidates are no members."""
+    k = len(conns) - 1
+    return want[0][:k], [None if c.channel >= k else p for c, p in zip(cands, want[1])]

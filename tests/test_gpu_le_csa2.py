@@ -1,6 +1,7 @@
 """The LE channel selection #2 stage (libbtbb_amd/csrc/le_csa2.h) on the GPU: hand-built candidate lists run through
 btbbx_le_track_device and then btbbx_le_csa2_device, as tests/test_gpu_le_track.py runs the tracking -- the lattice of
-tests/_le_csa2.py, lists that cross the kernels' seams (several LDS tiles of events per work item, more connections than sixteen
+tests/_le_csa2.py, the runs of tests/_le_csa2_paths.py that put winners and runners-up where the kernels split the work, lists that
+cross the kernels' seams (several LDS tiles of events per work item, more connections than sixteen
 bits number), and the chain discover -> track -> select on a capture, once through the host wrapper and once device-resident.
 Every expectation is the model's (tests/_le_csa2.py on top of tests/_le_track.py's model of the tracking), byte for byte.  Output
 buffers start as 0xA5 and are one record longer than their caps, so a byte a kernel leaves unwritten, or writes where it should
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 
 import _le_csa2 as lc
+import _le_csa2_paths as lp
 import _le_discover as ld
 import _le_track as lt
 import libbtbb_amd as bt
@@ -154,6 +156,56 @@ def test_bad_arguments_are_refused_before_any_launch():
     got = buf.cpu().numpy()
     assert got[10240:10240 + 64].tobytes() == b"\xff" * 64 and got[10240 + 64:12288].tobytes() == b"\xa5" * (2048 - 64)
     assert got[8192 + 96:10240].tobytes() == b"\xa5" * (2048 - 96) and got[:8192].tobytes() == b"\xa5" * 8192
+
+
+# ---- where the kernels split the work: the runs of tests/_le_csa2_paths.py -----------------------------------------------------
+def _run(name):
+    """One run of lp.RUNS on the device against the models; a cut run with conn_cap one below the connections, which drops the last
+    one: other event bases, another grid.  Returns (names, sels)."""
+    run = [r for r in lp.RUNS if r.name == name][0]
+    conns, cands, names = lp.run_list(run)
+    want = lp.run_model(run)[2]
+    if run.cut:
+        _check(conns, cands, run.flags, want=lc.without_last_connection(conns, cands, want), conn_cap=len(conns) - 1)
+    else:
+        _check(conns, cands, run.flags, want=want)
+    return names, want[0]
+
+
+@pytest.mark.parametrize("flags", [0, lc.REMAP])
+def test_pairs_of_planted_hypotheses(flags):
+    """37 connections of 32 events on one chId, 18 on hypothesis A and 14 on B, or 16 and 16: winner and runner-up in one lane, in
+    one wave, at threads 63 | 64, in two waves, in two blocks (0 and 63, adjacent ones at j = 1023 | 0), each UNIQUE in both orders
+    and as an exact tie."""
+    names, sels = _run("pairs, REMAP" if flags else "pairs")
+    by = dict(zip(names, sels))
+    for name, (a, b, tie) in lc.PAIRS.items():
+        assert (by[name].counter0, by[name].n_on, by[name].n_second, by[name].flags & 3) == ((min(a, b), 16, 16, 1) if tie else (a, 18, 14, 3)), (name, by[name])
+
+
+def test_winners_at_the_ends_of_wide_windows():
+    """Gaps that widen the window to 1 024 + 1 711 and to the cut, winners at j = 1023 and j = 0; d_last at the cut - 1, the cut,
+    the cut + 1; far events that decide; a tile over more than 2^16 counters; n_e wrapping inside the second tile; block 63."""
+    names, sels = _run("windows, REMAP")
+    by = dict(zip(names, sels))
+    assert [(by[w.name].counter0, by[w.name].flags) for w in lc.WINDOWS] == [(w.counter0, 7) for w in lc.WINDOWS]
+    assert (by["tile spans 2^16"].n_on, by["n_e wraps in tile two"].n_on, by["d_last cut + 1"].n_on) == (600, 722, 32)
+
+
+@pytest.mark.parametrize("flags", [0, lc.REMAP])
+def test_tile_counts_and_events_off_the_prediction_behind_event_63(flags):
+    """511, 512, 513, 1 024 and 1 025 events; events off the prediction at 63, 64, 511, 512, 513 and at the end; a map of 20
+    channels, whose unknown predictions count on neither side without REMAP; a runner-up that the second tile alone makes."""
+    names, sels = _run("counts, REMAP" if flags else "counts")
+    by = dict(zip(names, sels))
+    assert (by["1025 events"].n_on, by["1025 events"].n_off, by["1025 events"].counter0) == (1019, 6, 1023)
+    assert by["map of 20, last event off"].n_off == 3 and (by["map of 20, last event off"].n_on == 600) == bool(flags)
+    assert (by["second only in tile two"].n_on, by["second only in tile two"].n_second >= 60) == (543, True)
+
+
+@pytest.mark.parametrize("group", ["windows", "counts"])
+def test_wide_connections_with_the_last_one_cut_off(group):
+    _run("%s, REMAP, cut" % group)
 
 
 # ---- sizes that cross the kernels' seams ------------------------------------------------------------------------------
