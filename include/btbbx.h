@@ -542,7 +542,8 @@ int64_t btbbx_le_discover_host(const uint64_t *words, uint64_t n_words, uint64_t
  * and expected 0xff; everything else is written all the same.  A connection without a member: a record of zeros.
  * LIMITS, which follow from the rules: the counter is relative to the first event SEEN; an interval whose visible event spacings
  * are all multiples of k comes out k times too large (two events two intervals apart: doubled); a used channel that never shows
- * makes the remapping wrong; a parameter or channel map update inside the capture is not followed. */
+ * makes the remapping wrong; a parameter or channel map update inside the capture is not followed by this stage (with the
+ * CONNECT_IND in the capture, btbbx_le_seed_device and btbbx_le_epoch_device lift all three). */
 #define BTBBX_LE_TRACK_REMAP   1u   /* flags: score and predict through the remapping of the observed channel map */
 #define BTBBX_LE_TRACK_TIMED   1u   /* btbbx_le_track.flags: 6 <= interval <= 3200 */
 #define BTBBX_LE_TRACK_HOPPING 2u   /* btbbx_le_track.flags: TIMED and n_on_hop > n_second */
@@ -620,7 +621,8 @@ int64_t btbbx_le_track_host(const uint64_t *words, uint64_t n_words, uint64_t pi
  * LIMITS, which follow from the rules: the observed map stands in for the connection's, so a used channel that never shows makes
  * the remapping wrong; with few events, or a map of one or two channels, many hypotheses tie (full map, REMAP, 200 random draws:
  * the winner was unique and right in 22 of them at 6 events, 197 at 8, 200 at 12); a channel map update inside the capture is not
- * followed; the tracking's limits on the relative counters carry over. */
+ * followed by this stage (btbbx_le_epoch_device does, from the CONNECT_IND); the tracking's limits on the relative counters carry
+ * over. */
 #define BTBBX_LE_CSA2_REMAP     1u  /* flags argument: as BTBBX_LE_TRACK_REMAP */
 #define BTBBX_LE_CSA2_EVALUATED 1u  /* btbbx_le_csa2.flags: the connection's track is TIMED */
 #define BTBBX_LE_CSA2_UNIQUE    2u  /* EVALUATED and n_on > n_second */
@@ -662,6 +664,165 @@ int64_t btbbx_le_csa2_host(const uint64_t *words, uint64_t n_words, uint64_t pit
 			   btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
 			   uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
 			   btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_csa2 *sel, btbbx_le_csa2_pkt *sel_pkts);
+
+/* ---- LE following from CONNECT_IND: absolute event counters, channel map updates -------------- */
+/* The three limits the tracking and algorithm #2 share -- the observed map stands in for the connection's, the counter is
+ * relative to the first event seen, an update inside the capture is not followed -- go away when the capture holds what a sniffer
+ * follows: the CONNECT_IND on an advertising channel (AA, CRCInit, the true map, hop increment, interval, transmit window, ChSel;
+ * the fields lell_print decodes, bluetooth_le_packet.c:627-647) and the LL_CHANNEL_MAP_IND / LL_CONNECTION_UPDATE_IND control
+ * PDUs inside the connection, each with an absolute instant.  Two stages behind the tracking.  All arithmetic is integer
+ * arithmetic, 64 bits wide where a sum can leave 32.
+ *
+ * SEED.  With M = min(*d_adv_count, adv_cap) records as btbbx_le_decode_hits_device leaves them for a scan with BTBBX_LE_ADV_AA /
+ * BTBBX_LE_ADV_CRC_INIT, K = min(*d_conn_count, conn_cap), and bytes[] counted from the first AA octet (the payload starts at 6):
+ *   1. REQUEST.  Record j is a request iff crc_ok == 1, truncated == 0, is_data == 0, adv_type == 5 and length == 34.  InitA =
+ *      bytes 6..11, AdvA = 12..17, AA = LE32 at 18, CRCInit = LE24 at 22 (the integer btbbx_le_conn.crc_init holds), WinSize =
+ *      [25], WinOffset = LE16 at 26, Interval = LE16 at 28, Latency = LE16 at 30, Timeout = LE16 at 32, map = the low 37 bits of
+ *      the LE40 at 34, Hop = [39] & 0x1f, SCA = [39] >> 5, ChSel = (bytes[4] >> 5) & 1, TxAdd / RxAdd = bits 6 / 7 of bytes[4].
+ *   2. VALID iff 5 <= Hop <= 16, 6 <= Interval <= 3200, popcount(map) >= 2, 1 <= WinSize <= min(8, Interval - 1) and
+ *      WinOffset <= Interval.  Any other request is ignored.
+ *   3. JOIN.  R = offset + 352, the request's last CRC bit + 1.  Connection g takes, among the valid requests with its (AA,
+ *      CRCInit) and R <= tracks[g].first_anchor, the one with the largest (offset, stream), ties to the largest j.  None: the
+ *      record is all zero, the connection is not SEEDED.
+ *   4. RECORD.  flags = SEEDED, t0 = R + unit_bits * (1 + WinOffset) -- the start of the transmit window, transmitWindowDelay
+ *      being 1.25 ms --, the fields of rule 1, request = j.
+ * A caller may write seeds itself, from a CONNECT_IND seen elsewhere: the follow stage reads flags, t0, map, interval, hop and
+ * chsel, nothing else.  LIMIT: a request whose connection never shows seeds nothing. */
+#define BTBBX_LE_SEED_SEEDED 1u      /* btbbx_le_seed.flags */
+
+typedef struct btbbx_le_seed {       /* 56 bytes, one per stored connection, parallel to conns / tracks */
+	uint64_t t0;                 /* first bit of the transmit window */
+	uint64_t map;                /* ChM, 37 bits */
+	uint32_t access_address, crc_init;
+	uint32_t request;            /* index of the request among the advertising records */
+	uint16_t interval, win_offset, latency, timeout;
+	uint8_t  win_size, hop, sca, chsel;
+	uint8_t  init_a[6], adv_a[6];
+	uint8_t  tx_add, rx_add;     /* the address types of InitA / AdvA */
+	uint8_t  flags;
+	uint8_t  reserved;           /* written as 0 */
+} btbbx_le_seed;
+
+/* d_seeds[0 .. K) is written, every byte of it, nothing behind it; one launch, asynchronous on hip_stream, nothing read back.
+ * BTBBX_E_ARG, before any launch: a null pointer (d_adv may be NULL with adv_cap == 0), a record pointer that is not 8-byte
+ * aligned (the counters: 4), unit_bits < 2.  conn_cap == 0 succeeds and writes nothing; adv_cap == 0 seeds nothing. */
+int btbbx_le_seed_device(const btbbx_le_pkt *d_adv, const uint32_t *d_adv_count, uint32_t adv_cap,
+			 const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
+			 const btbbx_le_track *d_tracks, uint32_t unit_bits, btbbx_le_seed *d_seeds, void *hip_stream);
+
+/* FOLLOW.  N, K, members, time order, events, anchors A_e and channels C_e are the tracking's (its rules 1-3), read from
+ * pkts[i].rank / event / channel, the candidates' offsets and conns[g].first: candidate i < N is a member of g < K iff
+ * cands[i].conn == g and pkts[i].rank != 0xffffffff; the event's anchor is the offset of its member of the smallest rank.  A
+ * candidate that is no member gets twelve 0xff bytes.  A connection that is not SEEDED gets a zero record; its members get counter
+ * 0, epoch 0, expected 0xff, on_hop 0, state 0, and kind and opcode as rule 3 gives them.  For a SEEDED connection, with
+ * P = interval * unit_bits:
+ *   1. FIRST.  Event e is BEFORE iff A_e + jitter_bits < t0.  f = the first event that is not BEFORE;
+ *      c_f = (A_f + jitter_bits - t0) / P, by floor.  Every event BEFORE: nothing is counted.
+ *   2. COUNTERS.  For e >= f, c_(e+1) = c_e + (A_(e+1) - A_e + P / 2) / P in 64 bits: the tracking's rule 5 with the seed's
+ *      interval, not the fitted one.
+ *   3. CONTROL PDUs.  Member m is CONTROL iff (header0 & 3) == 3 and length >= 1.  Its payload octets (the first 12 at most)
+ *      are read from its stream behind the header, bits beyond the stream's end as 0, and dewhitened with the channel's sequence
+ *      continued behind the two header octets; opcode = payload octet 0.  In time order the first CONTROL member with opcode 5
+ *      and length 1 (LL_START_ENC_REQ) is ENC_START and sets ENCRYPTED; CONTROL members of larger rank are OPAQUE (opcode 0xff,
+ *      never parsed).  Otherwise: MAP UPDATE iff opcode 1 and length 8 (map' = the low 37 bits of octets 1..5, instant = LE16 of
+ *      octets 6..7); PARAM UPDATE iff opcode 0 and length 12 (instant = LE16 of octets 10..11); TERMINATE iff opcode 2 and
+ *      length 2 (it sets TERMINATED).  An update PDU in a counted (not BEFORE) event with counter c has delta = (instant - c) mod
+ *      2^16; it is VALID iff delta < 32767 and, for a map update, popcount(map') >= 2; its absolute instant is I = c + delta.  An
+ *      update in a BEFORE event is ignored.
+ *   4. STOP.  stop = the smallest I of any valid PARAM UPDATE, 2^64 - 1 without one.  Event e is BEYOND iff c_e >= stop.  A MAP
+ *      UPDATE whose own event is BEYOND is ignored.
+ *   5. MAP IN FORCE.  M_e = map' of the valid, unignored MAP UPDATE with the largest (I, rank) among those with I <= c_e, the
+ *      seed's map without one.  epoch_e = the number of such update PDUs with I <= c_e (retransmissions count), stored
+ *      saturating at 65535; 0 for a BEFORE event.
+ *   6. PREDICTION, for counted events that are not BEYOND.  used_e[] = the channels of M_e, ascending, n_used_e their number.
+ *      #1: u = (hop * ((c_e + 1) mod 37)) mod 37, expected = u if M_e holds it, else used_e[u mod n_used_e].  #2: rules 3-4 of
+ *      btbbx_le_csa2_* with c_e mod 2^16, the map M_e and always the remapping.  chsel 0: #1.  chsel 1: both are scored over the
+ *      events; the one with more events on its prediction is the connection's algorithm, a tie goes to #2.  BEFORE and BEYOND
+ *      events have expected 0xff and on_hop 0.
+ *   7. RECORDS.  n_before, n_on, n_off and n_beyond count EVENTS and add up to the connection's events; n_control counts
+ *      CONTROL members, OPAQUE ones included; n_map_updates the valid, unignored map update PDUs.  A packet's kind is
+ *      MAP_UPDATE / PARAM_UPDATE only for a VALID update that is not ignored; any other update stays CONTROL.
+ * LIMITS: the interval after a parameter update is not followed (the new window's anchor has to be found: the next step);
+ * LL_PAUSE_ENC is not tracked; a first event seen only through a packet longer than unit_bits - jitter_bits - 230 bits behind
+ * its missed anchor may get c_f one too large; a request whose connection never shows seeds nothing. */
+#define BTBBX_LE_FOLLOW_SEEDED     1u   /* btbbx_le_follow.flags */
+#define BTBBX_LE_FOLLOW_COUNTED    2u   /* some event is not BEFORE */
+#define BTBBX_LE_FOLLOW_STOPPED    4u   /* stop is finite */
+#define BTBBX_LE_FOLLOW_TERMINATED 8u
+#define BTBBX_LE_FOLLOW_ENCRYPTED  16u
+#define BTBBX_LE_STATE_COUNTED 0u       /* btbbx_le_follow_pkt.state */
+#define BTBBX_LE_STATE_BEFORE  1u
+#define BTBBX_LE_STATE_BEYOND  2u
+#define BTBBX_LE_PDU_DATA         0u    /* btbbx_le_follow_pkt.kind */
+#define BTBBX_LE_PDU_CONTROL      1u
+#define BTBBX_LE_PDU_MAP_UPDATE   2u
+#define BTBBX_LE_PDU_PARAM_UPDATE 3u
+#define BTBBX_LE_PDU_TERMINATE    4u
+#define BTBBX_LE_PDU_ENC_START    5u
+#define BTBBX_LE_PDU_OPAQUE       6u
+
+typedef struct btbbx_le_follow {     /* 48 bytes, one per stored connection, parallel to conns / tracks / seeds */
+	uint64_t map;                /* the map in force at the last predicted event; the seed's map without one */
+	uint32_t counter_first;      /* low 32 bits of c_f; 0 unless COUNTED */
+	uint32_t stop;               /* low 32 bits of stop */
+	uint32_t n_before, n_on, n_off, n_beyond;   /* events */
+	uint32_t n_control, n_map_updates;          /* members */
+	uint8_t  algorithm;          /* 1 or 2 */
+	uint8_t  flags;
+	uint8_t  reserved[6];        /* written as 0 */
+} btbbx_le_follow;                   /* a connection that is not SEEDED: 48 zero bytes */
+
+typedef struct btbbx_le_follow_pkt { /* 12 bytes, one per candidate, parallel to the sorted candidate list */
+	uint32_t counter;            /* low 32 bits of its event's connEventCounter; 0 for a BEFORE event */
+	uint16_t epoch;
+	uint8_t  kind, opcode;       /* opcode: 0xff unless CONTROL and parsed */
+	uint8_t  expected, on_hop, state;
+	uint8_t  reserved;           /* written as 0 */
+} btbbx_le_follow_pkt;               /* a candidate that is no member of a stored connection: twelve 0xff bytes */
+
+/* The input is what btbbx_le_discover_group_device, btbbx_le_track_device and btbbx_le_seed_device left, with the streams the
+ * candidates came from.  A list from elsewhere must keep the grouping's promise -- the members of g are candidates of
+ * [conns[g].first, first + n_packets) -- and the tracking's: ranks and events number a connection's members and events without
+ * gaps; a member whose first + rank or first + event lies beyond N is treated as no member.  d_tracks and d_phys_channel are
+ * taken for the chain's sake and not read: everything the stage needs of them stands in d_pkts.  d_follows[0 .. K) and
+ * d_follow_pkts[0 .. N) are written, every byte of them, nothing behind them; nothing is read back and the call is asynchronous on
+ * hip_stream.  d_scratch: btbbx_le_epoch_scratch_bytes(cand_cap, conn_cap) bytes (about 130 per candidate and 64 per
+ * connection).  The count of launches depends on conn_cap only through one radix pass per byte of it.  BTBBX_E_ARG, before any
+ * launch: a null pointer, n_streams == 0, unit_bits < 2, jitter_bits >= unit_bits / 2, n_words == 0 or above 2^42, pitch_words <
+ * n_words with more than one stream, a scratch that is too small or not 16-byte aligned, words or records that are not 8-byte
+ * aligned (d_pkts included; d_follow_pkts, whose records are 12 bytes, and the counters: 4; the channels: 2).  cand_cap == 0 or conn_cap == 0 succeeds and writes
+ * nothing. */
+size_t btbbx_le_epoch_scratch_bytes(uint32_t cand_cap, uint32_t conn_cap);
+int btbbx_le_epoch_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			   const uint16_t *d_phys_channel,
+			   const btbbx_le_cand *d_cands, const uint32_t *d_cand_count, uint32_t cand_cap,
+			   const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
+			   const btbbx_le_track *d_tracks, const btbbx_le_track_pkt *d_pkts, const btbbx_le_seed *d_seeds,
+			   uint32_t unit_bits, uint32_t jitter_bits,
+			   btbbx_le_follow *d_follows, btbbx_le_follow_pkt *d_follow_pkts,
+			   void *d_scratch, size_t scratch_bytes, void *hip_stream);
+
+/* Host wrapper: btbbx_le_track_host's chain with three additions on the same stream.  In front of the seed stage: the advertising
+ * scan over all streams of the same device copy of the capture (BTBBX_LE_ADV_AA, adv_errors 0..4 mismatches allowed), ordered by
+ * (stream, offset) and decoded with BTBBX_LE_ADV_CRC_INIT; it is repeated with room for every match when its first buffer was too
+ * small, as btbbx_le_scan_host does.  Behind the tracking: the seed stage, then the follow stage.  The tracking's arguments and
+ * return value; tracks, seeds and follows: conn_cap records, parallel to conns; pkts and follow_pkts (either may be NULL):
+ * cand_cap records, parallel to cands.  seeds[g].request indexes the advertising records in (stream, offset) order, which
+ * btbbx_le_scan_host returns for the same capture and adv_errors.  BTBBX_E_ARG: the tracking wrapper's conditions, adv_errors
+ * outside 0..4, seeds or follows NULL with conn_cap != 0.  Safe to call from several host threads at once. */
+int64_t btbbx_le_epoch_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			     uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+			     btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+			     uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+			     int adv_errors, btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_seed *seeds,
+			     btbbx_le_follow *follows, btbbx_le_follow_pkt *follow_pkts);
+
+/* Names.  The entries of this stage are btbbx_le_epoch_* ("epoch": the stretch of events one channel map is in force for), not
+ * btbbx_le_follow_*: the exported names that contain "follow" are, and stay, the two of the BR/EDR follow stage below.  The
+ * records keep the stage's name.  For source that would rather say what the stage does: */
+#define btbbx_le_follow_scratch_bytes btbbx_le_epoch_scratch_bytes
+#define btbbx_le_follow_device        btbbx_le_epoch_device
+#define btbbx_le_follow_host          btbbx_le_epoch_host
 
 /* ---- hop selection and CLK1-27 reversal ------------------------- */
 #define BTBBX_SEQUENCE_LENGTH 134217728u   /* values of CLK1-27, bluetooth_piconet.h:102 */

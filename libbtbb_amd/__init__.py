@@ -111,6 +111,23 @@ LE_CSA2_DTYPE = np.dtype([("n_on", "<u4"), ("n_off", "<u4"), ("n_second", "<u4")
 LE_CSA2_PKT_DTYPE = np.dtype([("counter", "<u2"), ("prn", "<u2"), ("unmapped", "u1"), ("expected", "u1"), ("on_hop", "u1"),
                               ("reserved", "u1")])
 assert LE_CSA2_DTYPE.itemsize == 24 and LE_CSA2_PKT_DTYPE.itemsize == 8
+# LE following from CONNECT_IND (include/btbbx.h btbbx_le_seed / btbbx_le_follow / btbbx_le_follow_pkt; le_follow.h checks the C
+# layout with static_asserts)
+LE_SEED_SEEDED = 1
+LE_FOLLOW_SEEDED, LE_FOLLOW_COUNTED, LE_FOLLOW_STOPPED, LE_FOLLOW_TERMINATED, LE_FOLLOW_ENCRYPTED = 1, 2, 4, 8, 16
+LE_STATE_COUNTED, LE_STATE_BEFORE, LE_STATE_BEYOND = 0, 1, 2
+(LE_PDU_DATA, LE_PDU_CONTROL, LE_PDU_MAP_UPDATE, LE_PDU_PARAM_UPDATE, LE_PDU_TERMINATE, LE_PDU_ENC_START,
+ LE_PDU_OPAQUE) = range(7)
+LE_SEED_DTYPE = np.dtype([("t0", "<u8"), ("map", "<u8"), ("access_address", "<u4"), ("crc_init", "<u4"), ("request", "<u4"),
+                          ("interval", "<u2"), ("win_offset", "<u2"), ("latency", "<u2"), ("timeout", "<u2"), ("win_size", "u1"),
+                          ("hop", "u1"), ("sca", "u1"), ("chsel", "u1"), ("init_a", "u1", (6,)), ("adv_a", "u1", (6,)),
+                          ("tx_add", "u1"), ("rx_add", "u1"), ("flags", "u1"), ("reserved", "u1")])
+LE_FOLLOW_DTYPE = np.dtype([("map", "<u8"), ("counter_first", "<u4"), ("stop", "<u4"), ("n_before", "<u4"), ("n_on", "<u4"),
+                            ("n_off", "<u4"), ("n_beyond", "<u4"), ("n_control", "<u4"), ("n_map_updates", "<u4"),
+                            ("algorithm", "u1"), ("flags", "u1"), ("reserved", "u1", (6,))])
+LE_FOLLOW_PKT_DTYPE = np.dtype([("counter", "<u4"), ("epoch", "<u2"), ("kind", "u1"), ("opcode", "u1"), ("expected", "u1"),
+                                ("on_hop", "u1"), ("state", "u1"), ("reserved", "u1")])
+assert LE_SEED_DTYPE.itemsize == 56 and LE_FOLLOW_DTYPE.itemsize == 48 and LE_FOLLOW_PKT_DTYPE.itemsize == 12
 
 # one surveyed piconet (include/btbbx.h btbbx_survey_rec; survey.hip checks the C layout with static_asserts)
 SURVEY_DTYPE = np.dtype([("lap", "<u4"), ("flags", "<u4"), ("uap", "u1"), ("clk_offset", "u1"), ("used_channels", "u1"),
@@ -207,6 +224,12 @@ SIGNATURES = {
     "btbbx_le_csa2_device": (C.c_int, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, C.c_size_t, _vp]),
     "btbbx_le_csa2_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
                                        _vp, _vp, _vp, _vp]),
+    "btbbx_le_seed_device": (C.c_int, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _vp]),
+    "btbbx_le_epoch_scratch_bytes": (C.c_size_t, [_u32, _u32]),
+    "btbbx_le_epoch_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _vp, _vp,
+                                         _vp, C.c_size_t, _vp]),
+    "btbbx_le_epoch_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
+                                         C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "btbbx_survey_scratch_bytes": (C.c_size_t, [_u32]),
     "btbbx_survey_hits_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp,
                                            _vp, C.c_size_t, _vp]),
@@ -491,6 +514,41 @@ def le_csa2(words, search_bits, phys_channels, max_len=27, min_count=2, n_stream
         raise BtbbError("buffers too small: %d connections > %d or %d candidates > %d" % (n, conn_cap, n_cands.value, cand_cap))
     nc, nk = min(n, conn_cap), min(n_cands.value, cand_cap)
     return conns[:nc].copy(), cands[:nk].copy(), tracks[:nc].copy(), pkts[:nk].copy(), sel[:nc].copy(), sel_pkts[:nk].copy()
+
+
+def le_follow(words, search_bits, phys_channels, max_len=27, min_count=2, n_streams=1, pitch_words=None, n_words=None,
+              unit_bits=1250, ifs_bits=200, jitter_bits=50, flags=LE_TRACK_REMAP, adv_errors=0, conn_cap=1 << 12, cand_cap=1 << 20,
+              truncate=False):
+    """le_track, then LE following from CONNECT_IND (include/btbbx.h btbbx_le_seed_device / btbbx_le_epoch_device): every
+    connection joined with the CONNECT_IND on an advertising stream of the same capture (adv_errors: mismatches allowed over its
+    preamble and access address), every event's absolute connEventCounter, the channel map updates put in force at their instants,
+    and every packet checked against the prediction of the map in force.  le_track's parameters.  Returns (conns, cands, tracks,
+    pkts, seeds, follows, follow_pkts): le_track's four arrays, LE_SEED_DTYPE and LE_FOLLOW_DTYPE records parallel to conns and
+    LE_FOLLOW_PKT_DTYPE records parallel to cands."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if pitch_words is None:
+        pitch_words = len(words) // n_streams
+    if n_words is None:
+        n_words = pitch_words
+    assert n_words <= pitch_words and (n_streams - 1) * pitch_words + n_words <= len(words)
+    phys = np.ascontiguousarray(np.broadcast_to(np.asarray(phys_channels, dtype=np.uint16), (n_streams,)))
+    conns = np.empty(max(conn_cap, 1), dtype=LE_CONN_DTYPE)
+    tracks = np.empty(max(conn_cap, 1), dtype=LE_TRACK_DTYPE)
+    seeds = np.empty(max(conn_cap, 1), dtype=LE_SEED_DTYPE)
+    follows = np.empty(max(conn_cap, 1), dtype=LE_FOLLOW_DTYPE)
+    cands = np.empty(max(cand_cap, 1), dtype=LE_CAND_DTYPE)
+    pkts = np.empty(max(cand_cap, 1), dtype=LE_TRACK_PKT_DTYPE)
+    follow_pkts = np.empty(max(cand_cap, 1), dtype=LE_FOLLOW_PKT_DTYPE)
+    n_cands = C.c_uint64(0)
+    n = check(lib().btbbx_le_epoch_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, _ptr(phys), max_len, min_count,
+                                         _ptr(conns), conn_cap, _ptr(cands), cand_cap, C.byref(n_cands), unit_bits, ifs_bits, jitter_bits,
+                                         flags, adv_errors, _ptr(tracks), _ptr(pkts), _ptr(seeds), _ptr(follows), _ptr(follow_pkts)),
+              "btbbx_le_epoch_host")
+    if (n > conn_cap or n_cands.value > cand_cap) and not truncate:
+        raise BtbbError("buffers too small: %d connections > %d or %d candidates > %d" % (n, conn_cap, n_cands.value, cand_cap))
+    nc, nk = min(n, conn_cap), min(n_cands.value, cand_cap)
+    return (conns[:nc].copy(), cands[:nk].copy(), tracks[:nc].copy(), pkts[:nk].copy(), seeds[:nc].copy(), follows[:nc].copy(),
+            follow_pkts[:nk].copy())
 
 
 class DeviceBuffer:

@@ -658,6 +658,7 @@ struct LeDiscHostRun {
 	btbbx_le_cand *d_cands;
 	btbbx_le_conn *d_conns;
 	const uint16_t *d_phys;
+	const uint64_t *d_words;                       // the capture as it was copied in
 	char *tail;
 };
 
@@ -716,6 +717,7 @@ static int le_disc_host_chain(const uint64_t *words, uint64_t n_words, uint64_t 
 	r->d_cands = (btbbx_le_cand *)(block + 256);
 	r->d_conns = (btbbx_le_conn *)(block + 256 + cand_bytes + scratch_bytes);
 	r->d_phys = d_phys;
+	r->d_words = d_words;
 	r->tail = block + 256 + cand_bytes + scratch_bytes + conn_bytes;
 	if (!r->have)
 		return BTBBX_OK;
