@@ -8,7 +8,8 @@ finds the map in force by a binary search of a radix-sorted list).
 * connect_ind / adv_record: a CONNECT_IND as the 64 bytes and the record btbbx_le_decode_hits_device leaves
 * World: planted connections -- they hop by the FORWARD selections of tests/_le_track.py (csa1_at) and tests/_le_csa2.py (csa2),
   which share nothing with the model's closed forms --, their requests and the stream bits of their control PDUs
-* lattice / seam_world / crowd_world: the lists the CPU and GPU tests share
+* lattice / seam_world / wrap_world: the lists the CPU and GPU tests share; crowd_world / byte_world / tally_world: the worlds laid
+  out by position for tests/_le_follow_paths.py, which names the kernels' paths they drive; cut_model: their cuts' models
 """
 import collections
 import functools
@@ -172,10 +173,12 @@ def predict2(aa, c, m, rules=MODEL):
     return expected
 
 
-def follow(conns, cands, tracks, pkts, seeds, words, n_words, unit_bits, jitter_bits, rules=MODEL):
+def follow(conns, cands, tracks, pkts, seeds, words, n_words, unit_bits, jitter_bits, rules=MODEL, trace=None):
     """conns, cands: as ld.group leaves them; tracks, pkts: what lt.track returned (len(tracks) = K, len(pkts) = N); seeds: one Seed
     or None per connection; words: the streams, one row each.  Returns (follows, fpkts): one Follow or None (zeros) per
-    connection, one FPkt or None (0xff) per candidate."""
+    connection, one FPkt or None (0xff) per candidate.  trace: a dict that takes, per seeded connection, what the records do not
+    hold in full -- the 64-bit counters, the updates as (I, rank, map', candidate), stop, the map in force and the state of every
+    event (tests/_le_follow_paths.py numbers the kernels' tables from them)."""
     k = len(tracks)
     fpkts = [None] * len(pkts)
     members = [[] for _ in range(k)]
@@ -280,6 +283,8 @@ def follow(conns, cands, tracks, pkts, seeds, words, n_words, unit_bits, jitter_
         if any(kd == TERMINATE for kd in kind.values()):
             flags |= TERMINATED
         first = min(cnt) if cnt else None
+        if trace is not None:
+            trace[g] = dict(cnt=cnt, ups=ups, stop=stop, in_force=in_force, state=state)
         follows.append(Follow(in_force[predicted[-1]] if predicted else s.map, cnt[first] & 0xFFFFFFFF if cnt else 0, stop & 0xFFFFFFFF,
                               tally(ST_BEFORE), on[algorithm], tally(ST_COUNTED) - on[algorithm], tally(ST_BEYOND), len(ctl), len(ups),
                               algorithm, flags))
@@ -409,10 +414,10 @@ class World:
 Built = collections.namedtuple("Built", "conns cands tracks pkts adv words names info unit n_words ifs jitter")
 
 
-def model(b, rules=MODEL):
+def model(b, rules=MODEL, trace=None):
     """(seeds, follows, fpkts) of the model on a Built."""
     seeds = seed(b.adv, b.conns, b.tracks, b.unit, rules)
-    return (seeds,) + follow(b.conns, b.cands, b.tracks, b.pkts, seeds, b.words, b.n_words, b.unit, b.jitter, rules)
+    return (seeds,) + follow(b.conns, b.cands, b.tracks, b.pkts, seeds, b.words, b.n_words, b.unit, b.jitter, rules, trace)
 
 
 def check_planted(b, seeds, follows, fpkts):
@@ -602,6 +607,154 @@ def wrap_model():
 @functools.lru_cache(maxsize=None)
 def seam_model():
     return model(seam_world())
+
+
+# ---- the worlds of tests/_le_follow_paths.py: laid out by position ------------------------------------------------------------
+# Their connections get ascending access addresses, so ld.group keeps them in the order they are planted in and connection g's
+# slots and events begin at the sum of the packets in front of it: a world is laid out by counting packets.
+CROWD_CONNS, CROWD_NOISE, CROWD_TILE = 1450, 40, 2048          # (CROWD_TILE: LT_TILE of le_track.h; tests/test_le_follow_paths_model.py holds them together)
+
+
+@functools.lru_cache(maxsize=None)
+def crowd_world():
+    """1 450 connections of 12 events side by side, unit_bits 120, streams of 16 384 words; four in five are seeded, and all but one
+    in twenty-five carry four LL_CHANNEL_MAP_IND in their events 1 to 4: I = 8 announced in front of I = 6, then two with I = 10.
+    More than 4 096 listed updates, in every scan tile of slots but the third (the connections that begin there are not seeded);
+    a connection begins on every tile seam but the fifth, which a seeded one lies across (the one in front of a seam gets as many
+    second packets as it takes: holes in the event table); forty non-members lie between the two halves.  Every instant is shared
+    by all connections with updates."""
+    w = World(41, unit=120, n_words=16384)
+    rng = np.random.default_rng(43)
+    pool = [lt.random_map(rng, n) for n in (17, 23, 30, 33, 36, 25, 28, 35)]
+    p = 0                                                                  # where the next connection's slots and events begin
+    for k in range(CROWD_CONNS):
+        if k == CROWD_CONNS // 2:
+            p += CROWD_NOISE
+        on_seam = p > 0 and p % CROWD_TILE == 0 or p < 5 * CROWD_TILE < p + 12
+        seeded = (on_seam or k % 10 != 9) and not 2 * CROWD_TILE - 14 <= p < 3 * CROWD_TILE
+        room = -(p + 12) % CROWD_TILE
+        second = tuple(range(room)) if room < 12 and p + 12 + room != 5 * CROWD_TILE else ((0, 7) if k % 3 == 0 else ())
+        a, b, c, d = (pool[(k + j) % 8] for j in range(4))
+        pdus = {} if k % 25 == 7 else {1: [map_ind(a, 8)], 2: [map_ind(b, 6)], 3: [map_ind(c, 10)], 4: [map_ind(d, 10)]}
+        for shift in range(0, 700, 37):                                    # (a control PDU that would overwrite another's bits: a little later)
+            keep = len(w.raw), len(w.adv), len(w.info), [len(t) for t in w.taken], w.k
+            try:
+                w.conn("planted: crowd %d" % k, range(12), alg=1 + k % 2, hop=5 + k % 12, chmap=pool[(k + 5) % 8] if k % 4 else lc.FULL_MAP,
+                       request=seeded, req_offset=2000 + 700 * k + shift, aa=(0x68000000 if k >= CROWD_CONNS // 2 else 0x20000000) + 0x3001 * k,
+                       maps=[(6, b), (8, a), (10, d)] if pdus else [], pdus=pdus, second=second)
+                break
+            except AssertionError:
+                del w.raw[keep[0]:], w.adv[keep[1]:], w.info[keep[2]:]
+                for t, n in zip(w.taken, keep[3]):
+                    del t[n:]
+                w.k = keep[4]
+        else:
+            raise AssertionError("no room for connection %d" % k)
+        p += 12 + len(second)
+    w.noise(CROWD_NOISE)
+    return w.built()
+
+
+@functools.lru_cache(maxsize=None)
+def crowd_model():
+    trace = {}
+    return model(crowd_world(), trace=trace) + (trace,)
+
+
+M35 = lc.FULL_MAP & ~(1 << 5)
+
+
+@functools.lru_cache(maxsize=None)
+def byte_world():
+    """wrap_world's geometry (unit_bits 2, jitter_bits 0, ifs_bits 0) with two connections that announce two updates each, the later
+    instant first: 0x10001 in front of 0xFFFF -- the low sixteen bits order them the wrong way round, byte 2 alone decides -- and
+    0x101 in front of 0xFF, which byte 1 decides."""
+    w = World(37, unit=2, n_words=12800, ifs=0, jitter=0)
+    w.conn("planted: byte 2 decides", (65527, 65528, 65529, 65530, 65534, 65535, 65536, 65537, 65538, 65540),
+           maps=[(0xFFFF, M35), (0x10001, M36)], pdus={65529: [map_ind(M36, 0x10001)], 65530: [map_ind(M35, 0xFFFF)]})
+    w.conn("planted: byte 1 decides", (250, 251, 252, 254, 255, 256, 257, 258, 260), hop=11,
+           maps=[(0xFF, M35), (0x101, M36)], pdus={250: [map_ind(M36, 0x101)], 251: [map_ind(M35, 0xFF)]})
+    w.noise(10)
+    return w.built()
+
+
+@functools.lru_cache(maxsize=None)
+def byte_model():
+    trace = {}
+    return model(byte_world(), trace=trace) + (trace,)
+
+
+@functools.lru_cache(maxsize=None)
+def tally_world():
+    """330 events laid out lane by lane for le_epoch_predict_kernel's tallies (a wave is 64 event positions): positions 0..3 a
+    connection whose counters pass 2^33; 4..62 one with two BEFORE events; 63..133 one whose run begins at lane 63, fills wave 1 and
+    leaves a BEYOND tail from lane 0 of wave 2 on (stop 65, an update in force before it and one behind it); 134..143 counted and
+    BEYOND events in one run and two holes; 144..148 unseeded; 149..191 seeded; wave 3: sixteen connections of three events and one
+    of sixteen; wave 4: one unseeded connection; 320..329 a seeded one behind it; 330..341 a connection whose update PDU lies across
+    the streams' end: the map and the instant's low octet are the streams' last bits, the high octet is read as zeros, which dewhitened
+    give an instant more than 32 767 events away: no update -- ones in their place give a valid one (World.conn writes no packet that
+    ends beyond the streams, so its first 112 bits are written here)."""
+    w = World(47)
+    made = [0]
+
+    def conn(name, counters, **kw):
+        made[0] += 1
+        w.conn(name, counters, aa=0x21000000 + 0x5003 * made[0], **kw)
+
+    conn("planted: counters beyond 2^33 in front of all", (0, 1, (1 << 32) + 2, (1 << 33) + 3))
+    conn("two BEFORE events, ends at lane 62", range(59), win_offset=6, at=-7 * UNIT)
+    conn("planted: head at lane 63, wave 1, a BEYOND tail", range(71), stop=65, maps=[(10, NINE)],
+         pdus={1: [map_ind(NINE, 10)], 2: [param_ind(65)], 3: [map_ind(FIVE, 67)]})
+    conn("planted: counted and BEYOND in one run, two holes", range(8), stop=4, pdus={1: [param_ind(4)]}, second=(0, 5), alg=2)
+    conn("unseeded between seeded runs", range(5), request=False)
+    conn("planted: up to the end of wave 2", range(43), maps=[(5, NINE)], pdus={1: [map_ind(NINE, 5)]})
+    for k in range(16):
+        conn("planted: three events, %d" % k, range(3), alg=1 + k % 2, hop=5 + k % 12)
+    conn("planted: up to the end of wave 3", range(16), alg=2)
+    conn("unseeded, a wave of its own", range(64), request=False)
+    conn("planted: behind the wave without a live lane", range(10), maps=[(4, FIVE)], pdus={1: [map_ind(FIVE, 4)]})
+    at = 64 * N_WORDS - 112
+    conn("planted: an instant's high octet behind the streams' end", range(28, 40), pdus={30: [map_ind(NINE, 34)]},
+         req_offset=at - 30 * 6 * UNIT - 352 - 2 * UNIT)
+    last = w.info[-1]
+    ch = last.channels[2]
+    assert [c.offset for c in w.raw if c.access_address == last.aa and c.length == 8] == [at]
+    w.bits[ch, at:] = _le.tx_bits(last.aa, ch, bytes((3, 8)) + map_ind(NINE, 34)[1], last.crc_init)[:112]
+    w.noise(30)
+    return w.built()
+
+
+@functools.lru_cache(maxsize=None)
+def tally_model():
+    trace = {}
+    return model(tally_world(), trace=trace) + (trace,)
+
+
+def cut_model(b, full, trace, work=None, kept=None):
+    """What model_cut gives for the first `work` candidates and `kept` connections of a Built, from the whole list's model (`full`,
+    `trace`): connections do not touch each other, so only the one the cut goes through is worked out again, alone.
+    -> (pkts, seeds, follows, fpkts, trace).  (tests/test_le_follow_paths_model.py holds it against model_cut.)"""
+    n = len(b.cands) if work is None else min(work, len(b.cands))
+    k = len(b.conns) if kept is None else min(kept, len(b.conns))
+    seeds, follows, fpkts, pkts = list(full[0][:k]), list(full[1][:k]), list(full[2][:n]), list(b.pkts[:n])
+    trace = {g: t for g, t in trace.items() if g < k}
+    for g, c in enumerate(b.conns):
+        lo, hi = c.first, c.first + c.n_packets
+        if g >= k:
+            for i in range(lo, min(hi, n)):
+                fpkts[i] = pkts[i] = None
+        elif hi > n:
+            m = max(n - lo, 0)
+            sub = [x._replace(channel=0) for x in b.cands[lo:lo + m]]
+            tracks, pk = lt.track(sub, 1, lt.LATTICE_MHZ, lt.N_STREAMS, b.unit, b.ifs, b.jitter, lt.REMAP)
+            sd, own = seed(b.adv, [c], tracks, b.unit), {}
+            fo, fp = follow([c], sub, tracks, pk, sd, b.words, b.n_words, b.unit, b.jitter, trace=own)
+            seeds[g], follows[g] = sd[0], fo[0]
+            fpkts[lo:lo + m], pkts[lo:lo + m] = fp, pk
+            trace.pop(g, None)
+            if 0 in own:
+                trace[g] = dict(own[0], ups=[(at, rank, mp, i + lo) for at, rank, mp, i in own[0]["ups"]])
+    return pkts, seeds, follows, fpkts, trace
 
 
 def model_cut(b, work=None, kept=None, n_adv=None, rules=MODEL, flags=lt.REMAP):

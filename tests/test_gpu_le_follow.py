@@ -3,12 +3,17 @@ btbbx_le_track_device, btbbx_le_seed_device and btbbx_le_epoch_device -- the lat
 list that crosses the kernels' seams -- and the chain scan -> discover -> track -> seed -> follow on a capture, once through the host
 wrapper and once device-resident.  Every expectation is the model's (tests/_le_follow.py on top of tests/_le_track.py's model of
 the tracking), byte for byte.  Output buffers start as 0xA5 and are one record longer than their caps, so a byte a kernel leaves
-unwritten, or writes where it should not, shows."""
+unwritten, or writes where it should not, shows.
+
+The worlds of tests/_le_follow_paths.py drive the kernels' decomposition -- tile prefix, rounds, radix passes over more than one tile
+and over the connection's second byte, the searches' ends, the per-wave runs --; which tag each carries is asserted on the CPU
+(tests/test_le_follow_paths_model.py) and once more here, in front of the run."""
 import numpy as np
 import pytest
 
 import _le_discover as ld
 import _le_follow as lf
+import _le_follow_paths as lp
 import _le_track as lt
 import libbtbb_amd as bt
 
@@ -44,8 +49,10 @@ def _records(buf, n, dtype):
     return buf.cpu().numpy()[:n * dtype.itemsize].view(dtype)
 
 
-def _follow_device(b, conn_cap=None, count=None, cand_cap=None, conn_count=None, adv_cap=None, adv_count=None):
-    """Tracking, seed and follow on the device -> (seeds, follows, fpkts), each whole, one record longer than its cap."""
+def _follow_device(b, conn_cap=None, count=None, cand_cap=None, conn_count=None, adv_cap=None, adv_count=None, pad_words=0, records=None):
+    """Tracking, seed and follow on the device -> (seeds, follows, fpkts), each whole, one record longer than its cap.
+    pad_words: the rows of the streams that many words apart, the words between them all ones; records: (conns, tracks, pkts)
+    as arrays -- the tracking is not run, the seed and follow stages get these in its place."""
     import torch
     lib = bt.lib()
     n, k, m = len(b.cands), len(b.conns), len(b.adv)
@@ -53,7 +60,11 @@ def _follow_device(b, conn_cap=None, count=None, cand_cap=None, conn_count=None,
     conn_count, conn_cap = k if conn_count is None else conn_count, k if conn_cap is None else conn_cap
     adv_count, adv_cap = m if adv_count is None else adv_count, m if adv_cap is None else adv_cap
     d_cands, d_conns = _dev(ld.cand_array(b.cands, CAND)), _dev(ld.conn_array(b.conns, CONN))
-    d_phys, d_words, d_adv = _dev(np.asarray(lt.LATTICE_MHZ, np.uint16)), _dev(b.words.reshape(-1)), _dev(lf.adv_array(b.adv, ADV))
+    words = b.words
+    if pad_words:
+        words = np.full((len(b.words), b.n_words + pad_words), ~np.uint64(0), np.uint64)
+        words[:, :b.n_words] = b.words
+    d_phys, d_words, d_adv = _dev(np.asarray(lt.LATTICE_MHZ, np.uint16)), _dev(words.reshape(-1)), _dev(lf.adv_array(b.adv, ADV))
     d_tracks, d_pkts = _filled((conn_cap + 1) * TRACK.itemsize), _filled((cand_cap + 1) * PKT.itemsize)
     d_seeds, d_follows = _filled((conn_cap + 1) * SEED.itemsize), _filled((conn_cap + 1) * FOLLOW.itemsize)
     d_fpkts = _filled((cand_cap + 1) * FPKT.itemsize)
@@ -61,12 +72,16 @@ def _follow_device(b, conn_cap=None, count=None, cand_cap=None, conn_count=None,
     tscratch, scratch = lib.btbbx_le_track_scratch_bytes(cand_cap, conn_cap), lib.btbbx_le_epoch_scratch_bytes(cand_cap, conn_cap)
     d_tscr, d_scr = _filled(tscratch), _filled(scratch)
     p = d_cnt.data_ptr()
-    bt.check(lib.btbbx_le_track_device(d_cands.data_ptr(), p, cand_cap, d_conns.data_ptr(), p + 4, conn_cap, d_phys.data_ptr(), lt.N_STREAMS,
-                                       b.unit, b.ifs, b.jitter, lt.REMAP, d_tracks.data_ptr(), d_pkts.data_ptr(), d_tscr.data_ptr(), tscratch,
-                                       None), "btbbx_le_track_device")
+    if records is None:
+        bt.check(lib.btbbx_le_track_device(d_cands.data_ptr(), p, cand_cap, d_conns.data_ptr(), p + 4, conn_cap, d_phys.data_ptr(), lt.N_STREAMS,
+                                           b.unit, b.ifs, b.jitter, lt.REMAP, d_tracks.data_ptr(), d_pkts.data_ptr(), d_tscr.data_ptr(), tscratch,
+                                           None), "btbbx_le_track_device")
+    else:
+        assert (len(records[0]), len(records[1]), len(records[2])) == (k, k, n) and (conn_cap, cand_cap) == (k, n)
+        d_conns, d_tracks, d_pkts = (_dev(r) for r in records)
     bt.check(lib.btbbx_le_seed_device(d_adv.data_ptr(), p + 8, adv_cap, d_conns.data_ptr(), p + 4, conn_cap, d_tracks.data_ptr(), b.unit,
                                       d_seeds.data_ptr(), None), "btbbx_le_seed_device")
-    bt.check(lib.btbbx_le_epoch_device(d_words.data_ptr(), b.n_words, b.n_words, lt.N_STREAMS, d_phys.data_ptr(), d_cands.data_ptr(), p,
+    bt.check(lib.btbbx_le_epoch_device(d_words.data_ptr(), b.n_words, b.n_words + pad_words, lt.N_STREAMS, d_phys.data_ptr(), d_cands.data_ptr(), p,
                                         cand_cap, d_conns.data_ptr(), p + 4, conn_cap, d_tracks.data_ptr(), d_pkts.data_ptr(),
                                         d_seeds.data_ptr(), b.unit, b.jitter, d_follows.data_ptr(), d_fpkts.data_ptr(), d_scr.data_ptr(),
                                         scratch, None), "btbbx_le_epoch_device")
@@ -209,6 +224,83 @@ def test_a_long_connection_with_forty_updates_beside_a_thousand_small_ones():
     assert (big.n_on, big.n_off, big.n_map_updates, big.algorithm) == (5000, 0, 40, 2), big
     assert lf.check_planted(b, *want) > 7000
     print("seams: %d connections, %d seeded" % (len(b.conns), sum(s is not None for s in want[0])))
+
+
+# ---- the path lattice (tests/_le_follow_paths.py) -----------------------------------------------------------------------
+@pytest.mark.parametrize("run", [r for r in lp.RUNS if r.cut is None], ids=[r.name for r in lp.RUNS if r.cut is None])
+def test_worlds_of_the_path_lattice(run):
+    """crowd_world: 4 436 listed updates over nine scan tiles, one of them empty, 1 450 connections; byte_world: instants that only
+    the passes over bytes 1 and 2 order; tally_world: the runs of le_epoch_predict_kernel lane by lane."""
+    b, full = lp.world(run.world)
+    assert set(run.tags) <= lp.run_tags(run)
+    _check(b, want=full[:3])
+    assert lf.check_planted(b, *full[:3]) > 0
+
+
+def test_cuts_of_the_crowd():
+    """conn_cap one short; cand_cap cut inside the last connection; a count that is no multiple of 256 and leaves an update in the
+    last slot."""
+    b, full = lp.world("crowd")
+    n, k, ragged = len(b.cands), len(b.conns), lp.ragged_count(b, full)
+    assert b.conns[-1].first < n - 5 and ragged % 256 and "update_in_the_last_slot_of_a_ragged_list" in lp.run_tags(lp.RUNS[1])
+    for kw, cut in ((dict(conn_cap=k - 1), dict(kept=k - 1)), (dict(cand_cap=n - 5), dict(work=n - 5)), (dict(count=ragged), dict(work=ragged))):
+        _, seeds, follows, fpkts, _ = lf.cut_model(b, full, full[3], **cut)
+        _check(b, want=(seeds, follows, fpkts), **kw)
+
+
+@pytest.mark.parametrize("conn_cap, passes", [(255, 1), (256, 2), (65535, 2), (65536, 3)])
+def test_lattice_at_the_capacities_that_add_a_connection_pass(conn_cap, passes):
+    """One radix pass per byte of conn_cap over the connection: the list comes out the same however many there are."""
+    assert passes == max(1, (conn_cap.bit_length() + 7) // 8)
+    _check(lf.lattice(), want=lf.lattice_model(), conn_cap=conn_cap)
+
+
+@pytest.mark.parametrize("name", ["lattice", "tally"])
+def test_rows_two_words_apart_from_their_ends(name):
+    """pitch_words = n_words + 2, the padding all ones: a payload read that stops at the pitch instead of n_words turns the zeros
+    behind a stream's end into ones.  The lattice's packets at the streams' end ("one bit beyond the stream's end") have their
+    payload inside the streams or more than two words behind them, so no byte of the lattice shows that; tally_world's last
+    connection has an LL_CHANNEL_MAP_IND whose instant lies half inside: with ones behind the end it becomes a valid update."""
+    b, want = (lf.lattice(), lf.lattice_model()) if name == "lattice" else (lf.tally_world(), lf.tally_model()[:3])
+    end = 64 * b.n_words
+    across = [c for c in b.cands if (c.header0 & 3) == 3 and c.length and c.offset + 56 < end < c.offset + 56 + 8 * min(c.length, 12) < end + 128]
+    assert len(across) == (1 if name == "tally" else 0)
+    assert name == "tally" or end + 1 in [c.offset + 80 + 8 * c.length for c in b.cands]
+    _check(b, want=want, pad_words=2)
+
+
+def _refused(b, tracks, pkts, none):
+    """The model's records with the candidates `none` made no members."""
+    pkts = [None if i in none else p for i, p in enumerate(pkts)]
+    seeds = lf.seed(b.adv, b.conns, tracks, b.unit)
+    return (seeds,) + lf.follow(b.conns, b.cands, tracks, pkts, seeds, b.words, b.n_words, b.unit, b.jitter)
+
+
+@pytest.mark.parametrize("case", ["rank", "event", "first = N", "first >= 2^32"])
+def test_a_list_that_breaks_the_grouping_promise_in_one_place(case):
+    """include/btbbx.h: a member whose first + rank or first + event lies beyond N is treated as no member; so is every candidate of
+    a connection whose `first` lies beyond N.  The tracking's records come from the model here, broken in exactly one place: the
+    last-ranked member of a connection, alone in its event (so the ranks and events that remain have no gap), gets rank or event
+    N - first; or conns[g].first becomes N, or gets bit 32 set.  Expected: the model's records with those candidates no members;
+    everything else byte for byte as before."""
+    b = lf.lattice()
+    n = len(b.cands)
+    g = b.names.index("planted: two updates in order" if case in ("rank", "event") else "planted: two updates out of order")
+    first, mine = b.conns[g].first, [i for i, c in enumerate(b.cands) if c.channel == g]
+    conns, tracks, pkts = ld.conn_array(b.conns, CONN), lt.track_array(b.tracks, TRACK), lt.pkt_array(b.pkts, PKT)
+    if case in ("rank", "event"):
+        last = max(mine, key=lambda i: b.pkts[i].rank)
+        assert sum(b.pkts[i].event == b.pkts[last].event for i in mine) == 1 and b.pkts[last].rank == len(mine) - 1
+        pkts[last][case] = n - first
+        none = {last}
+    else:
+        conns[g]["first"] = n if case == "first = N" else first | (1 << 32)
+        none = set(mine)
+    want = _refused(b, b.tracks, b.pkts, none)
+    whole = lf.lattice_model()
+    assert want[1][g] != whole[1][g] and [x for x in range(len(b.conns)) if want[1][x] != whole[1][x]] == [g]
+    assert all(want[2][i] is None for i in none) and sum(p is None for p in want[2]) == sum(p is None for p in whole[2]) + len(none)
+    _check(b, want=want, records=(conns, tracks, pkts))
 
 
 # ---- the chain ----------------------------------------------------------------------------------------------------------
