@@ -670,8 +670,9 @@ int64_t btbbx_le_csa2_host(const uint64_t *words, uint64_t n_words, uint64_t pit
  * relative to the first event seen, an update inside the capture is not followed -- go away when the capture holds what a sniffer
  * follows: the CONNECT_IND on an advertising channel (AA, CRCInit, the true map, hop increment, interval, transmit window, ChSel;
  * the fields lell_print decodes, bluetooth_le_packet.c:627-647) and the LL_CHANNEL_MAP_IND / LL_CONNECTION_UPDATE_IND control
- * PDUs inside the connection, each with an absolute instant.  Two stages behind the tracking.  All arithmetic is integer
- * arithmetic, 64 bits wide where a sum can leave 32.
+ * PDUs inside the connection, each with an absolute instant.  Two stages behind the tracking; a third beside the second,
+ * btbbx_le_span_device further below, goes on through the parameter updates at which the second stops.  All arithmetic is
+ * integer arithmetic, 64 bits wide where a sum can leave 32.
  *
  * SEED.  With M = min(*d_adv_count, adv_cap) records as btbbx_le_decode_hits_device leaves them for a scan with BTBBX_LE_ADV_AA /
  * BTBBX_LE_ADV_CRC_INIT, K = min(*d_conn_count, conn_cap), and bytes[] counted from the first AA octet (the payload starts at 6):
@@ -742,7 +743,7 @@ int btbbx_le_seed_device(const btbbx_le_pkt *d_adv, const uint32_t *d_adv_count,
  *   7. RECORDS.  n_before, n_on, n_off and n_beyond count EVENTS and add up to the connection's events; n_control counts
  *      CONTROL members, OPAQUE ones included; n_map_updates the valid, unignored map update PDUs.  A packet's kind is
  *      MAP_UPDATE / PARAM_UPDATE only for a VALID update that is not ignored; any other update stays CONTROL.
- * LIMITS: the interval after a parameter update is not followed (the new window's anchor has to be found: the next step);
+ * LIMITS: the interval after a parameter update is not followed by this stage (btbbx_le_span_device below finds the new window's anchor and goes on);
  * LL_PAUSE_ENC is not tracked; a first event seen only through a packet longer than unit_bits - jitter_bits - 230 bits behind
  * its missed anchor may get c_f one too large; a request whose connection never shows seeds nothing. */
 #define BTBBX_LE_FOLLOW_SEEDED     1u   /* btbbx_le_follow.flags */
@@ -823,6 +824,111 @@ int64_t btbbx_le_epoch_host(const uint64_t *words, uint64_t n_words, uint64_t pi
 #define btbbx_le_follow_scratch_bytes btbbx_le_epoch_scratch_bytes
 #define btbbx_le_follow_device        btbbx_le_epoch_device
 #define btbbx_le_follow_host          btbbx_le_epoch_host
+
+/* ---- LE following through connection parameter updates: spans ------------------------------
+ * The follow stage above ends at the instant of an LL_CONNECTION_UPDATE_IND.  The SPAN stage goes on: a span is the stretch of
+ * events that one set of connection parameters times; at the instant the new transmit window's anchor is found on the old grid,
+ * the counting restarts there with the new interval, and counters, map updates and the hop check run through.  It stands beside
+ * the follow stage, takes the same input and changes nothing of it.
+ *
+ * Members, time order, events, A_e and C_e; CONTROL parsing (12 octets, dewhitening, zeros beyond the stream's end), ENC_START and
+ * OPAQUE, TERMINATE, the validity of a map update, and delta = (instant - c) mod 2^16, VALID iff delta < 32767, I = c + delta are
+ * the follow stage's (its rules 1 to 3).  A candidate that is no member gets sixteen 0xff bytes; a connection that is not SEEDED
+ * gets 56 zero bytes, zero span records, and its members counter 0, epoch 0, span 0, expected 0xff, on_hop 0, state 0, applied 0.
+ * For a SEEDED connection, in integer arithmetic that is 64 bits wide:
+ *   1. SPAN 0.  Int_0 = seed.interval, T_0 = seed.t0, B_0 = 0, allowance a_0 = jitter_bits, start_0 = event 0.
+ *   2. COUNTING in span s.  P_s = Int_s * unit_bits.  Event e >= start_s is EARLY iff A_e + a_s < T_s: its state is BEFORE in
+ *      span 0 and GAP in a later span, it is not counted (counter 0, epoch 0, expected 0xff), and a PDU in it is ignored.  f_s =
+ *      the first event >= start_s that is not EARLY; c_(f_s) = B_s + (A_f + a_s - T_s) / P_s, by floor;
+ *      c_(e+1) = c_e + (A_(e+1) - A_e + P_s / 2) / P_s.
+ *   3. PARAM UPDATE.  Opcode 0 and length 12: WinSize' = octet 1, WinOffset' = LE16 at octets 2..3, Interval' = LE16 at 4..5,
+ *      Latency' = LE16 at 6..7, Timeout' = LE16 at 8..9, instant = LE16 at 10..11.
+ *   4. END of span s.  I_s = the smallest I of a VALID param update in any event e >= f_s, under span s's counting.  Without one,
+ *      span s is the last and stop = 2^64 - 1.  Span s's events are those with c_e < I_s; L is the last of them.
+ *   5. APPLY.  Among the VALID param updates with I == I_s whose own event has c_e < I_s, take the one of the largest rank.  It
+ *      applies iff it exists, s < max_updates, 6 <= Interval' <= 3200, 1 <= WinSize' <= min(8, Interval' - 1) and WinOffset' <=
+ *      Interval'.  Then G = A_L + (I_s - c_L) * P_s -- where event I_s would lie on the old grid; Core Vol 6 Part B 5.1.1 gives no
+ *      transmitWindowDelay here --, T_(s+1) = G + WinOffset' * unit_bits, B_(s+1) = I_s, Int_(s+1) = Interval', a_(s+1) = 2 *
+ *      jitter_bits (both ends of the measured distance deviate), start_(s+1) = L + 1; go on with rule 2.  The applied PDU has
+ *      applied = 1.
+ *   6. STOP.  Otherwise stop = I_s and the connection is STOPPED: CAPPED when s == max_updates, REFUSED otherwise (there is no
+ *      such PDU, or its parameters are invalid).  Events with c_e >= I_s keep span s's counters and are BEYOND.  A map update
+ *      whose own event is BEYOND is ignored.
+ *   7. MAP, PREDICTION, ALGORITHM, TALLIES: the follow stage's rules 5 to 7 over the final counters, which rise across spans
+ *      (B_(s+1) = I_s); tallies and the #1 / #2 choice run over all spans.  n_gap counts GAP events; n_before + n_gap + n_on +
+ *      n_off + n_beyond is the connection's events, and the n_events of its spans sum to n_on + n_off.  A packet's span is the
+ *      span whose counting gave its counter; for an EARLY event the span it lies in front of.  kind is PARAM_UPDATE for every
+ *      VALID param update in a counted event, and n_param_updates counts those.
+ * With max_updates == 0 every field a record shares with the follow stage's equals it (flags but for CAPPED and REFUSED); for any
+ * max_updates, an event of span 0 that the follow stage leaves COUNTED carries the same values.
+ * LIMITS: the first counter of a later span is exact while WinSize' * unit_bits + 4 * jitter_bits < P_(s+1) and the events
+ * deviate by at most jitter_bits; it also inherits A_L's deviation, and any drift over I_s - c_L intervals when the events just
+ * before the instant are missed.  An update whose PDU is seen only behind LL_START_ENC_REQ is never read; LL_PAUSE_ENC is not
+ * tracked; more than 16 updates are not followed. */
+#define BTBBX_LE_SPAN_CAPPED   32u      /* btbbx_le_span.flags, beside the BTBBX_LE_FOLLOW_* values */
+#define BTBBX_LE_SPAN_REFUSED  64u
+#define BTBBX_LE_STATE_GAP     3u       /* btbbx_le_span_pkt.state, beside COUNTED / BEFORE / BEYOND */
+
+typedef struct btbbx_le_span {       /* 56 bytes, one per stored connection, parallel to conns / tracks / seeds */
+	uint64_t map;                /* the map in force at the last predicted event; the seed's map without one */
+	uint32_t counter_first;      /* low 32 bits of c_(f_0); 0 unless COUNTED */
+	uint32_t stop;               /* low 32 bits of stop */
+	uint32_t n_before, n_on, n_off, n_beyond, n_gap;   /* events */
+	uint32_t n_control, n_map_updates, n_param_updates; /* members */
+	uint32_t n_spans;
+	uint16_t interval;           /* of the last span */
+	uint8_t  algorithm;          /* 1 or 2 */
+	uint8_t  flags;
+} btbbx_le_span;                     /* a connection that is not SEEDED: 56 zero bytes */
+
+typedef struct btbbx_le_span_pkt {   /* 16 bytes, one per candidate, parallel to the sorted candidate list */
+	uint32_t counter;            /* low 32 bits of its event's connEventCounter; 0 for a BEFORE or GAP event */
+	uint16_t epoch, span;
+	uint8_t  kind, opcode;       /* opcode: 0xff unless CONTROL and parsed */
+	uint8_t  expected, on_hop, state;
+	uint8_t  applied;            /* 1: the parameter update that opened a span */
+	uint8_t  reserved[2];        /* written as 0 */
+} btbbx_le_span_pkt;                 /* a candidate that is no member of a stored connection: sixteen 0xff bytes */
+
+typedef struct btbbx_le_span_rec {   /* 40 bytes; span s of connection g at index g * (max_updates + 1) + s */
+	uint64_t origin;             /* T_s */
+	uint32_t base;               /* low 32 bits of B_s */
+	uint32_t first_event;        /* f_s within the connection, 0xffffffff without one */
+	uint32_t n_events;           /* the span's events that are COUNTED and not BEYOND */
+	uint32_t pdu;                /* list index of the applied PDU, 0xffffffff for span 0 */
+	uint16_t interval, win_offset, latency, timeout;   /* span 0: the seed's */
+	uint8_t  win_size;
+	uint8_t  flags;              /* bit 0: the span exists */
+	uint8_t  reserved[6];        /* written as 0 */
+} btbbx_le_span_rec;                 /* a span that does not exist: 40 zero bytes */
+
+/* The arguments of btbbx_le_epoch_device up to jitter_bits, and its promises about them.  max_updates: 0..16.  d_spans[0 .. K),
+ * d_span_pkts[0 .. N) and d_span_recs[0 .. K * (max_updates + 1)) are written, every byte of them, nothing behind them; nothing is
+ * read back and the call is asynchronous on hip_stream.  d_scratch: btbbx_le_span_scratch_bytes(cand_cap, conn_cap, max_updates)
+ * bytes (the follow stage's and about 16 per candidate, 96 + 4 * (max_updates + 1) per connection).  The count of launches
+ * depends on max_updates -- six per round, max_updates + 1 rounds -- and on conn_cap through one radix pass per byte of it, never
+ * on the data.  BTBBX_E_ARG, before any launch: max_updates above 16, the follow stage's conditions, a record pointer that is not
+ * 8-byte aligned.  cand_cap == 0 or conn_cap == 0 succeeds and writes nothing. */
+size_t btbbx_le_span_scratch_bytes(uint32_t cand_cap, uint32_t conn_cap, uint32_t max_updates);
+int btbbx_le_span_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			 const uint16_t *d_phys_channel,
+			 const btbbx_le_cand *d_cands, const uint32_t *d_cand_count, uint32_t cand_cap,
+			 const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
+			 const btbbx_le_track *d_tracks, const btbbx_le_track_pkt *d_pkts, const btbbx_le_seed *d_seeds,
+			 uint32_t unit_bits, uint32_t jitter_bits, uint32_t max_updates,
+			 btbbx_le_span *d_spans, btbbx_le_span_pkt *d_span_pkts, btbbx_le_span_rec *d_span_recs,
+			 void *d_scratch, size_t scratch_bytes, void *hip_stream);
+
+/* Host wrapper: btbbx_le_epoch_host's chain -- the advertising scan, discovery, tracking and seed -- with the span stage behind
+ * the seed stage.  Its arguments up to seeds and its return value; spans: conn_cap records, span_recs: conn_cap * (max_updates +
+ * 1), span_pkts (may be NULL): cand_cap.  BTBBX_E_ARG: max_updates above 16, the follow wrapper's conditions, spans or span_recs
+ * NULL with conn_cap != 0. */
+int64_t btbbx_le_span_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			   uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+			   btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+			   uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+			   int adv_errors, btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_seed *seeds,
+			   uint32_t max_updates, btbbx_le_span *spans, btbbx_le_span_pkt *span_pkts, btbbx_le_span_rec *span_recs);
 
 /* ---- hop selection and CLK1-27 reversal ------------------------- */
 #define BTBBX_SEQUENCE_LENGTH 134217728u   /* values of CLK1-27, bluetooth_piconet.h:102 */

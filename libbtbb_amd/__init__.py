@@ -128,6 +128,19 @@ LE_FOLLOW_DTYPE = np.dtype([("map", "<u8"), ("counter_first", "<u4"), ("stop", "
 LE_FOLLOW_PKT_DTYPE = np.dtype([("counter", "<u4"), ("epoch", "<u2"), ("kind", "u1"), ("opcode", "u1"), ("expected", "u1"),
                                 ("on_hop", "u1"), ("state", "u1"), ("reserved", "u1")])
 assert LE_SEED_DTYPE.itemsize == 56 and LE_FOLLOW_DTYPE.itemsize == 48 and LE_FOLLOW_PKT_DTYPE.itemsize == 12
+# LE following through connection parameter updates (include/btbbx.h btbbx_le_span / btbbx_le_span_pkt / btbbx_le_span_rec; le_span.h
+# checks the C layout with static_asserts); the flags and states stand beside the LE_FOLLOW_* / LE_STATE_* values
+LE_SPAN_CAPPED, LE_SPAN_REFUSED = 32, 64
+LE_STATE_GAP = 3
+LE_SPAN_DTYPE = np.dtype([("map", "<u8"), ("counter_first", "<u4"), ("stop", "<u4"), ("n_before", "<u4"), ("n_on", "<u4"),
+                          ("n_off", "<u4"), ("n_beyond", "<u4"), ("n_gap", "<u4"), ("n_control", "<u4"), ("n_map_updates", "<u4"),
+                          ("n_param_updates", "<u4"), ("n_spans", "<u4"), ("interval", "<u2"), ("algorithm", "u1"), ("flags", "u1")])
+LE_SPAN_PKT_DTYPE = np.dtype([("counter", "<u4"), ("epoch", "<u2"), ("span", "<u2"), ("kind", "u1"), ("opcode", "u1"),
+                              ("expected", "u1"), ("on_hop", "u1"), ("state", "u1"), ("applied", "u1"), ("reserved", "u1", (2,))])
+LE_SPAN_REC_DTYPE = np.dtype([("origin", "<u8"), ("base", "<u4"), ("first_event", "<u4"), ("n_events", "<u4"), ("pdu", "<u4"),
+                              ("interval", "<u2"), ("win_offset", "<u2"), ("latency", "<u2"), ("timeout", "<u2"), ("win_size", "u1"),
+                              ("flags", "u1"), ("reserved", "u1", (6,))])
+assert LE_SPAN_DTYPE.itemsize == 56 and LE_SPAN_PKT_DTYPE.itemsize == 16 and LE_SPAN_REC_DTYPE.itemsize == 40
 
 # one surveyed piconet (include/btbbx.h btbbx_survey_rec; survey.hip checks the C layout with static_asserts)
 SURVEY_DTYPE = np.dtype([("lap", "<u4"), ("flags", "<u4"), ("uap", "u1"), ("clk_offset", "u1"), ("used_channels", "u1"),
@@ -230,6 +243,11 @@ SIGNATURES = {
                                          _vp, C.c_size_t, _vp]),
     "btbbx_le_epoch_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
                                          C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "btbbx_le_span_scratch_bytes": (C.c_size_t, [_u32, _u32, _u32]),
+    "btbbx_le_span_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp,
+                                       _vp, _vp, _vp, C.c_size_t, _vp]),
+    "btbbx_le_span_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
+                                       C.c_int, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
     "btbbx_survey_scratch_bytes": (C.c_size_t, [_u32]),
     "btbbx_survey_hits_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp,
                                            _vp, C.c_size_t, _vp]),
@@ -549,6 +567,42 @@ def le_follow(words, search_bits, phys_channels, max_len=27, min_count=2, n_stre
     nc, nk = min(n, conn_cap), min(n_cands.value, cand_cap)
     return (conns[:nc].copy(), cands[:nk].copy(), tracks[:nc].copy(), pkts[:nk].copy(), seeds[:nc].copy(), follows[:nc].copy(),
             follow_pkts[:nk].copy())
+
+
+def le_span(words, search_bits, phys_channels, max_len=27, min_count=2, n_streams=1, pitch_words=None, n_words=None,
+            unit_bits=1250, ifs_bits=200, jitter_bits=50, flags=LE_TRACK_REMAP, adv_errors=0, conn_cap=1 << 12, cand_cap=1 << 20,
+            truncate=False, max_updates=4):
+    """le_follow's chain with the span stage in the follow stage's place (include/btbbx.h btbbx_le_span_device): counters, map
+    updates and the hop check carried through up to max_updates (0..16) connection parameter updates per connection.  le_follow's
+    parameters.  Returns (conns, cands, tracks, pkts, seeds, spans, span_pkts, span_recs): le_follow's arrays up to seeds,
+    LE_SPAN_DTYPE records parallel to conns, LE_SPAN_PKT_DTYPE records parallel to cands and LE_SPAN_REC_DTYPE records of shape
+    (connections, max_updates + 1)."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if pitch_words is None:
+        pitch_words = len(words) // n_streams
+    if n_words is None:
+        n_words = pitch_words
+    assert n_words <= pitch_words and (n_streams - 1) * pitch_words + n_words <= len(words)
+    phys = np.ascontiguousarray(np.broadcast_to(np.asarray(phys_channels, dtype=np.uint16), (n_streams,)))
+    per = min(int(max_updates), 16) + 1
+    conns = np.empty(max(conn_cap, 1), dtype=LE_CONN_DTYPE)
+    tracks = np.empty(max(conn_cap, 1), dtype=LE_TRACK_DTYPE)
+    seeds = np.empty(max(conn_cap, 1), dtype=LE_SEED_DTYPE)
+    spans = np.empty(max(conn_cap, 1), dtype=LE_SPAN_DTYPE)
+    span_recs = np.empty((max(conn_cap, 1), per), dtype=LE_SPAN_REC_DTYPE)
+    cands = np.empty(max(cand_cap, 1), dtype=LE_CAND_DTYPE)
+    pkts = np.empty(max(cand_cap, 1), dtype=LE_TRACK_PKT_DTYPE)
+    span_pkts = np.empty(max(cand_cap, 1), dtype=LE_SPAN_PKT_DTYPE)
+    n_cands = C.c_uint64(0)
+    n = check(lib().btbbx_le_span_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, _ptr(phys), max_len, min_count,
+                                       _ptr(conns), conn_cap, _ptr(cands), cand_cap, C.byref(n_cands), unit_bits, ifs_bits, jitter_bits,
+                                       flags, adv_errors, _ptr(tracks), _ptr(pkts), _ptr(seeds), max_updates, _ptr(spans), _ptr(span_pkts),
+                                       _ptr(span_recs)), "btbbx_le_span_host")
+    if (n > conn_cap or n_cands.value > cand_cap) and not truncate:
+        raise BtbbError("buffers too small: %d connections > %d or %d candidates > %d" % (n, conn_cap, n_cands.value, cand_cap))
+    nc, nk = min(n, conn_cap), min(n_cands.value, cand_cap)
+    return (conns[:nc].copy(), cands[:nk].copy(), tracks[:nc].copy(), pkts[:nk].copy(), seeds[:nc].copy(), spans[:nc].copy(),
+            span_pkts[:nk].copy(), span_recs[:nc].copy())
 
 
 class DeviceBuffer:

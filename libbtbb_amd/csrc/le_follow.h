@@ -902,26 +902,58 @@ static LfAdvLayout le_follow_adv_layout(uint32_t cap)
 }
 
 static thread_local uint32_t lf_adv_guess;             // the advertising hits the tail of the running call has room for
+static thread_local int lf_span_updates = -1;          // max_updates of the running call when the span stage (le_span.h) ends the chain
 
-// behind the discovery's block: the tracking's part as btbbx_le_track_host lays it out, the seeds, this stage's scratch and
+// what btbbx_le_span_host hands to the chain in place of the follow stage's records; the stage itself is le_span.h's
+struct LfSpanOut {
+	uint32_t max_updates;
+	btbbx_le_span *spans;
+	btbbx_le_span_pkt *span_pkts;
+	btbbx_le_span_rec *span_recs;
+};
+static size_t le_span_scratch_total(uint32_t cand_cap, uint32_t conn_cap, uint32_t max_updates);
+static int le_span_launch(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, const btbbx_le_cand *d_cands,
+			  const uint32_t *d_count, uint32_t cap, const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
+			  const btbbx_le_track_pkt *d_pkts, const btbbx_le_seed *d_seeds, uint32_t unit_bits, uint32_t jitter_bits,
+			  uint32_t max_updates, btbbx_le_span *d_spans, btbbx_le_span_pkt *d_spkts, btbbx_le_span_rec *d_recs, void *d_scratch,
+			  hipStream_t q);
+
+// the last stage's scratch, per-connection and per-candidate records and, for the span stage, its span records
+static void le_follow_last_sizes(uint32_t dev_cap, uint32_t dev_conns, size_t &scratch, size_t &per_conn, size_t &per_cand, size_t &recs)
+{
+	if (lf_span_updates < 0) {
+		scratch = le_follow_layout(dev_cap, dev_conns).total;
+		per_conn = (size_t)dev_conns * sizeof(btbbx_le_follow);
+		per_cand = (size_t)dev_cap * sizeof(btbbx_le_follow_pkt);
+		recs = 0;
+	} else {
+		scratch = le_span_scratch_total(dev_cap, dev_conns, (uint32_t)lf_span_updates);
+		per_conn = (size_t)dev_conns * sizeof(btbbx_le_span);
+		per_cand = (size_t)dev_cap * sizeof(btbbx_le_span_pkt);
+		recs = (size_t)dev_conns * ((size_t)lf_span_updates + 1) * sizeof(btbbx_le_span_rec);
+	}
+}
+
+// behind the discovery's block: the tracking's part as btbbx_le_track_host lays it out, the seeds, the last stage's scratch and
 // records, the advertising scan's block
 static size_t le_follow_host_tail(uint32_t dev_cap, uint32_t dev_conns)
 {
-	return le_track_host_tail(dev_cap, dev_conns) + ld_up((size_t)dev_conns * sizeof(btbbx_le_seed)) +
-	       ld_up(le_follow_layout(dev_cap, dev_conns).total) + ld_up((size_t)dev_conns * sizeof(btbbx_le_follow)) +
-	       ld_up((size_t)dev_cap * sizeof(btbbx_le_follow_pkt)) + le_follow_adv_layout(lf_adv_guess).total;
+	size_t scratch, per_conn, per_cand, recs;
+	le_follow_last_sizes(dev_cap, dev_conns, scratch, per_conn, per_cand, recs);
+	return le_track_host_tail(dev_cap, dev_conns) + ld_up((size_t)dev_conns * sizeof(btbbx_le_seed)) + ld_up(scratch) + ld_up(per_conn) +
+	       ld_up(per_cand) + ld_up(recs) + le_follow_adv_layout(lf_adv_guess).total;
 }
 
 // Host wrapper: btbbx_le_track_host's chain; the advertising scan over the same device copy of the capture, ordered and decoded;
 // the seed stage and the follow stage behind the tracking, all on one stream; copy out.
-extern "C" int64_t btbbx_le_epoch_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
-					uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
-					btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
-					uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
-					int adv_errors, btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_seed *seeds,
-					btbbx_le_follow *follows, btbbx_le_follow_pkt *follow_pkts)
+// span: the span stage ends the chain and its records are copied out; NULL: the follow stage and follows / follow_pkts
+static int64_t le_follow_host_chain(const char *who, const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				    uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+				    btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+				    uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+				    int adv_errors, btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_seed *seeds,
+				    btbbx_le_follow *follows, btbbx_le_follow_pkt *follow_pkts, const LfSpanOut *span)
 {
-	const char *who = "btbbx_le_epoch_host";
 	int rc = le_disc_check_args(who, n_words, pitch_words, n_streams, search_bits, max_len);
 	if (rc)
 		return rc;
@@ -931,7 +963,8 @@ extern "C" int64_t btbbx_le_epoch_host(const uint64_t *words, uint64_t n_words, 
 	rc = le_track_check_args(who, n_streams, unit_bits, jitter_bits);
 	if (rc)
 		return rc;
-	if (!words || !phys_channel || ((!conns || !tracks || !seeds || !follows) && conn_cap) || (!cands && cand_cap)) {
+	if (!words || !phys_channel || ((!conns || !tracks || !seeds || (span ? !span->spans || !span->span_recs : !follows)) && conn_cap) ||
+	    (!cands && cand_cap)) {
 		set_error("%s: null pointer", who);
 		return BTBBX_E_ARG;
 	}
@@ -947,6 +980,7 @@ extern "C" int64_t btbbx_le_epoch_host(const uint64_t *words, uint64_t n_words, 
 	// (a 40-bit pattern with up to four errors matches noise at one offset in ten million)
 	const uint64_t guess = search_bits / 16384 * n_streams + 4096;
 	lf_adv_guess = guess > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)guess;
+	lf_span_updates = span ? (int)span->max_updates : -1;
 	LeDiscHostRun r;
 	rc = le_disc_host_chain(words, n_words, pitch_words, n_streams, search_bits, phys_channel, max_len, min_count, conn_cap,
 				le_follow_host_tail, &r);
@@ -965,9 +999,13 @@ extern "C" int64_t btbbx_le_epoch_host(const uint64_t *words, uint64_t n_words, 
 		char *own = r.tail + le_track_host_tail(r.dev_cap, r.dev_conns);
 		btbbx_le_seed *d_seeds = (btbbx_le_seed *)own;
 		char *fscratch = own + ld_up((size_t)r.dev_conns * sizeof(btbbx_le_seed));
-		btbbx_le_follow *d_follows = (btbbx_le_follow *)(fscratch + ld_up(le_follow_layout(r.dev_cap, r.dev_conns).total));
-		btbbx_le_follow_pkt *d_fpkts = (btbbx_le_follow_pkt *)((char *)d_follows + ld_up((size_t)r.dev_conns * sizeof(btbbx_le_follow)));
-		char *ablock = (char *)d_fpkts + ld_up((size_t)r.dev_cap * sizeof(btbbx_le_follow_pkt));
+		size_t last_scratch, last_conn, last_cand, last_recs;
+		le_follow_last_sizes(r.dev_cap, r.dev_conns, last_scratch, last_conn, last_cand, last_recs);
+		char *d_per_conn = fscratch + ld_up(last_scratch), *d_per_cand = d_per_conn + ld_up(last_conn);
+		char *d_recs = d_per_cand + ld_up(last_cand);
+		btbbx_le_follow *d_follows = (btbbx_le_follow *)d_per_conn;
+		btbbx_le_follow_pkt *d_fpkts = (btbbx_le_follow_pkt *)d_per_cand;
+		char *ablock = d_recs + ld_up(last_recs);
 		// the advertising scan, repeated with room for every match when the block was too small
 		uint32_t adv_cap = lf_adv_guess, adv_count = 0;
 		for (int pass = 0; pass < 2; pass++) {
@@ -1005,9 +1043,13 @@ extern "C" int64_t btbbx_le_epoch_host(const uint64_t *words, uint64_t n_words, 
 		if (!rc)
 			rc = btbbx_le_seed_device(d_adv, (uint32_t *)ablock, adv_cap, r.d_conns, r.d_conn_count, r.dev_conns, d_tracks, unit_bits,
 						  d_seeds, q);
-		if (!rc)
+		if (!rc && !span)
 			rc = le_follow_launch(r.d_words, n_words, pitch_words, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count,
 					      r.dev_conns, d_pkts, d_seeds, unit_bits, jitter_bits, d_follows, d_fpkts, fscratch, q);
+		if (!rc && span)
+			rc = le_span_launch(r.d_words, n_words, pitch_words, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count,
+					    r.dev_conns, d_pkts, d_seeds, unit_bits, jitter_bits, span->max_updates, (btbbx_le_span *)d_per_conn,
+					    (btbbx_le_span_pkt *)d_per_cand, (btbbx_le_span_rec *)d_recs, fscratch, q);
 		hipError_t e = hipSuccess;
 		auto out = [&](void *dst, const void *src, size_t bytes) {
 			if (!rc && e == hipSuccess && dst && bytes)
@@ -1016,9 +1058,16 @@ extern "C" int64_t btbbx_le_epoch_host(const uint64_t *words, uint64_t n_words, 
 		out(conns, r.d_conns, (size_t)nc * sizeof(btbbx_le_conn));
 		out(tracks, d_tracks, (size_t)nc * sizeof(btbbx_le_track));
 		out(seeds, d_seeds, (size_t)nc * sizeof(btbbx_le_seed));
-		out(follows, d_follows, (size_t)nc * sizeof(btbbx_le_follow));
 		out(pkts, d_pkts, (size_t)nk * sizeof(btbbx_le_track_pkt));
-		out(follow_pkts, d_fpkts, (size_t)nk * sizeof(btbbx_le_follow_pkt));
+		if (span) {
+			// (the device records of connection g stand at g * (max_updates + 1), whatever dev_conns is: the first nc of them)
+			out(span->spans, d_per_conn, (size_t)nc * sizeof(btbbx_le_span));
+			out(span->span_pkts, d_per_cand, (size_t)nk * sizeof(btbbx_le_span_pkt));
+			out(span->span_recs, d_recs, (size_t)nc * (span->max_updates + 1) * sizeof(btbbx_le_span_rec));
+		} else {
+			out(follows, d_follows, (size_t)nc * sizeof(btbbx_le_follow));
+			out(follow_pkts, d_fpkts, (size_t)nk * sizeof(btbbx_le_follow_pkt));
+		}
 		out(cands, r.d_cands, (size_t)nk * sizeof(btbbx_le_cand));
 		const hipError_t e2 = hipStreamSynchronize(q);           // (before the spill block goes, whatever happened)
 		if (spill)
@@ -1026,7 +1075,7 @@ extern "C" int64_t btbbx_le_epoch_host(const uint64_t *words, uint64_t n_words, 
 		if (rc)
 			return rc;
 		if (e != hipSuccess || e2 != hipSuccess)
-			return hip_fail(e != hipSuccess ? e : e2, "btbbx_le_epoch_host: copy out");
+			return hip_fail(e != hipSuccess ? e : e2, span ? "btbbx_le_span_host: copy out" : "btbbx_le_epoch_host: copy out");
 		return (int64_t)r.n_conns;
 	}
 	if (nk) {
@@ -1034,8 +1083,22 @@ extern "C" int64_t btbbx_le_epoch_host(const uint64_t *words, uint64_t n_words, 
 			memset(pkts, 0xff, (size_t)nk * sizeof(btbbx_le_track_pkt));    // (no connection stored: no candidate is a member)
 		if (follow_pkts)
 			memset(follow_pkts, 0xff, (size_t)nk * sizeof(btbbx_le_follow_pkt));
+		if (span && span->span_pkts)
+			memset(span->span_pkts, 0xff, (size_t)nk * sizeof(btbbx_le_span_pkt));
 		HIP_TRY(hipMemcpyAsync(cands, r.d_cands, (size_t)nk * sizeof(btbbx_le_cand), hipMemcpyDeviceToHost, q));
 	}
 	HIP_TRY(hipStreamSynchronize(q));
 	return (int64_t)r.n_conns;
+}
+
+extern "C" int64_t btbbx_le_epoch_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+					uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+					btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+					uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+					int adv_errors, btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_seed *seeds,
+					btbbx_le_follow *follows, btbbx_le_follow_pkt *follow_pkts)
+{
+	return le_follow_host_chain("btbbx_le_epoch_host", words, n_words, pitch_words, n_streams, search_bits, phys_channel, max_len, min_count,
+				    conns, conn_cap, cands, cand_cap, n_cands_out, unit_bits, ifs_bits, jitter_bits, flags, adv_errors, tracks, pkts,
+				    seeds, follows, follow_pkts, nullptr);
 }
