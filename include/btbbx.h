@@ -930,6 +930,118 @@ int64_t btbbx_le_span_host(const uint64_t *words, uint64_t n_words, uint64_t pit
 			   int adv_errors, btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_seed *seeds,
 			   uint32_t max_updates, btbbx_le_span *spans, btbbx_le_span_pkt *span_pkts, btbbx_le_span_rec *span_recs);
 
+/* ---- LE data extraction: roles, retransmission filter, L2CAP reassembly --------------------
+ * Every stage above ends in a verdict about a connection; this one hands out what the connection carried.  Behind the tracking, on
+ * the device, for every packet the role of its sender, its SN / NESN / MD bits and whether it is new or a retransmission; for every
+ * direction of every connection the L2CAP messages reassembled from their fragments, their dewhitened octets packed into one
+ * buffer and a record per message.  It needs no CONNECT_IND, so it serves promiscuously discovered and encrypted connections as
+ * well (encrypted octets come out as ciphertext), and it changes nothing of its input.
+ *
+ * The input is what btbbx_le_discover_group_device and btbbx_le_track_device left, plus the streams.  N = min(*d_cand_count,
+ * cand_cap), K = min(*d_conn_count, conn_cap).  Membership is the follow stage's, promises and guards included: candidate i < N is a
+ * member of g < K iff cands[i].conn == g and pkts[i].rank != 0xffffffff (and first + rank, first + event lie within N).  Time order
+ * is rank, events are pkts[i].event, an event's counter is the tracking's stored counter.  A list from elsewhere keeps, besides the
+ * follow stage's promises, the grouping's order: conns[g].first ascends with g.  All arithmetic is integer arithmetic; offsets and
+ * octet counts are 64 bits wide.
+ *   1. HEADER.  h0 = cands[i].header0, L = cands[i].length; llid = h0 & 3, nesn = (h0 >> 2) & 1, sn = (h0 >> 3) & 1, md = (h0 >> 4) & 1.
+ *   2. HEAD events.  Event e of a connection is HEAD iff e == 0 or its stored counter differs from that of event e - 1.  (By the
+ *      tracking's rule 3 a packet lost inside an event splits the event, by its rule 5 the tail then carries the same counter: such a
+ *      tail is not HEAD.  A connection that is not TIMED has every counter 0: only its event 0 is HEAD.)
+ *   3. ROLE.  A member of a HEAD event has role = (its rank - the rank of the event's first member) & 1: 0 CENTRAL, 1 PERIPHERAL
+ *      (inside an event the tracking admits no gap beyond ifs_bits, so packets alternate).  A member of any other event is UNKNOWN
+ *      (role 2) and takes no part in rules 4 to 6.
+ *   4. NEW / RETRANSMIT.  Per (connection, role in {0, 1}) in time order a member is NEW iff it is the first of its role or its sn
+ *      differs from the sn of the previous member of the SAME role; otherwise it is RETRANSMIT.
+ *   5. MESSAGES, over NEW members only, per (connection, role).  START iff llid == 2 and L >= 1.  CONTINUATION iff llid == 1 and
+ *      L >= 1: it belongs to the message of the latest START of its (connection, role) before it in time order; without one it is
+ *      ORPHAN.  EMPTY iff llid == 1 and L == 0.  CONTROL iff llid == 3.  Everything else (llid 0, or llid 2 with L == 0) is IGNORED.
+ *      EMPTY, CONTROL and IGNORED members lie between fragments without breaking a message.  A message has n_fragments = 1 + its
+ *      continuations and bytes = the sum of their L; a fragment's pos = the sum of L of the message's earlier fragments.  If the START
+ *      has L >= 4, l2cap_len = LE16 of its dewhitened payload octets 0..1 and cid = LE16 of octets 2..3; otherwise the message is RUNT
+ *      and both are 0xffff.  COMPLETE iff not RUNT and bytes == 4 + l2cap_len; OVERRUN iff not RUNT and bytes > 4 + l2cap_len.
+ *   6. ORDER and BYTES.  Messages are numbered M = 0, 1, ... by (connection, rank of the START) ascending: a connection's messages
+ *      lie next to each other, both roles interleaved in time order.  byte_offset(M) = the sum of bytes of all earlier messages.
+ *      Message M is STORED iff M < msg_cap and byte_offset + bytes <= byte_cap; offsets only grow, so the stored messages are a
+ *      prefix.  For a stored message d_bytes[byte_offset + pos + k] = payload octet k of each fragment: stream bits offset + 56 + 8k
+ *      .. + 7, least significant first, dewhitened with the channel's sequence continued behind the two header octets; bits beyond
+ *      the stream's end read as 0, as in the follow stage's rule 3.  d_msgs[M] is written for M < msg_cap, stored or not.
+ *      *d_msg_count = all messages and *d_byte_count (64 bits) = all their octets: the stage WRITES both, it does not add to them.
+ *      Nothing behind the stored prefix of d_bytes and nothing behind min(count, msg_cap) records of d_msgs is touched.
+ *   7. RECORDS.  Every byte of d_data[0 .. K) and d_data_pkts[0 .. N) is written, nothing behind them.  first_msg of a connection
+ *      without messages is the number of messages of the connections before it; the n_msgs of all connections add up to the count.
+ * LIMITS, which follow from the rules: when the central's packet of an event was not received, the peripheral's first packet is
+ * taken for it; two lost packets of one role in a row make a new packet look like a retransmission; the first event seen may be the
+ * tail of one; connections that are not TIMED yield data only from their first event; an L2CAP header split over fragments (START
+ * with L < 4) is not parsed. */
+#define BTBBX_LE_DATA_START        0u   /* btbbx_le_data_pkt.kind */
+#define BTBBX_LE_DATA_CONTINUATION 1u
+#define BTBBX_LE_DATA_ORPHAN       2u
+#define BTBBX_LE_DATA_EMPTY        3u
+#define BTBBX_LE_DATA_CONTROL      4u
+#define BTBBX_LE_DATA_IGNORED      5u
+#define BTBBX_LE_DATA_RETRANSMIT   6u
+#define BTBBX_LE_DATA_UNKNOWN      7u
+#define BTBBX_LE_ROLE_CENTRAL      0u   /* btbbx_le_data_pkt.role, btbbx_le_msg.role */
+#define BTBBX_LE_ROLE_PERIPHERAL   1u
+#define BTBBX_LE_ROLE_UNKNOWN      2u
+#define BTBBX_LE_MSG_COMPLETE      1u   /* btbbx_le_msg.flags */
+#define BTBBX_LE_MSG_OVERRUN       2u
+#define BTBBX_LE_MSG_RUNT          4u
+#define BTBBX_LE_MSG_STORED        8u
+
+typedef struct btbbx_le_data_pkt {   /* 12 bytes, parallel to the sorted candidate list; no member: twelve 0xff bytes */
+	uint32_t msg;                /* its message, 0xffffffff unless START or CONTINUATION */
+	uint32_t pos;                /* its first octet within the message; 0 without one */
+	uint8_t  role;               /* 0 central, 1 peripheral, 2 unknown */
+	uint8_t  kind;               /* START, CONTINUATION, ORPHAN, EMPTY, CONTROL, IGNORED, RETRANSMIT, UNKNOWN */
+	uint8_t  bits;               /* sn | nesn << 1 | md << 2 */
+	uint8_t  reserved;           /* 0 */
+} btbbx_le_data_pkt;
+typedef struct btbbx_le_data {       /* 48 bytes, parallel to conns; a connection without a member: zeros */
+	uint64_t bytes;              /* of its messages */
+	uint32_t first_msg, n_msgs, n_complete;
+	uint32_t n_central, n_peripheral, n_unknown;     /* members by role */
+	uint32_t n_retransmit, n_orphan, n_control, n_empty;
+} btbbx_le_data;
+typedef struct btbbx_le_msg {        /* 32 bytes */
+	uint64_t byte_offset;
+	uint32_t conn, start;        /* start: list index of the START */
+	uint32_t n_fragments, bytes;
+	uint16_t l2cap_len, cid;
+	uint8_t  role, flags;        /* COMPLETE 1, OVERRUN 2, RUNT 4, STORED 8 */
+	uint8_t  reserved[2];        /* written as 0 */
+} btbbx_le_msg;
+
+/* d_tracks and d_phys_channel are taken for the chain's sake and not read: everything the stage needs of them stands in d_pkts.
+ * Nothing is read back and the call is asynchronous on hip_stream.  d_scratch: btbbx_le_data_scratch_bytes(cand_cap, conn_cap)
+ * bytes (about 52 per candidate, 32 per 2048 candidates and 96 per connection), 16-byte aligned.  The count of launches, 18, depends on nothing.
+ * BTBBX_E_ARG, before any launch: a null pointer (d_msgs may be null with msg_cap 0, d_bytes with byte_cap 0), n_streams == 0,
+ * n_words == 0 or above 2^42, pitch_words < n_words with more than one stream, a scratch that is too small or not 16-byte aligned,
+ * words, records, d_bytes or d_byte_count that are not 8-byte aligned (d_data_pkts, whose records are 12 bytes, and the counters:
+ * 4; the channels: 2).  cand_cap == 0 or conn_cap == 0 succeeds and writes only the two counts, as 0. */
+size_t btbbx_le_data_scratch_bytes(uint32_t cand_cap, uint32_t conn_cap);
+int btbbx_le_data_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			 const uint16_t *d_phys_channel,
+			 const btbbx_le_cand *d_cands, const uint32_t *d_cand_count, uint32_t cand_cap,
+			 const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
+			 const btbbx_le_track *d_tracks, const btbbx_le_track_pkt *d_pkts,
+			 btbbx_le_data *d_data, btbbx_le_data_pkt *d_data_pkts, btbbx_le_msg *d_msgs, uint32_t msg_cap,
+			 uint32_t *d_msg_count, uint8_t *d_bytes, uint64_t byte_cap, uint64_t *d_byte_count,
+			 void *d_scratch, size_t scratch_bytes, void *hip_stream);
+
+/* Host wrapper: btbbx_le_track_host's chain with this stage behind the tracking on the same stream.  The tracking wrapper's
+ * arguments and return value; data: conn_cap records, parallel to conns; data_pkts (may be NULL): cand_cap records, parallel to
+ * cands; msgs: msg_cap records, bytes: byte_cap octets (either may be NULL with its cap 0); *n_msgs_out and *n_bytes_out (either may
+ * be NULL) = all messages and all their octets.  Of msgs the first min(*n_msgs_out, msg_cap) records are written, of bytes the
+ * stored prefix.  BTBBX_E_ARG: the tracking wrapper's conditions, data NULL with conn_cap != 0, msgs or bytes NULL with a cap. */
+int64_t btbbx_le_data_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			   uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+			   btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+			   uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+			   btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_data *data, btbbx_le_data_pkt *data_pkts,
+			   btbbx_le_msg *msgs, uint64_t msg_cap, uint64_t *n_msgs_out, uint8_t *bytes, uint64_t byte_cap,
+			   uint64_t *n_bytes_out);
+
 /* ---- hop selection and CLK1-27 reversal ------------------------- */
 #define BTBBX_SEQUENCE_LENGTH 134217728u   /* values of CLK1-27, bluetooth_piconet.h:102 */
 

@@ -141,6 +141,19 @@ LE_SPAN_REC_DTYPE = np.dtype([("origin", "<u8"), ("base", "<u4"), ("first_event"
                               ("interval", "<u2"), ("win_offset", "<u2"), ("latency", "<u2"), ("timeout", "<u2"), ("win_size", "u1"),
                               ("flags", "u1"), ("reserved", "u1", (6,))])
 assert LE_SPAN_DTYPE.itemsize == 56 and LE_SPAN_PKT_DTYPE.itemsize == 16 and LE_SPAN_REC_DTYPE.itemsize == 40
+# LE data extraction (include/btbbx.h btbbx_le_data / btbbx_le_data_pkt / btbbx_le_msg; le_data.h checks the C layout with
+# static_asserts): a packet's kind, its sender's role, a message's flags
+(LE_DATA_START, LE_DATA_CONTINUATION, LE_DATA_ORPHAN, LE_DATA_EMPTY, LE_DATA_CONTROL, LE_DATA_IGNORED, LE_DATA_RETRANSMIT,
+ LE_DATA_UNKNOWN) = range(8)
+LE_ROLE_CENTRAL, LE_ROLE_PERIPHERAL, LE_ROLE_UNKNOWN = 0, 1, 2
+LE_MSG_COMPLETE, LE_MSG_OVERRUN, LE_MSG_RUNT, LE_MSG_STORED = 1, 2, 4, 8
+LE_DATA_DTYPE = np.dtype([("bytes", "<u8"), ("first_msg", "<u4"), ("n_msgs", "<u4"), ("n_complete", "<u4"), ("n_central", "<u4"),
+                          ("n_peripheral", "<u4"), ("n_unknown", "<u4"), ("n_retransmit", "<u4"), ("n_orphan", "<u4"),
+                          ("n_control", "<u4"), ("n_empty", "<u4")])
+LE_DATA_PKT_DTYPE = np.dtype([("msg", "<u4"), ("pos", "<u4"), ("role", "u1"), ("kind", "u1"), ("bits", "u1"), ("reserved", "u1")])
+LE_MSG_DTYPE = np.dtype([("byte_offset", "<u8"), ("conn", "<u4"), ("start", "<u4"), ("n_fragments", "<u4"), ("bytes", "<u4"),
+                         ("l2cap_len", "<u2"), ("cid", "<u2"), ("role", "u1"), ("flags", "u1"), ("reserved", "u1", (2,))])
+assert LE_DATA_DTYPE.itemsize == 48 and LE_DATA_PKT_DTYPE.itemsize == 12 and LE_MSG_DTYPE.itemsize == 32
 
 # one surveyed piconet (include/btbbx.h btbbx_survey_rec; survey.hip checks the C layout with static_asserts)
 SURVEY_DTYPE = np.dtype([("lap", "<u4"), ("flags", "<u4"), ("uap", "u1"), ("clk_offset", "u1"), ("used_channels", "u1"),
@@ -248,6 +261,11 @@ SIGNATURES = {
                                        _vp, _vp, _vp, C.c_size_t, _vp]),
     "btbbx_le_span_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
                                        C.c_int, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "btbbx_le_data_scratch_bytes": (C.c_size_t, [_u32, _u32]),
+    "btbbx_le_data_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _vp,
+                                       _vp, _u64, _vp, _vp, C.c_size_t, _vp]),
+    "btbbx_le_data_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
+                                       _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),
     "btbbx_survey_scratch_bytes": (C.c_size_t, [_u32]),
     "btbbx_survey_hits_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp,
                                            _vp, C.c_size_t, _vp]),
@@ -603,6 +621,46 @@ def le_span(words, search_bits, phys_channels, max_len=27, min_count=2, n_stream
     nc, nk = min(n, conn_cap), min(n_cands.value, cand_cap)
     return (conns[:nc].copy(), cands[:nk].copy(), tracks[:nc].copy(), pkts[:nk].copy(), seeds[:nc].copy(), spans[:nc].copy(),
             span_pkts[:nk].copy(), span_recs[:nc].copy())
+
+
+def le_data(words, search_bits, phys_channels, max_len=27, min_count=2, n_streams=1, pitch_words=None, n_words=None,
+            unit_bits=1250, ifs_bits=200, jitter_bits=50, flags=LE_TRACK_REMAP, conn_cap=1 << 12, cand_cap=1 << 20, truncate=False,
+            msg_cap=1 << 16, byte_cap=1 << 22):
+    """le_track, then the data of every connection it stored (include/btbbx.h btbbx_le_data_device): every packet's role, SN / NESN /
+    MD bits and whether it is new or a retransmission, and the L2CAP messages of either direction reassembled from their fragments.
+    le_track's parameters; msg_cap and byte_cap: the message records and payload octets to keep (without truncate, more of either
+    raises).  Returns (conns, cands, tracks, pkts, data, data_pkts, msgs, payload): le_track's four arrays, LE_DATA_DTYPE records
+    parallel to conns, LE_DATA_PKT_DTYPE records parallel to cands, the LE_MSG_DTYPE records and the uint8 buffer their byte_offset
+    points into, cut to the stored messages."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if pitch_words is None:
+        pitch_words = len(words) // n_streams
+    if n_words is None:
+        n_words = pitch_words
+    assert n_words <= pitch_words and (n_streams - 1) * pitch_words + n_words <= len(words)
+    phys = np.ascontiguousarray(np.broadcast_to(np.asarray(phys_channels, dtype=np.uint16), (n_streams,)))
+    conns = np.empty(max(conn_cap, 1), dtype=LE_CONN_DTYPE)
+    tracks = np.empty(max(conn_cap, 1), dtype=LE_TRACK_DTYPE)
+    data = np.empty(max(conn_cap, 1), dtype=LE_DATA_DTYPE)
+    cands = np.empty(max(cand_cap, 1), dtype=LE_CAND_DTYPE)
+    pkts = np.empty(max(cand_cap, 1), dtype=LE_TRACK_PKT_DTYPE)
+    data_pkts = np.empty(max(cand_cap, 1), dtype=LE_DATA_PKT_DTYPE)
+    msgs = np.empty(max(msg_cap, 1), dtype=LE_MSG_DTYPE)
+    payload = np.empty(max(byte_cap, 1), dtype=np.uint8)
+    n_cands, n_msgs, n_bytes = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    n = check(lib().btbbx_le_data_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, _ptr(phys), max_len, min_count,
+                                       _ptr(conns), conn_cap, _ptr(cands), cand_cap, C.byref(n_cands), unit_bits, ifs_bits, jitter_bits,
+                                       flags, _ptr(tracks), _ptr(pkts), _ptr(data), _ptr(data_pkts), _ptr(msgs), msg_cap, C.byref(n_msgs),
+                                       _ptr(payload), byte_cap, C.byref(n_bytes)), "btbbx_le_data_host")
+    if (n > conn_cap or n_cands.value > cand_cap or n_msgs.value > msg_cap or n_bytes.value > byte_cap) and not truncate:
+        raise BtbbError("buffers too small: %d connections > %d, %d candidates > %d, %d messages > %d or %d octets > %d" % (
+            n, conn_cap, n_cands.value, cand_cap, n_msgs.value, msg_cap, n_bytes.value, byte_cap))
+    nc, nk, nm = min(n, conn_cap), min(n_cands.value, cand_cap), min(n_msgs.value, msg_cap)
+    msgs = msgs[:nm].copy()
+    stored = msgs[(msgs["flags"] & LE_MSG_STORED) != 0]
+    kept = int(stored["byte_offset"][-1]) + int(stored["bytes"][-1]) if len(stored) else 0
+    return (conns[:nc].copy(), cands[:nk].copy(), tracks[:nc].copy(), pkts[:nk].copy(), data[:nc].copy(), data_pkts[:nk].copy(), msgs,
+            payload[:kept].copy())
 
 
 class DeviceBuffer:

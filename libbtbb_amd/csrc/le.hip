@@ -541,3 +541,4 @@ extern "C" int64_t btbbx_le_scan_host(const uint64_t *words, uint64_t n_words, u
 #include "le_csa2.h"
 #include "le_follow.h"
 #include "le_span.h"
+#include "le_data.h"
