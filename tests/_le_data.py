@@ -42,6 +42,13 @@ class Rules:
         self.whiten_restart = False         # rule 6: the whitening sequence restarted at the payload
         self.pos_all_members = False        # rule 5: pos counted over all members behind the START, not over the fragments
         self.order_by_index = False         # rule 6: messages ordered by the START's list index, not its rank
+        # (told apart on the worlds of tests/_le_data_lattice.py: LATTICE_VARIANTS there)
+        self.unknown_sets_sn = False        # rule 4: an UNKNOWN member's sn becomes the last sn of both roles
+        self.empty_breaks = False           # rule 5: an EMPTY member closes the open message of its role
+        self.retx_joins = False             # rule 5: a RETRANSMIT continuation's L is added to the open message once more
+        self.end_reads_on = False           # rule 6: bits beyond a row's end taken from the words that follow in memory
+        self.whiten_period_128 = False      # rule 6: the whitening sequence continued with period 128, not 127
+        self.offset_mod_2_32 = False        # rule 6: byte_offset kept modulo 2^32
         for k, v in kw.items():
             assert hasattr(self, k), k
             setattr(self, k, v)
@@ -55,9 +62,20 @@ VARIANTS = dict(role_flip=dict(role_flip=True), retx_any_role=dict(retx_any_role
 
 def payload_octets(row, n_words, offset, length, ch, rules=MODEL):
     """Rule 6: the `length` payload octets of the packet at `offset` of one stream, dewhitened; zeros beyond the stream's end."""
-    raw = _le.stream_bits(row, n_words, offset + 56, 8 * length)
+    raw = _le.stream_bits(row, n_words, offset + 56, 8 * length, past_end=rules.end_reads_on)
     at = 0 if rules.whiten_restart else 16
-    return _le.bits_octets(raw ^ _le._whitening_2080(ch & 0x3F)[at:at + 8 * length])
+    white = _le._whitening_2080(ch & 0x3F)
+    if rules.whiten_period_128:
+        return _le.bits_octets(raw ^ white[np.arange(at, at + 8 * length) % 128])
+    return _le.bits_octets(raw ^ white[at:at + 8 * length])
+
+
+def stream_row(rows, s, rules=MODEL):
+    """The words of stream s; for the end_reads_on variant the memory from its first word on, the rows behind it included."""
+    if not rules.end_reads_on:
+        return rows[s]
+    rows = np.asarray(rows)
+    return rows.reshape(-1)[s * rows.shape[1]:]
 
 
 def members_of(conns, cands, pkts):
@@ -102,6 +120,8 @@ def data(conns, cands, pkts, rows, n_words, msg_cap, byte_cap, rules=MODEL):
                 m["all"] += L
             if role == ROLE_UNKNOWN:
                 dpkts[i] = DPkt(NONE, 0, role, UNKNOWN, bits)
+                if rules.unknown_sets_sn:
+                    last_sn[CENTRAL] = last_sn[PERIPHERAL] = sn
                 continue
             key = "any" if rules.retx_any_role else role                                             # rule 4
             new = key not in last_sn or last_sn[key] != sn
@@ -109,6 +129,8 @@ def data(conns, cands, pkts, rows, n_words, msg_cap, byte_cap, rules=MODEL):
             if not new:
                 tally["retransmit"] += 1
                 dpkts[i] = DPkt(NONE, 0, role, RETRANSMIT, bits)
+                if rules.retx_joins and llid == 1 and L >= 1 and role in open_msg:
+                    open_msg[role]["bytes"] += L
                 continue
             key = "any" if rules.cont_any_role else role                                             # rule 5
             if llid == 2 and L >= 1:
@@ -129,6 +151,8 @@ def data(conns, cands, pkts, rows, n_words, msg_cap, byte_cap, rules=MODEL):
             elif llid == 1:
                 tally["empty"] += 1
                 dpkts[i] = DPkt(NONE, 0, role, EMPTY, bits)
+                if rules.empty_breaks:
+                    open_msg.pop(key, None)
             elif llid == 3:
                 tally["control"] += 1
                 dpkts[i] = DPkt(NONE, 0, role, CONTROL, bits)
@@ -143,7 +167,7 @@ def data(conns, cands, pkts, rows, n_words, msg_cap, byte_cap, rules=MODEL):
         c = cands[m["start"]]
         flags, l2cap_len, cid = RUNT, 0xFFFF, 0xFFFF
         if c.length >= 4:
-            hdr = payload_octets(rows[c.stream], n_words, c.offset, 4, pkts[m["start"]].channel, rules)
+            hdr = payload_octets(stream_row(rows, c.stream, rules), n_words, c.offset, 4, pkts[m["start"]].channel, rules)
             l2cap_len, cid = hdr[0] | hdr[1] << 8, hdr[2] | hdr[3] << 8
             flags = COMPLETE if m["bytes"] == 4 + l2cap_len else (OVERRUN if m["bytes"] > 4 + l2cap_len else 0)
         m["complete"] = bool(flags & COMPLETE)
@@ -152,10 +176,11 @@ def data(conns, cands, pkts, rows, n_words, msg_cap, byte_cap, rules=MODEL):
             buf = bytearray(m["bytes"] if not rules.pos_all_members else max(pos + cands[i].length for i, pos in m["frags"]))
             for i, pos in m["frags"]:
                 f = cands[i]
-                buf[pos:pos + f.length] = payload_octets(rows[f.stream], n_words, f.offset, f.length, pkts[i].channel, rules)
+                buf[pos:pos + f.length] = payload_octets(stream_row(rows, f.stream, rules), n_words, f.offset, f.length, pkts[i].channel, rules)
             payload[offset:offset + len(buf)] = buf
         if M < msg_cap:
-            msgs.append(Msg(offset, m["conn"], m["start"], len(m["frags"]), m["bytes"] & 0xFFFFFFFF, l2cap_len, cid, m["role"], flags))
+            msgs.append(Msg(offset & 0xFFFFFFFF if rules.offset_mod_2_32 else offset, m["conn"], m["start"], len(m["frags"]),
+                            m["bytes"] & 0xFFFFFFFF, l2cap_len, cid, m["role"], flags))
         offset += m["bytes"]
     records, before = [], 0
     for has, tally, mine in per_conn:
@@ -173,11 +198,11 @@ def check_invariants(out, conns, cands, pkts, msg_cap, byte_cap):
     """What rules 6 and 7 promise of any output."""
     assert sum(d.n_msgs for d in out.data) == out.n_msgs and sum(d.bytes for d in out.data) == out.n_bytes
     before = 0
+    mine = collections.Counter(c.channel for i, c in enumerate(cands) if out.dpkts[i] is not None)      # (one pass, whatever K)
     for g, d in enumerate(out.data):
         if d != Data(*([0] * 11)):
             assert d.first_msg == before
-            mine = [i for i, c in enumerate(cands) if c.channel == g and out.dpkts[i] is not None]
-            assert d.n_central + d.n_peripheral + d.n_unknown == len(mine)
+            assert d.n_central + d.n_peripheral + d.n_unknown == mine[g]
             before += d.n_msgs
     assert len(out.msgs) == min(out.n_msgs, msg_cap)
     stored = [bool(m.flags & STORED) for m in out.msgs]
@@ -379,7 +404,7 @@ def hand_built(conn_members, n_words, n_streams=1, seed=3, gap=1, shuffle=True, 
     rng = np.random.default_rng(seed)
     conns, cands, pkts = [], [], []
     for g, members in enumerate(conn_members):
-        for _ in range(gap):
+        for _ in range(gap if isinstance(gap, int) else gap[g]):             # (gap: one number, or one per connection)
             cands.append(ld.Cand(int(rng.integers(0, 64 * n_words)), 0x11110000 + g, 7, 0, 1, 0, ld.NO_CONN))
             pkts.append(None)
         order = rng.permutation(len(members)) if shuffle else np.arange(len(members))
