@@ -414,79 +414,3 @@ extern "C" int btbbx_le_csa2_device(const btbbx_le_cand *d_cands, const uint32_t
 	return le_csa2_launch(d_cands, d_cand_count, cand_cap, d_conns, d_conn_count, conn_cap, d_tracks, d_pkts, flags, d_sel, d_sel_pkts,
 			      d_scratch, (hipStream_t)hip_stream);
 }
-
-// behind the discovery's block: the tracking's scratch and records as btbbx_le_track_host lays them out, then this stage's
-static size_t le_csa2_host_tail(uint32_t dev_cap, uint32_t dev_conns)
-{
-	return le_track_host_tail(dev_cap, dev_conns) + ld_up(le_csa2_layout(dev_cap, dev_conns).total) +
-	       ld_up((size_t)dev_conns * sizeof(btbbx_le_csa2)) + ld_up((size_t)dev_cap * sizeof(btbbx_le_csa2_pkt));
-}
-
-// Host wrapper: btbbx_le_track_host's chain with the selection queued behind the tracking on the same stream, copy out.
-extern "C" int64_t btbbx_le_csa2_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
-				      uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
-				      btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
-				      uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
-				      btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_csa2 *sel, btbbx_le_csa2_pkt *sel_pkts)
-{
-	const char *who = "btbbx_le_csa2_host";
-	int rc = le_disc_check_args(who, n_words, pitch_words, n_streams, search_bits, max_len);
-	if (rc)
-		return rc;
-	rc = le_track_check_args(who, n_streams, unit_bits, jitter_bits);
-	if (rc)
-		return rc;
-	if (!words || !phys_channel || ((!conns || !tracks || !sel) && conn_cap) || (!cands && cand_cap)) {
-		set_error("%s: null pointer", who);
-		return BTBBX_E_ARG;
-	}
-	rc = ctx_require();
-	if (rc)
-		return rc;
-	if (n_cands_out)
-		*n_cands_out = 0;
-	CallScope scope;
-	hipStream_t q = scope_stream();
-	LeDiscHostRun r;
-	rc = le_disc_host_chain(words, n_words, pitch_words, n_streams, search_bits, phys_channel, max_len, min_count, conn_cap,
-				le_csa2_host_tail, &r);
-	if (rc)
-		return rc;
-	if (n_cands_out)
-		*n_cands_out = r.count;
-	if (!r.have)
-		return 0;
-	const uint64_t nc = std::min<uint64_t>(r.n_conns, r.dev_conns), nk = std::min<uint64_t>(r.have, cand_cap);
-	if (nc) {
-		char *scratch = r.tail;
-		btbbx_le_track *d_tracks = (btbbx_le_track *)(scratch + ld_up(le_track_layout(r.dev_cap, r.dev_conns).total));
-		btbbx_le_track_pkt *d_pkts = (btbbx_le_track_pkt *)((char *)d_tracks + ld_up((size_t)r.dev_conns * sizeof(btbbx_le_track)));
-		char *own = r.tail + le_track_host_tail(r.dev_cap, r.dev_conns);
-		btbbx_le_csa2 *d_sel = (btbbx_le_csa2 *)(own + ld_up(le_csa2_layout(r.dev_cap, r.dev_conns).total));
-		btbbx_le_csa2_pkt *d_sel_pkts = (btbbx_le_csa2_pkt *)((char *)d_sel + ld_up((size_t)r.dev_conns * sizeof(btbbx_le_csa2)));
-		rc = le_track_launch(r.d_cands, r.d_count, r.dev_cap, r.d_conn_count, r.dev_conns, r.d_phys, n_streams, unit_bits, ifs_bits,
-				     jitter_bits, flags, d_tracks, d_pkts, scratch, q);
-		if (rc)
-			return rc;
-		rc = le_csa2_launch(r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count, r.dev_conns, d_tracks, d_pkts, flags, d_sel,
-				    d_sel_pkts, own, q);
-		if (rc)
-			return rc;
-		HIP_TRY(hipMemcpyAsync(conns, r.d_conns, (size_t)nc * sizeof(btbbx_le_conn), hipMemcpyDeviceToHost, q));
-		HIP_TRY(hipMemcpyAsync(tracks, d_tracks, (size_t)nc * sizeof(btbbx_le_track), hipMemcpyDeviceToHost, q));
-		HIP_TRY(hipMemcpyAsync(sel, d_sel, (size_t)nc * sizeof(btbbx_le_csa2), hipMemcpyDeviceToHost, q));
-		if (nk && pkts)
-			HIP_TRY(hipMemcpyAsync(pkts, d_pkts, (size_t)nk * sizeof(btbbx_le_track_pkt), hipMemcpyDeviceToHost, q));
-		if (nk && sel_pkts)
-			HIP_TRY(hipMemcpyAsync(sel_pkts, d_sel_pkts, (size_t)nk * sizeof(btbbx_le_csa2_pkt), hipMemcpyDeviceToHost, q));
-	} else if (nk) {
-		if (pkts)
-			memset(pkts, 0xff, (size_t)nk * sizeof(btbbx_le_track_pkt));    // (no connection stored: no candidate is a member)
-		if (sel_pkts)
-			memset(sel_pkts, 0xff, (size_t)nk * sizeof(btbbx_le_csa2_pkt));
-	}
-	if (nk)
-		HIP_TRY(hipMemcpyAsync(cands, r.d_cands, (size_t)nk * sizeof(btbbx_le_cand), hipMemcpyDeviceToHost, q));
-	HIP_TRY(hipStreamSynchronize(q));
-	return (int64_t)r.n_conns;
-}

@@ -826,140 +826,3 @@ extern "C" int btbbx_le_data_device(const uint64_t *d_words, uint64_t n_words, u
 	return le_data_launch(d_words, n_words, pitch_words, n_streams, d_cands, d_cand_count, cand_cap, d_conns, d_conn_count, conn_cap, d_pkts,
 			      d_data, d_data_pkts, d_msgs, msg_cap, d_msg_count, d_bytes, byte_cap, d_byte_count, d_scratch, q);
 }
-
-// what the running host call keeps on the device for this stage (le_disc_host_chain asks for the tail's size by the two caps alone)
-static thread_local uint64_t ldt_host_msg_cap, ldt_host_byte_cap;
-
-struct LdtHostTail {
-	size_t scratch, data, dpkts, msgs, counts, bytes, total;
-	uint32_t msg_cap;
-	uint64_t byte_cap;
-};
-
-static LdtHostTail le_data_host_layout(uint32_t dev_cap, uint32_t dev_conns)
-{
-	LdtHostTail T;
-	T.msg_cap = (uint32_t)std::min<uint64_t>(ldt_host_msg_cap, dev_cap);               // (a message has a START of its own)
-	T.byte_cap = std::min<uint64_t>(ldt_host_byte_cap, 255ull * dev_cap);             // (and a fragment at most 255 octets)
-	size_t at = le_track_host_tail(dev_cap, dev_conns);
-	auto take = [&](size_t bytes) { const size_t here = at; at += ld_up(bytes); return here; };
-	T.scratch = take(le_data_layout(dev_cap, dev_conns).total);
-	T.data = take((size_t)dev_conns * sizeof(btbbx_le_data));
-	T.dpkts = take((size_t)dev_cap * sizeof(btbbx_le_data_pkt));
-	T.msgs = take((size_t)T.msg_cap * sizeof(btbbx_le_msg));
-	T.counts = take(256);
-	T.bytes = take((size_t)T.byte_cap + 8);
-	T.total = at;
-	return T;
-}
-
-static size_t le_data_host_tail(uint32_t dev_cap, uint32_t dev_conns) { return le_data_host_layout(dev_cap, dev_conns).total; }
-
-// Host wrapper: btbbx_le_track_host's chain, this stage behind it on the same stream, copy out.
-extern "C" int64_t btbbx_le_data_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
-				      uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
-				      btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
-				      uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
-				      btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_data *data, btbbx_le_data_pkt *data_pkts,
-				      btbbx_le_msg *msgs, uint64_t msg_cap, uint64_t *n_msgs_out, uint8_t *bytes, uint64_t byte_cap,
-				      uint64_t *n_bytes_out)
-{
-	const char *who = "btbbx_le_data_host";
-	int rc = le_disc_check_args(who, n_words, pitch_words, n_streams, search_bits, max_len);
-	if (rc)
-		return rc;
-	rc = le_track_check_args(who, n_streams, unit_bits, jitter_bits);
-	if (rc)
-		return rc;
-	if (!words || !phys_channel || ((!conns || !tracks || !data) && conn_cap) || (!cands && cand_cap) || (!msgs && msg_cap) ||
-	    (!bytes && byte_cap)) {
-		set_error("%s: null pointer", who);
-		return BTBBX_E_ARG;
-	}
-	rc = ctx_require();
-	if (rc)
-		return rc;
-	if (n_cands_out)
-		*n_cands_out = 0;
-	if (n_msgs_out)
-		*n_msgs_out = 0;
-	if (n_bytes_out)
-		*n_bytes_out = 0;
-	CallScope scope;
-	hipStream_t q = scope_stream();
-	LeDiscHostRun r;
-	ldt_host_msg_cap = msg_cap;
-	ldt_host_byte_cap = byte_cap;
-	rc = le_disc_host_chain(words, n_words, pitch_words, n_streams, search_bits, phys_channel, max_len, min_count, conn_cap,
-				le_data_host_tail, &r);
-	if (rc)
-		return rc;
-	if (n_cands_out)
-		*n_cands_out = r.count;
-	if (!r.have)
-		return 0;
-	const uint64_t nc = std::min<uint64_t>(r.n_conns, r.dev_conns), nk = std::min<uint64_t>(r.have, cand_cap);
-	if (nc) {
-		const LdtHostTail T = le_data_host_layout(r.dev_cap, r.dev_conns);
-		char *scratch = r.tail;
-		btbbx_le_track *d_tracks = (btbbx_le_track *)(scratch + ld_up(le_track_layout(r.dev_cap, r.dev_conns).total));
-		btbbx_le_track_pkt *d_pkts = (btbbx_le_track_pkt *)((char *)d_tracks + ld_up((size_t)r.dev_conns * sizeof(btbbx_le_track)));
-		btbbx_le_data *d_data = (btbbx_le_data *)(r.tail + T.data);
-		btbbx_le_data_pkt *d_dpkts = (btbbx_le_data_pkt *)(r.tail + T.dpkts);
-		btbbx_le_msg *d_msgs = (btbbx_le_msg *)(r.tail + T.msgs);
-		uint64_t *d_counts = (uint64_t *)(r.tail + T.counts);
-		uint8_t *d_bytes = (uint8_t *)(r.tail + T.bytes);
-		rc = le_track_launch(r.d_cands, r.d_count, r.dev_cap, r.d_conn_count, r.dev_conns, r.d_phys, n_streams, unit_bits, ifs_bits,
-				     jitter_bits, flags, d_tracks, d_pkts, scratch, q);
-		if (rc)
-			return rc;
-		rc = le_data_launch(r.d_words, n_words, pitch_words, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count,
-				    r.dev_conns, d_pkts, d_data, d_dpkts, d_msgs, T.msg_cap, (uint32_t *)(d_counts + 1), d_bytes, T.byte_cap, d_counts,
-				    r.tail + T.scratch, q);
-		if (rc)
-			return rc;
-		uint64_t counts[2] = {0, 0};
-		HIP_TRY(hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, q));
-		HIP_TRY(hipMemcpyAsync(conns, r.d_conns, (size_t)nc * sizeof(btbbx_le_conn), hipMemcpyDeviceToHost, q));
-		HIP_TRY(hipMemcpyAsync(tracks, d_tracks, (size_t)nc * sizeof(btbbx_le_track), hipMemcpyDeviceToHost, q));
-		HIP_TRY(hipMemcpyAsync(data, d_data, (size_t)nc * sizeof(btbbx_le_data), hipMemcpyDeviceToHost, q));
-		if (nk && pkts)
-			HIP_TRY(hipMemcpyAsync(pkts, d_pkts, (size_t)nk * sizeof(btbbx_le_track_pkt), hipMemcpyDeviceToHost, q));
-		if (nk && data_pkts)
-			HIP_TRY(hipMemcpyAsync(data_pkts, d_dpkts, (size_t)nk * sizeof(btbbx_le_data_pkt), hipMemcpyDeviceToHost, q));
-		if (nk)
-			HIP_TRY(hipMemcpyAsync(cands, r.d_cands, (size_t)nk * sizeof(btbbx_le_cand), hipMemcpyDeviceToHost, q));
-		HIP_TRY(hipStreamSynchronize(q));
-		const uint64_t n_msgs = (uint32_t)counts[1], have_msgs = std::min<uint64_t>(n_msgs, T.msg_cap);
-		if (n_msgs_out)
-			*n_msgs_out = n_msgs;
-		if (n_bytes_out)
-			*n_bytes_out = counts[0];
-		if (have_msgs) {
-			HIP_TRY(hipMemcpyAsync(msgs, d_msgs, (size_t)have_msgs * sizeof(btbbx_le_msg), hipMemcpyDeviceToHost, q));
-			HIP_TRY(hipStreamSynchronize(q));
-			uint64_t lo = 0, hi = have_msgs;                    // the stored messages are a prefix: the first that is not
-			while (lo < hi) {
-				const uint64_t mid = lo + (hi - lo) / 2;
-				if (msgs[mid].flags & BTBBX_LE_MSG_STORED)
-					lo = mid + 1;
-				else
-					hi = mid;
-			}
-			const uint64_t stored = lo ? msgs[lo - 1].byte_offset + msgs[lo - 1].bytes : 0;
-			if (stored) {
-				HIP_TRY(hipMemcpyAsync(bytes, d_bytes, (size_t)stored, hipMemcpyDeviceToHost, q));
-				HIP_TRY(hipStreamSynchronize(q));
-			}
-		}
-		return (int64_t)r.n_conns;
-	}
-	if (nk && pkts)
-		memset(pkts, 0xff, (size_t)nk * sizeof(btbbx_le_track_pkt));       // (no connection stored: no candidate is a member)
-	if (nk && data_pkts)
-		memset(data_pkts, 0xff, (size_t)nk * sizeof(btbbx_le_data_pkt));
-	if (nk)
-		HIP_TRY(hipMemcpyAsync(cands, r.d_cands, (size_t)nk * sizeof(btbbx_le_cand), hipMemcpyDeviceToHost, q));
-	HIP_TRY(hipStreamSynchronize(q));
-	return (int64_t)r.n_conns;
-}

@@ -583,6 +583,22 @@ extern "C" size_t btbbx_le_discover_scratch_bytes(uint32_t cand_cap)
 	return le_disc_layout(cand_cap).total;
 }
 
+// the radix sort's buffers where a stage's layout L has them in its scratch s; params[0] holds the list's length
+template <class Layout> static RadixBufs le_radix_bufs(char *s, const Layout &L, const uint32_t *params, uint32_t cap)
+{
+	return {{(uint64_t *)(s + L.keys[0]), (uint64_t *)(s + L.keys[1])}, {(uint32_t *)(s + L.vals[0]), (uint32_t *)(s + L.vals[1])},
+		(uint32_t *)(s + L.hist), (uint32_t *)(s + L.tot), params, cap};
+}
+
+// a stable sort by the n_bytes low bytes of the keys, least significant first, from side cur; returns the side the list ends in
+static int le_sort_bytes(const RadixBufs &b, int n_bytes, int cur, hipStream_t q)
+{
+	RadixPass passes[8];
+	for (int p = 0; p < 8; p++)
+		passes[p] = {0, 8u * p};
+	return radix_sort_passes(b, nullptr, passes, n_bytes, cur, q);
+}
+
 static int le_disc_launch_group(btbbx_le_cand *d_cands, const uint32_t *d_count, uint32_t cap, uint32_t min_count, btbbx_le_conn *d_conns,
 				uint32_t conn_cap, uint32_t *d_conn_count, void *d_scratch, hipStream_t q)
 {
@@ -591,24 +607,13 @@ static int le_disc_launch_group(btbbx_le_cand *d_cands, const uint32_t *d_count,
 	uint32_t *params = (uint32_t *)(s + L.params), *tiles = (uint32_t *)(s + L.tiles), *qtiles = (uint32_t *)(s + L.qtiles);
 	uint32_t *gstart = (uint32_t *)(s + L.gstart), *gid = (uint32_t *)(s + L.gid), *cidx = (uint32_t *)(s + L.cidx);
 	btbbx_le_cand *sorted = (btbbx_le_cand *)(s + L.sorted);
-	RadixBufs b;
-	b.keys[0] = (uint64_t *)(s + L.keys[0]);
-	b.keys[1] = (uint64_t *)(s + L.keys[1]);
-	b.vals[0] = (uint32_t *)(s + L.vals[0]);
-	b.vals[1] = (uint32_t *)(s + L.vals[1]);
-	b.hist = (uint32_t *)(s + L.hist);
-	b.tot = (uint32_t *)(s + L.tot);
-	b.params = params;
-	b.cap = cap;
+	const RadixBufs b = le_radix_bufs(s, L, params, cap);
 	const dim3 per_cand((cap + LE_THREADS - 1) / LE_THREADS), per_tile(L.grp_tiles), wg(LE_THREADS);
 	hipLaunchKernelGGL(le_disc_key_kernel, per_cand, wg, 0, q, d_cands, d_count, cap, params, b.keys[0], b.vals[0]);
 	// least significant first: the 48 offset bits and the stream number, then -- rekeyed -- CRCInit and the AA
-	RadixPass passes[8];
-	for (int p = 0; p < 8; p++)
-		passes[p] = {0, 8u * p};
-	int cur = radix_sort_passes(b, nullptr, passes, 8, 0, q);
+	int cur = le_sort_bytes(b, 8, 0, q);
 	hipLaunchKernelGGL(le_disc_rekey_kernel, per_cand, wg, 0, q, d_cands, params, b.vals[cur], b.keys[cur]);
-	cur = radix_sort_passes(b, nullptr, passes, 7, cur, q);
+	cur = le_sort_bytes(b, 7, cur, q);
 	const uint64_t *keys = b.keys[cur];
 	hipLaunchKernelGGL(le_disc_mark_kernel, per_tile, wg, 0, q, keys, params, tiles);
 	hipLaunchKernelGGL(le_disc_prefix_kernel, dim3(1), wg, 0, q, tiles, L.grp_tiles, params, gstart, (uint32_t *)nullptr);
@@ -647,122 +652,4 @@ extern "C" int btbbx_le_discover_group_device(btbbx_le_cand *d_cands, const uint
 		return BTBBX_OK;
 	}
 	return le_disc_launch_group(d_cands, d_cand_count, cand_cap, min_count, d_conns, conn_cap, d_conn_count, d_scratch, q);
-}
-
-// What the host chain leaves on the device, inside the caller's CallScope: the counters, the sorted candidates, the connection
-// records and, behind them, `tail` (tail_bytes(dev_cap, dev_conns) bytes for what a caller runs next on the same stream).
-struct LeDiscHostRun {
-	uint32_t dev_cap, dev_conns;                   // what the device buffers hold
-	uint32_t count, have, n_conns;                 // candidates found, candidates kept (min(count, dev_cap)), connections found
-	uint32_t *d_count, *d_conn_count;
-	btbbx_le_cand *d_cands;
-	btbbx_le_conn *d_conns;
-	const uint16_t *d_phys;
-	const uint64_t *d_words;                       // the capture as it was copied in
-	char *tail;
-};
-
-// copy in, scan (again with room for every candidate when the first guess was too small, as btbbx_scan_host does), group; both
-// counts read back.  have == 0: nothing was grouped and nothing but count is set
-static int le_disc_host_chain(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, uint64_t search_bits,
-			      const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count, uint64_t conn_cap,
-			      size_t (*tail_bytes)(uint32_t, uint32_t), LeDiscHostRun *r)
-{
-	int rc;
-	if (n_streams == 1)
-		pitch_words = n_words;
-	hipStream_t q = scope_stream();
-	const uint64_t cap_words = (uint64_t)(n_streams - 1) * pitch_words + n_words;
-	const size_t words_bytes = ((size_t)(cap_words + 1) * 8 + 255) & ~(size_t)255;
-	char *dblock = (char *)scope_device(words_bytes + 2 * (size_t)n_streams);
-	if (!dblock)
-		return BTBBX_E_NOMEM;
-	const uint64_t *d_words = (const uint64_t *)dblock;
-	uint16_t *d_phys = (uint16_t *)(dblock + words_bytes);
-	HIP_TRY(hipMemcpyAsync(dblock, words, (size_t)cap_words * 8, hipMemcpyHostToDevice, q));
-	HIP_TRY(hipMemcpyAsync(d_phys, phys_channel, 2 * (size_t)n_streams, hipMemcpyHostToDevice, q));
-	// first guess: one candidate per 4096 offsets + slack (noise yields one per 37 000 at max_len 27, one per 4000 at 255)
-	uint64_t guess = search_bits / 4096 * n_streams + 4096;
-	uint32_t dev_cap = guess > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)guess;
-	uint32_t count = 0;
-	char *block = nullptr;
-	size_t cand_bytes = 0, scratch_bytes = 0, conn_bytes = 0;
-	uint32_t dev_conns = 0;
-	for (int pass = 0; pass < 2; pass++) {
-		cand_bytes = ld_up((size_t)dev_cap * sizeof(btbbx_le_cand));
-		scratch_bytes = ld_up(btbbx_le_discover_scratch_bytes(dev_cap));
-		dev_conns = (uint32_t)std::min<uint64_t>(conn_cap, dev_cap);
-		conn_bytes = ld_up((size_t)dev_conns * sizeof(btbbx_le_conn));
-		block = (char *)scope_hits(256 + cand_bytes + scratch_bytes + conn_bytes + (tail_bytes ? tail_bytes(dev_cap, dev_conns) : 0));
-		if (!block)
-			return BTBBX_E_NOMEM;
-		HIP_TRY(hipMemsetAsync(block, 0, 2 * sizeof(uint32_t), q));
-		rc = le_disc_launch_scan(d_words, n_words, pitch_words, n_streams, search_bits, d_phys, max_len, (btbbx_le_cand *)(block + 256),
-					 dev_cap, (uint32_t *)block, q);
-		if (rc)
-			return rc;
-		HIP_TRY(hipMemcpyAsync(&count, block, sizeof(count), hipMemcpyDeviceToHost, q));
-		HIP_TRY(hipStreamSynchronize(q));
-		if (count <= dev_cap)
-			break;
-		dev_cap = count;
-	}
-	r->dev_cap = dev_cap;
-	r->dev_conns = dev_conns;
-	r->count = count;
-	r->have = std::min(count, dev_cap);
-	r->n_conns = 0;
-	r->d_count = (uint32_t *)block;
-	r->d_conn_count = (uint32_t *)block + 1;
-	r->d_cands = (btbbx_le_cand *)(block + 256);
-	r->d_conns = (btbbx_le_conn *)(block + 256 + cand_bytes + scratch_bytes);
-	r->d_phys = d_phys;
-	r->d_words = d_words;
-	r->tail = block + 256 + cand_bytes + scratch_bytes + conn_bytes;
-	if (!r->have)
-		return BTBBX_OK;
-	rc = le_disc_launch_group(r->d_cands, r->d_count, dev_cap, min_count, r->d_conns, dev_conns, r->d_conn_count, block + 256 + cand_bytes, q);
-	if (rc)
-		return rc;
-	HIP_TRY(hipMemcpyAsync(&r->n_conns, r->d_conn_count, sizeof(uint32_t), hipMemcpyDeviceToHost, q));
-	HIP_TRY(hipStreamSynchronize(q));
-	return BTBBX_OK;
-}
-
-// Host wrapper: the chain above, copy out.
-extern "C" int64_t btbbx_le_discover_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
-					  uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
-					  btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
-					  uint64_t *n_cands_out)
-{
-	const char *who = "btbbx_le_discover_host";
-	int rc = le_disc_check_args(who, n_words, pitch_words, n_streams, search_bits, max_len);
-	if (rc)
-		return rc;
-	if (!words || !phys_channel || (!conns && conn_cap) || (!cands && cand_cap)) {
-		set_error("%s: null pointer", who);
-		return BTBBX_E_ARG;
-	}
-	rc = ctx_require();
-	if (rc)
-		return rc;
-	if (n_cands_out)
-		*n_cands_out = 0;
-	CallScope scope;
-	hipStream_t q = scope_stream();
-	LeDiscHostRun r;
-	rc = le_disc_host_chain(words, n_words, pitch_words, n_streams, search_bits, phys_channel, max_len, min_count, conn_cap, nullptr, &r);
-	if (rc)
-		return rc;
-	if (n_cands_out)
-		*n_cands_out = r.count;
-	if (!r.have)
-		return 0;
-	const uint64_t nc = std::min<uint64_t>(r.n_conns, r.dev_conns), nk = std::min<uint64_t>(r.have, cand_cap);
-	if (nc)
-		HIP_TRY(hipMemcpyAsync(conns, r.d_conns, (size_t)nc * sizeof(btbbx_le_conn), hipMemcpyDeviceToHost, q));
-	if (nk)
-		HIP_TRY(hipMemcpyAsync(cands, r.d_cands, (size_t)nk * sizeof(btbbx_le_cand), hipMemcpyDeviceToHost, q));
-	HIP_TRY(hipStreamSynchronize(q));
-	return (int64_t)r.n_conns;
 }

@@ -25,8 +25,10 @@
 //   9. le_epoch_pkt_kernel      one lane per candidate: the per-packet record
 //
 // No kernel keeps per-connection state in an array of fixed size, and the count of launches depends on conn_cap only through
-// the radix passes over its bytes.  The kernels are extern "C", as in le_csa2.h.  Nothing here synchronises or reads back but
-// the host wrapper.
+// the radix passes over its bytes.  The kernels are extern "C", as in le_csa2.h.  Nothing here synchronises or reads back; the
+// host wrapper is le_host.h's.  What the span stage (le_span.h) does in the same way is written here once, for both: lf_mark_tile and
+// lf_list_tile, the sort of the update list, lf_predict, lf_tallies, lf_verdict, lf_pdu_kind, lf_pkt_event, and kernels 1-3, the
+// rekey and the gather kernel, which the span stage launches as they are.
 #pragma once
 #include "le_csa2.h"
 
@@ -486,14 +488,14 @@ __device__ __forceinline__ bool lf_map_update(const btbbx_le_cand *cands, const 
 	return lf_instant(info.y, c, at) && __popc(info.z) + __popc(info.w) >= 2;
 }
 
-extern "C" __global__ __launch_bounds__(LE_THREADS) void le_epoch_mark_kernel(const btbbx_le_cand *cands, const btbbx_le_track_pkt *pkts,
-									      const btbbx_le_conn *conns, const btbbx_le_seed *seeds,
-									      const uint32_t *params, const uint32_t *slot, const uint4 *ctl,
-									      const LfConn *work, const uint64_t *anchor, const unsigned long long *step,
-									      uint32_t jitter_bits, uint32_t *utiles)
+// The mark pass and the list pass of an update list, for this stage and for the span stage (le_span.h).  is_update(q, i, g, at, param)
+// says whether slot q holds an update that is listed -- candidate i of connection g, in force at `at` -- and may set `param` for
+// a slot whose candidate on_param(i, g) is to see.  The mark pass counts a tile's updates into utiles (32 or 64 bits wide, by the
+// prefix sum that follows)
+template <class Tile, class Pred> __device__ __forceinline__ void lf_mark_tile(uint32_t n, Tile *utiles, Pred is_update)
 {
 	__shared__ uint32_t count;
-	const uint32_t tid = threadIdx.x, n = params[0], k = params[1];
+	const uint32_t tid = threadIdx.x;
 	if (tid == 0)
 		count = 0;
 	__syncthreads();
@@ -504,7 +506,8 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_epoch_mark_kernel(co
 			break;
 		uint32_t i, g;
 		unsigned long long at;
-		mine += lf_map_update(cands, pkts, conns, seeds, slot, ctl, work, anchor, step, jitter_bits, q, n, k, i, g, at) ? 1u : 0u;
+		bool param;
+		mine += is_update(q, i, g, at, param) ? 1u : 0u;
 	}
 	if (mine)
 		atomicAdd(&count, mine);
@@ -513,26 +516,25 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_epoch_mark_kernel(co
 		utiles[blockIdx.x] = count;
 }
 
-// the updates in slot order, which is (connection, rank) order: update u gets the sort key I and its own index as the value
-extern "C" __global__ __launch_bounds__(LE_THREADS) void le_epoch_list_kernel(const btbbx_le_cand *cands, const btbbx_le_track_pkt *pkts,
-									      const btbbx_le_conn *conns, const btbbx_le_seed *seeds,
-									      const uint32_t *params, const uint32_t *slot, uint4 *ctl, LfConn *work,
-									      const uint64_t *anchor, const unsigned long long *step, uint32_t jitter_bits,
-									      const uint32_t *utiles, uint32_t *uparams, uint64_t *keys, uint32_t *vals,
-									      uint64_t *u_i, uint64_t *u_map, uint32_t *u_conn)
+// the updates in slot order, which is (connection, rank) order: update u gets the sort key I and its own index as the value.
+// The list's length is uparams[0]: TOTAL_IN_PARAMS: le_track_prefix_kernel left it in uparams[2]; else the last tile's carry is it
+template <bool TOTAL_IN_PARAMS, class Tile, class Pred, class OnParam>
+__device__ __forceinline__ void lf_list_tile(uint32_t n, const Tile *utiles, uint32_t *uparams, uint4 *ctl, LfConn *work, uint64_t *keys,
+					     uint32_t *vals, uint64_t *u_i, uint64_t *u_map, uint32_t *u_conn, Pred is_update, OnParam on_param)
 {
 	__shared__ uint32_t lds[LT_WAVES];
-	const uint32_t tid = threadIdx.x, n = params[0], k = params[1];
-	if (blockIdx.x == 0 && tid == 0)
-		uparams[0] = uparams[2];                            // (le_track_prefix_kernel left the total there)
-	uint32_t carry = utiles[blockIdx.x];
+	const uint32_t tid = threadIdx.x;
+	if (TOTAL_IN_PARAMS && blockIdx.x == 0 && tid == 0)
+		uparams[0] = uparams[2];
+	uint32_t carry = (uint32_t)utiles[blockIdx.x];
 	for (uint32_t r = 0; r < LT_TILE / LE_THREADS; r++) {
 		if (blockIdx.x * LT_TILE + r * LE_THREADS >= n)
 			break;                                          // (uniform over the workgroup)
 		const uint32_t q = blockIdx.x * LT_TILE + r * LE_THREADS + tid;
 		uint32_t i = LF_NONE, g = LF_NONE;
 		unsigned long long at = 0;
-		const bool is = q < n && lf_map_update(cands, pkts, conns, seeds, slot, ctl, work, anchor, step, jitter_bits, q, n, k, i, g, at);
+		bool param = false;
+		const bool is = q < n && is_update(q, i, g, at, param);
 		uint32_t sum;
 		const uint32_t ex = block_exclusive_scan<LT_WAVES>(is ? 1u : 0u, lds, sum);
 		if (is) {
@@ -546,8 +548,39 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_epoch_list_kernel(co
 			ctl[i].x = info.x | LF_IS_MAP;
 			atomicAdd(&work[g].n_map, 1u);
 		}
+		if (param)
+			on_param(i, g);
 		carry += sum;
 	}
+	if (!TOTAL_IN_PARAMS && blockIdx.x == gridDim.x - 1 && tid == 0)
+		uparams[0] = uparams[2] = carry;
+}
+
+extern "C" __global__ __launch_bounds__(LE_THREADS) void le_epoch_mark_kernel(const btbbx_le_cand *cands, const btbbx_le_track_pkt *pkts,
+									      const btbbx_le_conn *conns, const btbbx_le_seed *seeds,
+									      const uint32_t *params, const uint32_t *slot, const uint4 *ctl,
+									      const LfConn *work, const uint64_t *anchor, const unsigned long long *step,
+									      uint32_t jitter_bits, uint32_t *utiles)
+{
+	const uint32_t n = params[0], k = params[1];
+	lf_mark_tile(n, utiles, [=](uint32_t q, uint32_t &i, uint32_t &g, unsigned long long &at, bool &) __attribute__((always_inline)) {
+		return lf_map_update(cands, pkts, conns, seeds, slot, ctl, work, anchor, step, jitter_bits, q, n, k, i, g, at);
+	});
+}
+
+extern "C" __global__ __launch_bounds__(LE_THREADS) void le_epoch_list_kernel(const btbbx_le_cand *cands, const btbbx_le_track_pkt *pkts,
+									      const btbbx_le_conn *conns, const btbbx_le_seed *seeds,
+									      const uint32_t *params, const uint32_t *slot, uint4 *ctl, LfConn *work,
+									      const uint64_t *anchor, const unsigned long long *step, uint32_t jitter_bits,
+									      const uint32_t *utiles, uint32_t *uparams, uint64_t *keys, uint32_t *vals,
+									      uint64_t *u_i, uint64_t *u_map, uint32_t *u_conn)
+{
+	const uint32_t n = params[0], k = params[1];
+	lf_list_tile<true>(n, utiles, uparams, ctl, work, keys, vals, u_i, u_map, u_conn,
+			   [=](uint32_t q, uint32_t &i, uint32_t &g, unsigned long long &at, bool &) __attribute__((always_inline)) {
+				   return lf_map_update(cands, pkts, conns, seeds, slot, ctl, work, anchor, step, jitter_bits, q, n, k, i, g, at);
+			   },
+			   [](uint32_t, uint32_t) {});
 }
 
 // between the two sorts: the key becomes the connection
@@ -611,7 +644,67 @@ __device__ __forceinline__ void lf_tally(bool head, uint64_t run, bool flag, uin
 		atomicAdd(of_mine, count);
 }
 
-// rules 4-6 for the event at table position q; evres[q] = expected #1 | expected #2 << 8 | state << 16, epoch, counter, 0
+// rules 4-6 for a counted event of connection g with counter c on channel ch: the updates in force and, unless the event lies
+// beyond *stop, the channel either algorithm expects (0xff: none) and whether the event is on it.  Returns whether the event is
+// predicted, that is, not BEYOND.  ev, on1 and on2 come in with the values of an event that is not; u = uparams[0].
+// (Pointers, not values: what is read behind the search is not kept in registers over it)
+struct LfEvent {
+	uint32_t epoch, exp1, exp2;
+};
+
+__device__ __forceinline__ bool lf_predict(const btbbx_le_seed *s, const btbbx_le_conn *conn, uint32_t g, unsigned long long c,
+					   const unsigned long long *stop, uint32_t ch, const uint64_t *s_conn, const uint64_t *s_i,
+					   const uint64_t *s_map, uint32_t u, LfEvent &ev, bool &on1, bool &on2)
+{
+	const uint32_t lo = lf_lower(s_conn, u, g), hi = lf_upper(s_conn, s_i, u, g, c);
+	ev.epoch = hi - lo;
+	bool pred = false;
+	if (c < *stop) {
+		const unsigned long long map = (ev.epoch ? s_map[hi - 1] : s->map) & LC_MAP37;
+		const uint32_t n_used = (uint32_t)__popcll(map);
+		if (n_used) {
+			const uint32_t un = (s->hop * (uint32_t)((c + 1) % 37ull)) % 37u;
+			ev.exp1 = (map >> un) & 1 ? un : lt_nth_bit(map, un % n_used);
+			uint32_t unmapped;
+			ev.exp2 = lc_expected(lc_prn((uint32_t)c & 0xffffu, lc_channel_id(conn->access_address)), map, n_used, BTBBX_LE_CSA2_REMAP,
+					      unmapped);
+		}
+		pred = true;
+		on1 = ev.exp1 == ch;
+		on2 = ev.exp2 == ch;
+	}
+	return pred;
+}
+
+// The tallies of one event per lane.  A connection's events stand side by side in the table, so within the wave they are a run
+// of lanes that begins where the connection changes (a lane without a live event belongs to the run in front of it and holds no
+// flag): one atomic per tally, run and wave, whether the wave lies within one connection or over thirty small ones.  gap / n_gap:
+// the span stage's extra tally.  The last predicted event: only a lane whose neighbour does not continue its connection's run of
+// predicted events asks
+__device__ __forceinline__ void lf_tallies(uint32_t g, bool live, uint32_t lane, uint32_t e, bool before, bool gap, bool beyond, bool pred,
+					   bool on1, bool on2, LfConn *work, uint32_t *n_gap)
+{
+	const uint32_t pg = __shfl_up(g, 1);
+	const bool head = live && (lane == 0 || pg != g);
+	const uint64_t heads = __ballot(head), upto = lane == 63 ? ~0ULL : (2ULL << lane) - 1;
+	uint64_t run = 0;
+	if (head) {
+		const uint64_t behind = heads & ~upto;
+		run = (behind ? (1ULL << __builtin_ctzll(behind)) - 1 : ~0ULL) & ~(upto >> 1);
+	}
+	LfConn *w = work + (live ? g : 0);
+	lf_tally(head, run, before, &w->n_before);
+	lf_tally(head, run, gap, n_gap);
+	lf_tally(head, run, beyond, &w->n_beyond);
+	lf_tally(head, run, pred, &w->n_pred);
+	lf_tally(head, run, on1, &w->on1);
+	lf_tally(head, run, on2, &w->on2);
+	const uint32_t ng = __shfl_down(g, 1), np = __shfl_down(pred ? 1u : 0u, 1);
+	if (pred && (lane == 63 || ng != g || !np))
+		atomicMax(&work[g].last_pred, e + 1);
+}
+
+// the event at table position q; evres[q] = expected #1 | expected #2 << 8 | state << 16, epoch, counter, 0
 extern "C" __global__ __launch_bounds__(LE_THREADS) void le_epoch_predict_kernel(const btbbx_le_conn *conns, const btbbx_le_seed *seeds,
 										 const uint32_t *params, const uint32_t *uparams, const uint64_t *anchor,
 										 const uint32_t *econn, const unsigned long long *step,
@@ -623,64 +716,60 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_epoch_predict_kernel
 	if (q < n)
 		g = econn[q];
 	const bool live = g != LF_NONE && lf_seeded(seeds, g);
-	bool before = false, beyond = false, pred = false, on1 = false, on2 = false;
+	bool before = false, pred = false, beyond = false, on1 = false, on2 = false;
 	uint32_t e = 0;
 	if (live) {
+		LfEvent ev = {0, 0xff, 0xff};
 		const btbbx_le_seed s = seeds[g];
 		const uint32_t first = (uint32_t)conns[g].first;
 		const uint64_t a = anchor[q];
-		const uint32_t ch = (uint32_t)(a >> 56);
 		e = q - first;
-		uint32_t exp1 = 0xff, exp2 = 0xff, epoch = 0, counter = 0, state = BTBBX_LE_STATE_BEFORE;
+		uint32_t counter = 0, state = BTBBX_LE_STATE_BEFORE;
 		before = (a & LT_OFF_MASK) + jitter_bits < s.t0;
 		if (!before) {
 			const unsigned long long c = lf_counter(step, first, q);
-			const uint32_t u = uparams[0], lo = lf_lower(s_conn, u, g), hi = lf_upper(s_conn, s_i, u, g, c);
-			epoch = hi - lo;
+			pred = lf_predict(&s, conns + g, g, c, &work[g].stop, (uint32_t)(a >> 56), s_conn, s_i, s_map, uparams[0], ev, on1, on2);
 			counter = (uint32_t)c;
-			beyond = c >= work[g].stop;
+			beyond = !pred;
 			state = beyond ? BTBBX_LE_STATE_BEYOND : BTBBX_LE_STATE_COUNTED;
-			if (!beyond) {
-				const unsigned long long map = (epoch ? s_map[hi - 1] : s.map) & LC_MAP37;
-				const uint32_t n_used = (uint32_t)__popcll(map);
-				pred = true;
-				if (n_used) {
-					const uint32_t un = (s.hop * (uint32_t)((c + 1) % 37ull)) % 37u;
-					exp1 = (map >> un) & 1 ? un : lt_nth_bit(map, un % n_used);
-					uint32_t unmapped;
-					exp2 = lc_expected(lc_prn((uint32_t)c & 0xffffu, lc_channel_id(conns[g].access_address)), map, n_used,
-							   BTBBX_LE_CSA2_REMAP, unmapped);
-				}
-				on1 = exp1 == ch;
-				on2 = exp2 == ch;
-			}
 		}
-		evres[q] = make_uint4(exp1 | (exp2 << 8) | (state << 16), epoch, counter, 0);
+		evres[q] = make_uint4(ev.exp1 | (ev.exp2 << 8) | (state << 16), ev.epoch, counter, 0);
 	}
-	// A connection's events stand side by side in the table, so within the wave they are a run of lanes that begins where the
-	// connection changes (a lane without a live event belongs to the run in front of it and holds no flag): one atomic per tally,
-	// run and wave, whether the wave lies within one connection or over thirty small ones
-	const uint32_t pg = __shfl_up(g, 1);
-	const bool head = live && (lane == 0 || pg != g);
-	const uint64_t heads = __ballot(head), upto = lane == 63 ? ~0ULL : (2ULL << lane) - 1;
-	uint64_t run = 0;
-	if (head) {
-		const uint64_t behind = heads & ~upto;
-		run = (behind ? (1ULL << __builtin_ctzll(behind)) - 1 : ~0ULL) & ~(upto >> 1);
-	}
-	LfConn *w = work + (live ? g : 0);
-	lf_tally(head, run, before, &w->n_before);
-	lf_tally(head, run, beyond, &w->n_beyond);
-	lf_tally(head, run, pred, &w->n_pred);
-	lf_tally(head, run, on1, &w->on1);
-	lf_tally(head, run, on2, &w->on2);
-	// the last predicted event: only a lane whose neighbour does not continue its connection's run of predicted events asks
-	const uint32_t ng = __shfl_down(g, 1), np = __shfl_down(pred ? 1u : 0u, 1);
-	if (pred && (lane == 63 || ng != g || !np))
-		atomicMax(&work[g].last_pred, e + 1);
+	// (no GAP in this stage: lf_tally leaves before it touches its pointer when no lane of the wave holds the flag)
+	lf_tallies(g, live, lane, e, before, false, beyond, pred, on1, on2, work, nullptr);
 }
 
 // ---- 8. verdict -------------------------------------------------------------------------------------------------------------
+
+// what a SEEDED connection's tallies w say: the algorithm and its events on the hop, the first counted event's counter, the map in
+// force at the last predicted event, and SEEDED | COUNTED with the flags the passes gathered.  f = word 3 of the
+// connection's record (first, as 64 bits)
+struct LfVerdict {
+	unsigned long long map;
+	uint32_t algorithm, n_on, c_first, flags;
+};
+
+__device__ __forceinline__ LfVerdict lf_verdict(const LfConn &w, const btbbx_le_seed &s, uint2 f, uint32_t g, uint32_t n, const uint32_t *uparams,
+						const unsigned long long *step, const uint64_t *s_conn, const uint64_t *s_map,
+						const uint4 *evres)
+{
+	LfVerdict v;
+	const bool counted = w.n_pred + w.n_beyond != 0;
+	v.algorithm = s.chsel && w.on2 >= w.on1 ? 2u : 1u;
+	v.n_on = v.algorithm == 2 ? w.on2 : w.on1;
+	v.c_first = 0;
+	v.map = s.map;
+	if (counted && !f.y && f.x < n && w.n_before < n - f.x) {
+		v.c_first = (uint32_t)lf_counter(step, f.x, f.x + w.n_before);
+		if (w.last_pred) {
+			const uint32_t epoch = evres[f.x + w.last_pred - 1].y;
+			if (epoch)
+				v.map = s_map[lf_lower(s_conn, uparams[0], g) + epoch - 1] & LC_MAP37;
+		}
+	}
+	v.flags = BTBBX_LE_FOLLOW_SEEDED | (counted ? BTBBX_LE_FOLLOW_COUNTED : 0u) | w.flags;
+	return v;
+}
 
 extern "C" __global__ __launch_bounds__(LE_THREADS) void le_epoch_verdict_kernel(const btbbx_le_conn *conns, const btbbx_le_seed *seeds,
 										 const uint32_t *params, const uint32_t *uparams,
@@ -699,34 +788,63 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_epoch_verdict_kernel
 		return;
 	}
 	const LfConn w = work[g];
-	const btbbx_le_seed s = seeds[g];
-	const uint2 f = reinterpret_cast<const uint2 *>(conns + g)[3];
-	const bool counted = w.n_pred + w.n_beyond != 0;
-	const uint32_t algorithm = s.chsel && w.on2 >= w.on1 ? 2u : 1u, n_on = algorithm == 2 ? w.on2 : w.on1;
-	uint32_t c_first = 0;
-	unsigned long long map = s.map;
-	if (counted && !f.y && f.x < n && w.n_before < n - f.x) {
-		c_first = (uint32_t)lf_counter(step, f.x, f.x + w.n_before);
-		if (w.last_pred) {
-			const uint32_t epoch = evres[f.x + w.last_pred - 1].y;
-			if (epoch)
-				map = s_map[lf_lower(s_conn, uparams[0], g) + epoch - 1] & LC_MAP37;
-		}
-	}
-	uint32_t flags = BTBBX_LE_FOLLOW_SEEDED | (counted ? BTBBX_LE_FOLLOW_COUNTED : 0u) | w.flags;
+	const LfVerdict v = lf_verdict(w, seeds[g], reinterpret_cast<const uint2 *>(conns + g)[3], g, n, uparams, step, s_conn, s_map, evres);
+	uint32_t flags = v.flags;
 	if (w.stop != LF_NO_STOP)
 		flags |= BTBBX_LE_FOLLOW_STOPPED;
 	if (w.enc_rank != LF_NONE)
 		flags |= BTBBX_LE_FOLLOW_ENCRYPTED;
-	out[0] = make_uint2((uint32_t)map, (uint32_t)(map >> 32));
-	out[1] = make_uint2(c_first, (uint32_t)w.stop);
-	out[2] = make_uint2(w.n_before, n_on);
-	out[3] = make_uint2(w.n_pred - n_on, w.n_beyond);
+	out[0] = make_uint2((uint32_t)v.map, (uint32_t)(v.map >> 32));
+	out[1] = make_uint2(v.c_first, (uint32_t)w.stop);
+	out[2] = make_uint2(w.n_before, v.n_on);
+	out[3] = make_uint2(w.n_pred - v.n_on, w.n_beyond);
 	out[4] = make_uint2(w.n_control, w.n_map);
-	out[5] = make_uint2(algorithm | (flags << 8), 0);
+	out[5] = make_uint2(v.algorithm | (flags << 8), 0);
 }
 
 // ---- 9. packets -------------------------------------------------------------------------------------------------------------
+
+// the kind of the PDU whose control word is x, of the member with this rank; op: the opcode, 0xff where none can be read
+__device__ __forceinline__ uint32_t lf_pdu_kind(uint32_t x, uint32_t rank, uint32_t enc_rank, uint32_t &op)
+{
+	const uint32_t opcode = (x >> 8) & 0xffu, len = (x >> 16) & 0xffu;
+	uint32_t kind = BTBBX_LE_PDU_DATA;
+	op = 0xff;
+	if (x & LF_CONTROL) {
+		if (rank > enc_rank) {
+			kind = BTBBX_LE_PDU_OPAQUE;
+		} else {
+			op = opcode;
+			kind = BTBBX_LE_PDU_CONTROL;
+			if (opcode == 5 && len == 1)
+				kind = BTBBX_LE_PDU_ENC_START;
+			else if (opcode == 2 && len == 2)
+				kind = BTBBX_LE_PDU_TERMINATE;
+			else if (x & LF_IS_MAP)
+				kind = BTBBX_LE_PDU_MAP_UPDATE;
+			else if (x & LF_IS_PARAM)
+				kind = BTBBX_LE_PDU_PARAM_UPDATE;
+		}
+	}
+	return kind;
+}
+
+// what a member on channel ch of a SEEDED connection reads from its event's evres word; *algorithm: the connection's verdict
+struct LfPktEvent {
+	uint32_t state, epoch, counter, span, expected, on;
+};
+
+__device__ __forceinline__ void lf_pkt_event(uint4 ev, const uint8_t *algorithm, uint32_t ch, LfPktEvent &e)
+{
+	e.state = (ev.x >> 16) & 0xffu;
+	e.epoch = ev.y < 0xffffu ? ev.y : 0xffffu;
+	e.counter = ev.z;
+	e.span = ev.w;
+	if (e.state == BTBBX_LE_STATE_COUNTED) {
+		e.expected = *algorithm == 2 ? (ev.x >> 8) & 0xffu : ev.x & 0xffu;
+		e.on = e.expected == ch ? 1u : 0u;
+	}
+}
 
 extern "C" __global__ __launch_bounds__(LE_THREADS) void le_epoch_pkt_kernel(const btbbx_le_cand *cands, const btbbx_le_track_pkt *pkts,
 									     const btbbx_le_conn *conns, const btbbx_le_seed *seeds,
@@ -740,38 +858,14 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_epoch_pkt_kernel(con
 	uint32_t g, first, w0 = 0xffffffffu, w1 = 0xffffffffu, w2 = 0xffffffffu;
 	uint4 p;
 	if (lf_member(cands, pkts, conns, i, n, k, g, p, first)) {
-		const uint32_t x = ctl[i].x, opcode = (x >> 8) & 0xffu, len = (x >> 16) & 0xffu, enc = work[g].enc_rank;
-		uint32_t kind = BTBBX_LE_PDU_DATA, op = 0xff;
-		if (x & LF_CONTROL) {
-			if (p.x > enc) {
-				kind = BTBBX_LE_PDU_OPAQUE;
-			} else {
-				op = opcode;
-				kind = BTBBX_LE_PDU_CONTROL;
-				if (opcode == 5 && len == 1)
-					kind = BTBBX_LE_PDU_ENC_START;
-				else if (opcode == 2 && len == 2)
-					kind = BTBBX_LE_PDU_TERMINATE;
-				else if (x & LF_IS_MAP)
-					kind = BTBBX_LE_PDU_MAP_UPDATE;
-				else if (x & LF_IS_PARAM)
-					kind = BTBBX_LE_PDU_PARAM_UPDATE;
-			}
-		}
-		uint32_t counter = 0, epoch = 0, expected = 0xff, on = 0, state = 0;
-		if (lf_seeded(seeds, g)) {
-			const uint4 ev = evres[first + p.y];
-			state = (ev.x >> 16) & 0xffu;
-			epoch = ev.y < 0xffffu ? ev.y : 0xffffu;
-			counter = ev.z;
-			if (state == BTBBX_LE_STATE_COUNTED) {
-				expected = follows[g].algorithm == 2 ? (ev.x >> 8) & 0xffu : ev.x & 0xffu;
-				on = expected == (p.w & 0xffu) ? 1u : 0u;
-			}
-		}
-		w0 = counter;
-		w1 = epoch | (kind << 16) | (op << 24);
-		w2 = expected | (on << 8) | (state << 16);
+		uint32_t op;
+		const uint32_t kind = lf_pdu_kind(ctl[i].x, p.x, work[g].enc_rank, op);
+		LfPktEvent e = {0, 0, 0, 0, 0xff, 0};
+		if (lf_seeded(seeds, g))
+			lf_pkt_event(evres[first + p.y], &follows[g].algorithm, p.w & 0xffu, e);
+		w0 = e.counter;
+		w1 = e.epoch | (kind << 16) | (op << 24);
+		w2 = e.expected | (e.on << 8) | (e.state << 16);
 	}
 	uint32_t *o = reinterpret_cast<uint32_t *>(out + i);
 	o[0] = w0;
@@ -786,62 +880,96 @@ extern "C" size_t btbbx_le_epoch_scratch_bytes(uint32_t cand_cap, uint32_t conn_
 	return le_follow_layout(cand_cap, conn_cap).total;
 }
 
+// the arrays of a run in its scratch, for this stage and for the span stage, whose own arrays stand behind them
+struct LfBufs {
+	uint32_t *params, *uparams, *slot, *econn, *utiles, *u_conn;
+	uint64_t *anchor, *u_i, *u_map, *s_i, *s_map;
+	unsigned long long *step, *tiles64;
+	uint4 *ctl, *evres;
+	LfConn *work;
+	RadixBufs b;
+	uint32_t tiles_n;
+};
+
+static LfBufs le_follow_bufs(void *d_scratch, uint32_t cap, uint32_t conn_cap)
+{
+	const LfLayout L = le_follow_layout(cap, conn_cap);
+	char *s = (char *)d_scratch;
+	LfBufs B;
+	B.params = (uint32_t *)(s + L.params);
+	B.uparams = (uint32_t *)(s + L.uparams);
+	B.slot = (uint32_t *)(s + L.slot);
+	B.econn = (uint32_t *)(s + L.econn);
+	B.utiles = (uint32_t *)(s + L.utiles);
+	B.u_conn = (uint32_t *)(s + L.u_conn);
+	B.anchor = (uint64_t *)(s + L.anchor);
+	B.u_i = (uint64_t *)(s + L.u_i);
+	B.u_map = (uint64_t *)(s + L.u_map);
+	B.s_i = (uint64_t *)(s + L.s_i);
+	B.s_map = (uint64_t *)(s + L.s_map);
+	B.step = (unsigned long long *)(s + L.step);
+	B.tiles64 = (unsigned long long *)(s + L.tiles64);
+	B.ctl = (uint4 *)(s + L.ctl);
+	B.evres = (uint4 *)(s + L.evres);
+	B.work = (LfConn *)(s + L.work);
+	B.b = le_radix_bufs(s, L, B.uparams, cap);
+	B.tiles_n = L.tiles_n;
+	return B;
+}
+
+// kernels 1-3: the tables every later pass of this stage and of the span stage reads
+static void le_follow_open(const LfBufs &B, const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			   const btbbx_le_cand *d_cands, const uint32_t *d_count, uint32_t cap, const btbbx_le_conn *d_conns,
+			   const uint32_t *d_conn_count, uint32_t conn_cap, const btbbx_le_track_pkt *d_pkts, hipStream_t q)
+{
+	const dim3 per_cand((cap + LE_THREADS - 1) / LE_THREADS), wg(LE_THREADS);
+	const uint32_t init_grid = (uint32_t)(((uint64_t)std::max(cap, conn_cap) + LE_THREADS - 1) / LE_THREADS);
+	hipLaunchKernelGGL(le_epoch_init_kernel, dim3(init_grid), wg, 0, q, d_count, cap, d_conn_count, conn_cap, B.params, B.uparams, B.slot, B.econn,
+			   B.work);
+	hipLaunchKernelGGL(le_epoch_slot_kernel, per_cand, wg, 0, q, d_words, n_words, pitch_words, n_streams, d_cands, d_pkts, d_conns, B.params,
+			   B.slot, B.ctl, B.work);
+	hipLaunchKernelGGL(le_epoch_open_kernel, per_cand, wg, 0, q, d_cands, d_pkts, d_conns, B.params, B.slot, B.anchor, B.econn);
+}
+
+// the update list a list kernel left in side 0 of the sort's buffers, sorted stably by I -- least significant first: the 48 bits an
+// absolute instant can have -- and then, rekeyed, by the connection index; gathered into s_i / s_map.  Returns s_conn
+static const uint64_t *le_follow_sort_updates(const LfBufs &B, uint32_t cap, uint32_t conn_cap, hipStream_t q)
+{
+	const dim3 per_cand((cap + LE_THREADS - 1) / LE_THREADS), wg(LE_THREADS);
+	int cur = le_sort_bytes(B.b, 6, 0, q);
+	hipLaunchKernelGGL(le_epoch_rekey_kernel, per_cand, wg, 0, q, B.uparams, B.b.vals[cur], B.u_conn, B.b.keys[cur]);
+	cur = le_sort_bytes(B.b, le_conn_passes(conn_cap), cur, q);
+	hipLaunchKernelGGL(le_epoch_gather_kernel, per_cand, wg, 0, q, B.uparams, B.b.vals[cur], B.u_i, B.u_map, B.s_i, B.s_map);
+	return B.b.keys[cur];
+}
+
 // the launches of one run: 12 of this stage's kernels, 3 of the tracking's scans, and 3 per radix pass (6 over I, 1 to 4 over conn_cap)
 static int le_follow_launch(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, const btbbx_le_cand *d_cands,
 			    const uint32_t *d_count, uint32_t cap, const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
 			    const btbbx_le_track_pkt *d_pkts, const btbbx_le_seed *d_seeds, uint32_t unit_bits, uint32_t jitter_bits,
 			    btbbx_le_follow *d_follows, btbbx_le_follow_pkt *d_fpkts, void *d_scratch, hipStream_t q)
 {
-	const LfLayout L = le_follow_layout(cap, conn_cap);
-	char *s = (char *)d_scratch;
-	uint32_t *params = (uint32_t *)(s + L.params), *uparams = (uint32_t *)(s + L.uparams), *slot = (uint32_t *)(s + L.slot);
-	uint32_t *econn = (uint32_t *)(s + L.econn), *utiles = (uint32_t *)(s + L.utiles), *u_conn = (uint32_t *)(s + L.u_conn);
-	uint64_t *anchor = (uint64_t *)(s + L.anchor), *u_i = (uint64_t *)(s + L.u_i), *u_map = (uint64_t *)(s + L.u_map);
-	uint64_t *s_i = (uint64_t *)(s + L.s_i), *s_map = (uint64_t *)(s + L.s_map);
-	unsigned long long *step = (unsigned long long *)(s + L.step), *tiles64 = (unsigned long long *)(s + L.tiles64);
-	uint4 *ctl = (uint4 *)(s + L.ctl), *evres = (uint4 *)(s + L.evres);
-	LfConn *work = (LfConn *)(s + L.work);
-	RadixBufs b;
-	b.keys[0] = (uint64_t *)(s + L.keys[0]);
-	b.keys[1] = (uint64_t *)(s + L.keys[1]);
-	b.vals[0] = (uint32_t *)(s + L.vals[0]);
-	b.vals[1] = (uint32_t *)(s + L.vals[1]);
-	b.hist = (uint32_t *)(s + L.hist);
-	b.tot = (uint32_t *)(s + L.tot);
-	b.params = uparams;
-	b.cap = cap;
-	const dim3 per_cand((cap + LE_THREADS - 1) / LE_THREADS), per_tile(L.tiles_n), wg(LE_THREADS);
-	const uint32_t init_grid = (uint32_t)(((uint64_t)std::max(cap, conn_cap) + LE_THREADS - 1) / LE_THREADS);
-	hipLaunchKernelGGL(le_epoch_init_kernel, dim3(init_grid), wg, 0, q, d_count, cap, d_conn_count, conn_cap, params, uparams, slot, econn, work);
-	hipLaunchKernelGGL(le_epoch_slot_kernel, per_cand, wg, 0, q, d_words, n_words, pitch_words, n_streams, d_cands, d_pkts, d_conns, params, slot,
-			   ctl, work);
-	hipLaunchKernelGGL(le_epoch_open_kernel, per_cand, wg, 0, q, d_cands, d_pkts, d_conns, params, slot, anchor, econn);
-	hipLaunchKernelGGL(le_epoch_step_kernel, per_tile, wg, 0, q, anchor, econn, d_conns, d_seeds, params, unit_bits, jitter_bits, step, tiles64);
-	hipLaunchKernelGGL(le_track_prefix64_kernel, dim3(1), wg, 0, q, tiles64, L.tiles_n);
-	hipLaunchKernelGGL(le_track_count_kernel, per_tile, wg, 0, q, params, tiles64, step);
-	hipLaunchKernelGGL(le_epoch_stop_kernel, per_cand, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, params, anchor, step, jitter_bits, ctl, work);
-	hipLaunchKernelGGL(le_epoch_mark_kernel, per_tile, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, params, slot, ctl, work, anchor, step,
-			   jitter_bits, utiles);
-	hipLaunchKernelGGL(le_track_prefix_kernel, dim3(1), wg, 0, q, utiles, L.tiles_n, uparams);
-	hipLaunchKernelGGL(le_epoch_list_kernel, per_tile, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, params, slot, ctl, work, anchor, step,
-			   jitter_bits, utiles, uparams, b.keys[0], b.vals[0], u_i, u_map, u_conn);
-	// least significant first: the 48 bits an absolute instant can have, then -- rekeyed -- the connection index
-	RadixPass passes[6];
-	for (int p = 0; p < 6; p++)
-		passes[p] = {0, 8u * p};
-	int cur = radix_sort_passes(b, nullptr, passes, 6, 0, q);
-	hipLaunchKernelGGL(le_epoch_rekey_kernel, per_cand, wg, 0, q, uparams, b.vals[cur], u_conn, b.keys[cur]);
-	int conn_passes = 1;
-	while (conn_passes < 4 && (conn_cap >> (8 * conn_passes)))
-		conn_passes++;
-	cur = radix_sort_passes(b, nullptr, passes, conn_passes, cur, q);
-	const uint64_t *s_conn = b.keys[cur];
-	hipLaunchKernelGGL(le_epoch_gather_kernel, per_cand, wg, 0, q, uparams, b.vals[cur], u_i, u_map, s_i, s_map);
-	hipLaunchKernelGGL(le_epoch_predict_kernel, per_cand, wg, 0, q, d_conns, d_seeds, params, uparams, anchor, econn, step, s_conn, s_i, s_map,
-			   jitter_bits, evres, work);
-	hipLaunchKernelGGL(le_epoch_verdict_kernel, dim3((conn_cap + LE_THREADS - 1) / LE_THREADS), wg, 0, q, d_conns, d_seeds, params, uparams, step,
-			   s_conn, s_map, evres, work, d_follows);
-	hipLaunchKernelGGL(le_epoch_pkt_kernel, per_cand, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, params, ctl, evres, work, d_follows, d_fpkts);
+	const LfBufs B = le_follow_bufs(d_scratch, cap, conn_cap);
+	const dim3 per_cand((cap + LE_THREADS - 1) / LE_THREADS), per_tile(B.tiles_n), wg(LE_THREADS);
+	le_follow_open(B, d_words, n_words, pitch_words, n_streams, d_cands, d_count, cap, d_conns, d_conn_count, conn_cap, d_pkts, q);
+	hipLaunchKernelGGL(le_epoch_step_kernel, per_tile, wg, 0, q, B.anchor, B.econn, d_conns, d_seeds, B.params, unit_bits, jitter_bits, B.step,
+			   B.tiles64);
+	hipLaunchKernelGGL(le_track_prefix64_kernel, dim3(1), wg, 0, q, B.tiles64, B.tiles_n);
+	hipLaunchKernelGGL(le_track_count_kernel, per_tile, wg, 0, q, B.params, B.tiles64, B.step);
+	hipLaunchKernelGGL(le_epoch_stop_kernel, per_cand, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, B.params, B.anchor, B.step, jitter_bits, B.ctl,
+			   B.work);
+	hipLaunchKernelGGL(le_epoch_mark_kernel, per_tile, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, B.params, B.slot, B.ctl, B.work, B.anchor,
+			   B.step, jitter_bits, B.utiles);
+	hipLaunchKernelGGL(le_track_prefix_kernel, dim3(1), wg, 0, q, B.utiles, B.tiles_n, B.uparams);
+	hipLaunchKernelGGL(le_epoch_list_kernel, per_tile, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, B.params, B.slot, B.ctl, B.work, B.anchor,
+			   B.step, jitter_bits, B.utiles, B.uparams, B.b.keys[0], B.b.vals[0], B.u_i, B.u_map, B.u_conn);
+	const uint64_t *s_conn = le_follow_sort_updates(B, cap, conn_cap, q);
+	hipLaunchKernelGGL(le_epoch_predict_kernel, per_cand, wg, 0, q, d_conns, d_seeds, B.params, B.uparams, B.anchor, B.econn, B.step, s_conn, B.s_i,
+			   B.s_map, jitter_bits, B.evres, B.work);
+	hipLaunchKernelGGL(le_epoch_verdict_kernel, dim3((conn_cap + LE_THREADS - 1) / LE_THREADS), wg, 0, q, d_conns, d_seeds, B.params, B.uparams,
+			   B.step, s_conn, B.s_map, B.evres, B.work, d_follows);
+	hipLaunchKernelGGL(le_epoch_pkt_kernel, per_cand, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, B.params, B.ctl, B.evres, B.work, d_follows,
+			   d_fpkts);
 	HIP_TRY(hipGetLastError());
 	return BTBBX_OK;
 }
@@ -882,223 +1010,4 @@ extern "C" int btbbx_le_epoch_device(const uint64_t *d_words, uint64_t n_words, 
 		return BTBBX_OK;
 	return le_follow_launch(d_words, n_words, pitch_words, n_streams, d_cands, d_cand_count, cand_cap, d_conns, d_conn_count, conn_cap, d_pkts,
 				d_seeds, unit_bits, jitter_bits, d_follows, d_follow_pkts, d_scratch, (hipStream_t)hip_stream);
-}
-
-// ---- the host wrapper -------------------------------------------------------------------------------------------------------
-
-// the advertising scan's block: the counter, the hits, the ordering's scratch, the decoded records
-struct LfAdvLayout {
-	size_t hits, order, pkts, total;
-};
-
-static LfAdvLayout le_follow_adv_layout(uint32_t cap)
-{
-	LfAdvLayout A;
-	A.hits = 256;
-	A.order = A.hits + ld_up((size_t)cap * sizeof(btbbx_hit));
-	A.pkts = A.order + (cap >= 2 ? ld_up(btbbx_order_hits_scratch_bytes(cap)) : 0);
-	A.total = A.pkts + ld_up((size_t)cap * sizeof(btbbx_le_pkt));
-	return A;
-}
-
-static thread_local uint32_t lf_adv_guess;             // the advertising hits the tail of the running call has room for
-static thread_local int lf_span_updates = -1;          // max_updates of the running call when the span stage (le_span.h) ends the chain
-
-// what btbbx_le_span_host hands to the chain in place of the follow stage's records; the stage itself is le_span.h's
-struct LfSpanOut {
-	uint32_t max_updates;
-	btbbx_le_span *spans;
-	btbbx_le_span_pkt *span_pkts;
-	btbbx_le_span_rec *span_recs;
-};
-static size_t le_span_scratch_total(uint32_t cand_cap, uint32_t conn_cap, uint32_t max_updates);
-static int le_span_launch(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, const btbbx_le_cand *d_cands,
-			  const uint32_t *d_count, uint32_t cap, const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
-			  const btbbx_le_track_pkt *d_pkts, const btbbx_le_seed *d_seeds, uint32_t unit_bits, uint32_t jitter_bits,
-			  uint32_t max_updates, btbbx_le_span *d_spans, btbbx_le_span_pkt *d_spkts, btbbx_le_span_rec *d_recs, void *d_scratch,
-			  hipStream_t q);
-
-// the last stage's scratch, per-connection and per-candidate records and, for the span stage, its span records
-static void le_follow_last_sizes(uint32_t dev_cap, uint32_t dev_conns, size_t &scratch, size_t &per_conn, size_t &per_cand, size_t &recs)
-{
-	if (lf_span_updates < 0) {
-		scratch = le_follow_layout(dev_cap, dev_conns).total;
-		per_conn = (size_t)dev_conns * sizeof(btbbx_le_follow);
-		per_cand = (size_t)dev_cap * sizeof(btbbx_le_follow_pkt);
-		recs = 0;
-	} else {
-		scratch = le_span_scratch_total(dev_cap, dev_conns, (uint32_t)lf_span_updates);
-		per_conn = (size_t)dev_conns * sizeof(btbbx_le_span);
-		per_cand = (size_t)dev_cap * sizeof(btbbx_le_span_pkt);
-		recs = (size_t)dev_conns * ((size_t)lf_span_updates + 1) * sizeof(btbbx_le_span_rec);
-	}
-}
-
-// behind the discovery's block: the tracking's part as btbbx_le_track_host lays it out, the seeds, the last stage's scratch and
-// records, the advertising scan's block
-static size_t le_follow_host_tail(uint32_t dev_cap, uint32_t dev_conns)
-{
-	size_t scratch, per_conn, per_cand, recs;
-	le_follow_last_sizes(dev_cap, dev_conns, scratch, per_conn, per_cand, recs);
-	return le_track_host_tail(dev_cap, dev_conns) + ld_up((size_t)dev_conns * sizeof(btbbx_le_seed)) + ld_up(scratch) + ld_up(per_conn) +
-	       ld_up(per_cand) + ld_up(recs) + le_follow_adv_layout(lf_adv_guess).total;
-}
-
-// Host wrapper: btbbx_le_track_host's chain; the advertising scan over the same device copy of the capture, ordered and decoded;
-// the seed stage and the follow stage behind the tracking, all on one stream; copy out.
-// span: the span stage ends the chain and its records are copied out; NULL: the follow stage and follows / follow_pkts
-static int64_t le_follow_host_chain(const char *who, const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
-				    uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
-				    btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
-				    uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
-				    int adv_errors, btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_seed *seeds,
-				    btbbx_le_follow *follows, btbbx_le_follow_pkt *follow_pkts, const LfSpanOut *span)
-{
-	int rc = le_disc_check_args(who, n_words, pitch_words, n_streams, search_bits, max_len);
-	if (rc)
-		return rc;
-	rc = le_check_args(who, n_words, pitch_words, n_streams, search_bits, adv_errors);
-	if (rc)
-		return rc;
-	rc = le_track_check_args(who, n_streams, unit_bits, jitter_bits);
-	if (rc)
-		return rc;
-	if (!words || !phys_channel || ((!conns || !tracks || !seeds || (span ? !span->spans || !span->span_recs : !follows)) && conn_cap) ||
-	    (!cands && cand_cap)) {
-		set_error("%s: null pointer", who);
-		return BTBBX_E_ARG;
-	}
-	rc = ctx_require();
-	if (rc)
-		return rc;
-	if (n_cands_out)
-		*n_cands_out = 0;
-	if (n_streams == 1)
-		pitch_words = n_words;
-	CallScope scope;
-	hipStream_t q = scope_stream();
-	// (a 40-bit pattern with up to four errors matches noise at one offset in ten million)
-	const uint64_t guess = search_bits / 16384 * n_streams + 4096;
-	lf_adv_guess = guess > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)guess;
-	lf_span_updates = span ? (int)span->max_updates : -1;
-	LeDiscHostRun r;
-	rc = le_disc_host_chain(words, n_words, pitch_words, n_streams, search_bits, phys_channel, max_len, min_count, conn_cap,
-				le_follow_host_tail, &r);
-	if (rc)
-		return rc;
-	if (n_cands_out)
-		*n_cands_out = r.count;
-	if (!r.have)
-		return 0;
-	const uint64_t nc = std::min<uint64_t>(r.n_conns, r.dev_conns), nk = std::min<uint64_t>(r.have, cand_cap);
-	void *spill = nullptr;                                  // a second advertising block, when the first was too small
-	if (nc) {
-		char *scratch = r.tail;
-		btbbx_le_track *d_tracks = (btbbx_le_track *)(scratch + ld_up(le_track_layout(r.dev_cap, r.dev_conns).total));
-		btbbx_le_track_pkt *d_pkts = (btbbx_le_track_pkt *)((char *)d_tracks + ld_up((size_t)r.dev_conns * sizeof(btbbx_le_track)));
-		char *own = r.tail + le_track_host_tail(r.dev_cap, r.dev_conns);
-		btbbx_le_seed *d_seeds = (btbbx_le_seed *)own;
-		char *fscratch = own + ld_up((size_t)r.dev_conns * sizeof(btbbx_le_seed));
-		size_t last_scratch, last_conn, last_cand, last_recs;
-		le_follow_last_sizes(r.dev_cap, r.dev_conns, last_scratch, last_conn, last_cand, last_recs);
-		char *d_per_conn = fscratch + ld_up(last_scratch), *d_per_cand = d_per_conn + ld_up(last_conn);
-		char *d_recs = d_per_cand + ld_up(last_cand);
-		btbbx_le_follow *d_follows = (btbbx_le_follow *)d_per_conn;
-		btbbx_le_follow_pkt *d_fpkts = (btbbx_le_follow_pkt *)d_per_cand;
-		char *ablock = d_recs + ld_up(last_recs);
-		// the advertising scan, repeated with room for every match when the block was too small
-		uint32_t adv_cap = lf_adv_guess, adv_count = 0;
-		for (int pass = 0; pass < 2; pass++) {
-			HIP_TRY(hipMemsetAsync(ablock, 0, sizeof(uint32_t), q));
-			rc = le_launch_scan(r.d_words, n_words, pitch_words, n_streams, search_bits, BTBBX_LE_ADV_AA, adv_errors,
-					    (btbbx_hit *)(ablock + le_follow_adv_layout(adv_cap).hits), adv_cap, (uint32_t *)ablock, q);
-			if (rc)
-				break;
-			hipError_t e = hipMemcpyAsync(&adv_count, ablock, sizeof(adv_count), hipMemcpyDeviceToHost, q);
-			if (e == hipSuccess)
-				e = hipStreamSynchronize(q);
-			if (e != hipSuccess) {
-				rc = hip_fail(e, "advertising scan");
-				break;
-			}
-			if (adv_count <= adv_cap || pass)
-				break;
-			adv_cap = adv_count;
-			if (hipMalloc(&spill, le_follow_adv_layout(adv_cap).total) != hipSuccess) {
-				set_error("%s: advertising block of %zu bytes failed", who, le_follow_adv_layout(adv_cap).total);
-				return BTBBX_E_NOMEM;
-			}
-			ablock = (char *)spill;
-		}
-		const LfAdvLayout A = le_follow_adv_layout(adv_cap);
-		btbbx_le_pkt *d_adv = (btbbx_le_pkt *)(ablock + A.pkts);
-		if (!rc && std::min(adv_count, adv_cap) >= 2)
-			rc = btbbx_order_hits_device((btbbx_hit *)(ablock + A.hits), (uint32_t *)ablock, adv_cap, ablock + A.order, A.pkts - A.order, q);
-		if (!rc)
-			rc = btbbx_le_decode_hits_device(r.d_words, n_words, pitch_words, (btbbx_hit *)(ablock + A.hits), (uint32_t *)ablock, adv_cap,
-							 r.d_phys, BTBBX_LE_ADV_CRC_INIT, d_adv, q);
-		if (!rc)
-			rc = le_track_launch(r.d_cands, r.d_count, r.dev_cap, r.d_conn_count, r.dev_conns, r.d_phys, n_streams, unit_bits, ifs_bits,
-					     jitter_bits, flags, d_tracks, d_pkts, scratch, q);
-		if (!rc)
-			rc = btbbx_le_seed_device(d_adv, (uint32_t *)ablock, adv_cap, r.d_conns, r.d_conn_count, r.dev_conns, d_tracks, unit_bits,
-						  d_seeds, q);
-		if (!rc && !span)
-			rc = le_follow_launch(r.d_words, n_words, pitch_words, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count,
-					      r.dev_conns, d_pkts, d_seeds, unit_bits, jitter_bits, d_follows, d_fpkts, fscratch, q);
-		if (!rc && span)
-			rc = le_span_launch(r.d_words, n_words, pitch_words, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count,
-					    r.dev_conns, d_pkts, d_seeds, unit_bits, jitter_bits, span->max_updates, (btbbx_le_span *)d_per_conn,
-					    (btbbx_le_span_pkt *)d_per_cand, (btbbx_le_span_rec *)d_recs, fscratch, q);
-		hipError_t e = hipSuccess;
-		auto out = [&](void *dst, const void *src, size_t bytes) {
-			if (!rc && e == hipSuccess && dst && bytes)
-				e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, q);
-		};
-		out(conns, r.d_conns, (size_t)nc * sizeof(btbbx_le_conn));
-		out(tracks, d_tracks, (size_t)nc * sizeof(btbbx_le_track));
-		out(seeds, d_seeds, (size_t)nc * sizeof(btbbx_le_seed));
-		out(pkts, d_pkts, (size_t)nk * sizeof(btbbx_le_track_pkt));
-		if (span) {
-			// (the device records of connection g stand at g * (max_updates + 1), whatever dev_conns is: the first nc of them)
-			out(span->spans, d_per_conn, (size_t)nc * sizeof(btbbx_le_span));
-			out(span->span_pkts, d_per_cand, (size_t)nk * sizeof(btbbx_le_span_pkt));
-			out(span->span_recs, d_recs, (size_t)nc * (span->max_updates + 1) * sizeof(btbbx_le_span_rec));
-		} else {
-			out(follows, d_follows, (size_t)nc * sizeof(btbbx_le_follow));
-			out(follow_pkts, d_fpkts, (size_t)nk * sizeof(btbbx_le_follow_pkt));
-		}
-		out(cands, r.d_cands, (size_t)nk * sizeof(btbbx_le_cand));
-		const hipError_t e2 = hipStreamSynchronize(q);           // (before the spill block goes, whatever happened)
-		if (spill)
-			(void)hipFree(spill);
-		if (rc)
-			return rc;
-		if (e != hipSuccess || e2 != hipSuccess)
-			return hip_fail(e != hipSuccess ? e : e2, span ? "btbbx_le_span_host: copy out" : "btbbx_le_epoch_host: copy out");
-		return (int64_t)r.n_conns;
-	}
-	if (nk) {
-		if (pkts)
-			memset(pkts, 0xff, (size_t)nk * sizeof(btbbx_le_track_pkt));    // (no connection stored: no candidate is a member)
-		if (follow_pkts)
-			memset(follow_pkts, 0xff, (size_t)nk * sizeof(btbbx_le_follow_pkt));
-		if (span && span->span_pkts)
-			memset(span->span_pkts, 0xff, (size_t)nk * sizeof(btbbx_le_span_pkt));
-		HIP_TRY(hipMemcpyAsync(cands, r.d_cands, (size_t)nk * sizeof(btbbx_le_cand), hipMemcpyDeviceToHost, q));
-	}
-	HIP_TRY(hipStreamSynchronize(q));
-	return (int64_t)r.n_conns;
-}
-
-extern "C" int64_t btbbx_le_epoch_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
-					uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
-					btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
-					uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
-					int adv_errors, btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_seed *seeds,
-					btbbx_le_follow *follows, btbbx_le_follow_pkt *follow_pkts)
-{
-	return le_follow_host_chain("btbbx_le_epoch_host", words, n_words, pitch_words, n_streams, search_bits, phys_channel, max_len, min_count,
-				    conns, conn_cap, cands, cand_cap, n_cands_out, unit_bits, ifs_bits, jitter_bits, flags, adv_errors, tracks, pkts,
-				    seeds, follows, follow_pkts, nullptr);
 }

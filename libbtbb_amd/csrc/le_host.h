@@ -1,0 +1,568 @@
+// le_host.h -- the host wrappers of the LE stages (included by le.hip, behind le_data.h).  Every wrapper runs one chain: the
+// capture goes to the device, the discovery scans and groups it, the tracking works on what the discovery stored, the wrapper's own
+// stages follow on the same stream and the records are copied out.  The chain is written here once:
+//
+//   le_disc_host_chain    copy in, scan (twice when the first guess was too small), group; the caller's tail behind the block
+//   le_host_check         the argument checks every wrapper behind the discovery makes
+//   le_host_begin         the discovery chain with the tracking's part of the tail and the wrapper's own behind it
+//   le_host_track         the tracking's launches
+//   le_host_finish        the copy-out, or the fill of the per-candidate arrays when no connection was stored
+//
+// A wrapper calls these in this order, launches its own stages between le_host_track and le_host_finish, and names its own
+// outputs (LeHostOut).  Nothing of one call outlives it: what a tail's size depends on is captured by the callable that computes it.
+#pragma once
+#include "le_data.h"
+
+// What the discovery leaves on the device, inside the caller's CallScope: the counters, the sorted candidates, the connection
+// records and, behind them, `tail` (tail_bytes(dev_cap, dev_conns) bytes for what a caller runs next on the same stream).
+struct LeDiscHostRun {
+	uint32_t dev_cap, dev_conns;                   // what the device buffers hold
+	uint32_t count, have, n_conns;                 // candidates found, candidates kept (min(count, dev_cap)), connections found
+	uint32_t *d_count, *d_conn_count;
+	btbbx_le_cand *d_cands;
+	btbbx_le_conn *d_conns;
+	const uint16_t *d_phys;
+	const uint64_t *d_words;                       // the capture as it was copied in
+	char *tail;
+};
+
+// copy in, scan (again with room for every candidate when the first guess was too small, as btbbx_scan_host does), group; both
+// counts read back.  have == 0: nothing was grouped and nothing but count is set
+template <class Tail>
+static int le_disc_host_chain(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, uint64_t search_bits,
+			      const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count, uint64_t conn_cap, Tail tail_bytes,
+			      LeDiscHostRun *r)
+{
+	int rc;
+	if (n_streams == 1)
+		pitch_words = n_words;
+	hipStream_t q = scope_stream();
+	const uint64_t cap_words = (uint64_t)(n_streams - 1) * pitch_words + n_words;
+	const size_t words_bytes = ((size_t)(cap_words + 1) * 8 + 255) & ~(size_t)255;
+	char *dblock = (char *)scope_device(words_bytes + 2 * (size_t)n_streams);
+	if (!dblock)
+		return BTBBX_E_NOMEM;
+	const uint64_t *d_words = (const uint64_t *)dblock;
+	uint16_t *d_phys = (uint16_t *)(dblock + words_bytes);
+	HIP_TRY(hipMemcpyAsync(dblock, words, (size_t)cap_words * 8, hipMemcpyHostToDevice, q));
+	HIP_TRY(hipMemcpyAsync(d_phys, phys_channel, 2 * (size_t)n_streams, hipMemcpyHostToDevice, q));
+	// first guess: one candidate per 4096 offsets + slack (noise yields one per 37 000 at max_len 27, one per 4000 at 255)
+	uint64_t guess = search_bits / 4096 * n_streams + 4096;
+	uint32_t dev_cap = guess > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)guess;
+	uint32_t count = 0;
+	char *block = nullptr;
+	size_t cand_bytes = 0, scratch_bytes = 0, conn_bytes = 0;
+	uint32_t dev_conns = 0;
+	for (int pass = 0; pass < 2; pass++) {
+		cand_bytes = ld_up((size_t)dev_cap * sizeof(btbbx_le_cand));
+		scratch_bytes = ld_up(btbbx_le_discover_scratch_bytes(dev_cap));
+		dev_conns = (uint32_t)std::min<uint64_t>(conn_cap, dev_cap);
+		conn_bytes = ld_up((size_t)dev_conns * sizeof(btbbx_le_conn));
+		block = (char *)scope_hits(256 + cand_bytes + scratch_bytes + conn_bytes + tail_bytes(dev_cap, dev_conns));
+		if (!block)
+			return BTBBX_E_NOMEM;
+		HIP_TRY(hipMemsetAsync(block, 0, 2 * sizeof(uint32_t), q));
+		rc = le_disc_launch_scan(d_words, n_words, pitch_words, n_streams, search_bits, d_phys, max_len, (btbbx_le_cand *)(block + 256),
+					 dev_cap, (uint32_t *)block, q);
+		if (rc)
+			return rc;
+		HIP_TRY(hipMemcpyAsync(&count, block, sizeof(count), hipMemcpyDeviceToHost, q));
+		HIP_TRY(hipStreamSynchronize(q));
+		if (count <= dev_cap)
+			break;
+		dev_cap = count;
+	}
+	r->dev_cap = dev_cap;
+	r->dev_conns = dev_conns;
+	r->count = count;
+	r->have = std::min(count, dev_cap);
+	r->n_conns = 0;
+	r->d_count = (uint32_t *)block;
+	r->d_conn_count = (uint32_t *)block + 1;
+	r->d_cands = (btbbx_le_cand *)(block + 256);
+	r->d_conns = (btbbx_le_conn *)(block + 256 + cand_bytes + scratch_bytes);
+	r->d_phys = d_phys;
+	r->d_words = d_words;
+	r->tail = block + 256 + cand_bytes + scratch_bytes + conn_bytes;
+	if (!r->have)
+		return BTBBX_OK;
+	rc = le_disc_launch_group(r->d_cands, r->d_count, dev_cap, min_count, r->d_conns, dev_conns, r->d_conn_count, block + 256 + cand_bytes, q);
+	if (rc)
+		return rc;
+	HIP_TRY(hipMemcpyAsync(&r->n_conns, r->d_conn_count, sizeof(uint32_t), hipMemcpyDeviceToHost, q));
+	HIP_TRY(hipStreamSynchronize(q));
+	return BTBBX_OK;
+}
+
+// ---- the frame of the wrappers --------------------------------------------------------------------------------------------------
+
+// what every wrapper behind the discovery takes
+struct LeHostArgs {
+	const char *who;
+	const uint64_t *words;
+	uint64_t n_words, pitch_words;
+	uint32_t n_streams;
+	uint64_t search_bits;
+	const uint16_t *phys_channel;
+	uint32_t max_len, min_count;
+	btbbx_le_conn *conns;
+	uint64_t conn_cap;
+	btbbx_le_cand *cands;
+	uint64_t cand_cap;
+	uint64_t *n_cands_out;
+	uint32_t unit_bits, ifs_bits, jitter_bits, flags;
+	btbbx_le_track *tracks;
+	btbbx_le_track_pkt *pkts;
+};
+// a wrapper's LeHostArgs: its parameters carry the fields' names, so the order is written here alone
+#define LE_HOST_ARGS(who)                                                                                                          \
+	{who, words, n_words, pitch_words, n_streams, search_bits, phys_channel, max_len, min_count, conns, conn_cap, cands, cand_cap,  \
+	 n_cands_out, unit_bits, ifs_bits, jitter_bits, flags, tracks, pkts}
+
+// the tracking's part of the tail, as offsets from LeDiscHostRun::tail
+struct LtHostTail {
+	size_t scratch, tracks, pkts, total;
+};
+
+static LtHostTail le_track_host_layout(uint32_t dev_cap, uint32_t dev_conns)
+{
+	LtHostTail T;
+	T.scratch = 0;
+	T.tracks = ld_up(le_track_layout(dev_cap, dev_conns).total);
+	T.pkts = T.tracks + ld_up((size_t)dev_conns * sizeof(btbbx_le_track));
+	T.total = T.pkts + ld_up((size_t)dev_cap * sizeof(btbbx_le_track_pkt));
+	return T;
+}
+
+static size_t le_track_host_tail(uint32_t dev_cap, uint32_t dev_conns) { return le_track_host_layout(dev_cap, dev_conns).total; }
+
+struct LeHostRun : LeDiscHostRun {
+	hipStream_t q;
+	uint64_t nc, nk;                               // the connections and the candidates that are copied out
+	btbbx_le_track *d_tracks;
+	btbbx_le_track_pkt *d_pkts;
+	char *own;                                     // the wrapper's own part of the tail, behind the tracking's
+};
+
+// an output of a wrapper beyond conns / tracks / pkts / cands: one record of `size` bytes per connection, or per candidate; a
+// per-candidate array is filled with 0xff when no connection was stored (no candidate is a member then)
+struct LeHostOut {
+	void *dst;
+	const void *src;
+	size_t size;
+	bool per_cand;
+};
+
+// adv_errors: NULL when the wrapper scans no advertising channel; missing: one of the wrapper's own outputs is NULL and must not be
+static int le_host_check(const LeHostArgs &a, const int *adv_errors, bool missing)
+{
+	int rc = le_disc_check_args(a.who, a.n_words, a.pitch_words, a.n_streams, a.search_bits, a.max_len);
+	if (!rc && adv_errors)
+		rc = le_check_args(a.who, a.n_words, a.pitch_words, a.n_streams, a.search_bits, *adv_errors);
+	if (!rc)
+		rc = le_track_check_args(a.who, a.n_streams, a.unit_bits, a.jitter_bits);
+	if (rc)
+		return rc;
+	if (!a.words || !a.phys_channel || ((!a.conns || !a.tracks) && a.conn_cap) || (!a.cands && a.cand_cap) || missing) {
+		set_error("%s: null pointer", a.who);
+		return BTBBX_E_ARG;
+	}
+	return ctx_require();
+}
+
+// inside the wrapper's CallScope.  own_tail(dev_cap, dev_conns): the bytes the wrapper needs behind the tracking's.  r->have == 0:
+// the capture held no candidate and the wrapper returns 0
+template <class Tail> static int le_host_begin(const LeHostArgs &a, Tail own_tail, LeHostRun *r)
+{
+	if (a.n_cands_out)
+		*a.n_cands_out = 0;
+	r->q = scope_stream();
+	const int rc = le_disc_host_chain(a.words, a.n_words, a.pitch_words, a.n_streams, a.search_bits, a.phys_channel, a.max_len, a.min_count,
+					  a.conn_cap, [&](uint32_t cap, uint32_t conns) { return le_track_host_tail(cap, conns) + own_tail(cap, conns); },
+					  r);
+	if (rc)
+		return rc;
+	if (a.n_cands_out)
+		*a.n_cands_out = r->count;
+	if (!r->have)
+		return BTBBX_OK;
+	const LtHostTail T = le_track_host_layout(r->dev_cap, r->dev_conns);
+	r->nc = std::min<uint64_t>(r->n_conns, r->dev_conns);
+	r->nk = std::min<uint64_t>(r->have, a.cand_cap);
+	r->d_tracks = (btbbx_le_track *)(r->tail + T.tracks);
+	r->d_pkts = (btbbx_le_track_pkt *)(r->tail + T.pkts);
+	r->own = r->tail + T.total;
+	return BTBBX_OK;
+}
+
+static int le_host_track(const LeHostArgs &a, const LeHostRun &r)
+{
+	return le_track_launch(r.d_cands, r.d_count, r.dev_cap, r.d_conn_count, r.dev_conns, r.d_phys, a.n_streams, a.unit_bits, a.ifs_bits,
+			       a.jitter_bits, a.flags, r.d_tracks, r.d_pkts, r.tail, r.q);
+}
+
+// rc: what the wrapper's launches gave.  With a connection stored: the records are copied out unless rc is set, the stream is
+// synchronised whatever happened, and rc is reported in front of a failed copy.  Returns the wrapper's result
+static int64_t le_host_finish(const LeHostArgs &a, const LeHostRun &r, int rc, const LeHostOut *outs, int n_outs)
+{
+	hipError_t e = hipSuccess;
+	auto out = [&](void *dst, const void *src, size_t bytes) {
+		if (!rc && e == hipSuccess && dst && bytes)
+			e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, r.q);
+	};
+	if (r.nc) {
+		out(a.conns, r.d_conns, (size_t)r.nc * sizeof(btbbx_le_conn));
+		out(a.tracks, r.d_tracks, (size_t)r.nc * sizeof(btbbx_le_track));
+		out(a.pkts, r.d_pkts, (size_t)r.nk * sizeof(btbbx_le_track_pkt));
+		for (int o = 0; o < n_outs; o++)
+			out(outs[o].dst, outs[o].src, (size_t)(outs[o].per_cand ? r.nk : r.nc) * outs[o].size);
+	} else {
+		if (a.pkts)
+			memset(a.pkts, 0xff, (size_t)r.nk * sizeof(btbbx_le_track_pkt));
+		for (int o = 0; o < n_outs; o++)
+			if (outs[o].per_cand && outs[o].dst)
+				memset(outs[o].dst, 0xff, (size_t)r.nk * outs[o].size);
+	}
+	out(a.cands, r.d_cands, (size_t)r.nk * sizeof(btbbx_le_cand));
+	const hipError_t e2 = hipStreamSynchronize(r.q);
+	if (rc)
+		return rc;
+	if (e != hipSuccess || e2 != hipSuccess) {
+		char what[64];
+		snprintf(what, sizeof what, "%s: copy out", a.who);
+		return hip_fail(e != hipSuccess ? e : e2, what);
+	}
+	return (int64_t)r.n_conns;
+}
+
+// ---- discovery, tracking, channel selection #2 ----------------------------------------------------------------------------------
+
+extern "C" int64_t btbbx_le_discover_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+					  uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+					  btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+					  uint64_t *n_cands_out)
+{
+	const char *who = "btbbx_le_discover_host";
+	int rc = le_disc_check_args(who, n_words, pitch_words, n_streams, search_bits, max_len);
+	if (rc)
+		return rc;
+	if (!words || !phys_channel || (!conns && conn_cap) || (!cands && cand_cap)) {
+		set_error("%s: null pointer", who);
+		return BTBBX_E_ARG;
+	}
+	rc = ctx_require();
+	if (rc)
+		return rc;
+	if (n_cands_out)
+		*n_cands_out = 0;
+	CallScope scope;
+	hipStream_t q = scope_stream();
+	LeDiscHostRun r;
+	rc = le_disc_host_chain(words, n_words, pitch_words, n_streams, search_bits, phys_channel, max_len, min_count, conn_cap,
+				[](uint32_t, uint32_t) { return (size_t)0; }, &r);
+	if (rc)
+		return rc;
+	if (n_cands_out)
+		*n_cands_out = r.count;
+	if (!r.have)
+		return 0;
+	const uint64_t nc = std::min<uint64_t>(r.n_conns, r.dev_conns), nk = std::min<uint64_t>(r.have, cand_cap);
+	if (nc)
+		HIP_TRY(hipMemcpyAsync(conns, r.d_conns, (size_t)nc * sizeof(btbbx_le_conn), hipMemcpyDeviceToHost, q));
+	if (nk)
+		HIP_TRY(hipMemcpyAsync(cands, r.d_cands, (size_t)nk * sizeof(btbbx_le_cand), hipMemcpyDeviceToHost, q));
+	HIP_TRY(hipStreamSynchronize(q));
+	return (int64_t)r.n_conns;
+}
+
+extern "C" int64_t btbbx_le_track_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				       uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+				       btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+				       uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+				       btbbx_le_track *tracks, btbbx_le_track_pkt *pkts)
+{
+	const LeHostArgs a = LE_HOST_ARGS("btbbx_le_track_host");
+	int rc = le_host_check(a, nullptr, false);
+	if (rc)
+		return rc;
+	CallScope scope;
+	LeHostRun r;
+	rc = le_host_begin(a, [](uint32_t, uint32_t) { return (size_t)0; }, &r);
+	if (rc || !r.have)
+		return rc;
+	if (r.nc && (rc = le_host_track(a, r)))
+		return rc;
+	return le_host_finish(a, r, 0, nullptr, 0);
+}
+
+extern "C" int64_t btbbx_le_csa2_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				      uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+				      btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+				      uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+				      btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_csa2 *sel, btbbx_le_csa2_pkt *sel_pkts)
+{
+	const LeHostArgs a = LE_HOST_ARGS("btbbx_le_csa2_host");
+	int rc = le_host_check(a, nullptr, !sel && conn_cap);
+	if (rc)
+		return rc;
+	CallScope scope;
+	LeHostRun r;
+	// behind the tracking's part: this stage's scratch, its per-connection and its per-candidate records
+	const auto scratch = [](uint32_t cap, uint32_t conns) { return ld_up(le_csa2_layout(cap, conns).total); };
+	rc = le_host_begin(a, [&](uint32_t cap, uint32_t conns) {
+		return scratch(cap, conns) + ld_up((size_t)conns * sizeof(btbbx_le_csa2)) + ld_up((size_t)cap * sizeof(btbbx_le_csa2_pkt)); }, &r);
+	if (rc || !r.have)
+		return rc;
+	btbbx_le_csa2 *d_sel = (btbbx_le_csa2 *)(r.own + scratch(r.dev_cap, r.dev_conns));
+	btbbx_le_csa2_pkt *d_sel_pkts = (btbbx_le_csa2_pkt *)((char *)d_sel + ld_up((size_t)r.dev_conns * sizeof(btbbx_le_csa2)));
+	if (r.nc && (rc = le_host_track(a, r)))
+		return rc;
+	if (r.nc && (rc = le_csa2_launch(r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count, r.dev_conns, r.d_tracks, r.d_pkts, flags, d_sel,
+					  d_sel_pkts, r.own, r.q)))
+		return rc;
+	const LeHostOut outs[] = {{sel, d_sel, sizeof(btbbx_le_csa2), false}, {sel_pkts, d_sel_pkts, sizeof(btbbx_le_csa2_pkt), true}};
+	return le_host_finish(a, r, 0, outs, 2);
+}
+
+// ---- data extraction ------------------------------------------------------------------------------------------------------------
+
+// this stage's part of the tail, as offsets from LeHostRun::own
+struct LdtHostTail {
+	size_t scratch, data, dpkts, msgs, counts, bytes, total;
+	uint32_t msg_cap;
+	uint64_t byte_cap;
+};
+
+static LdtHostTail le_data_host_layout(uint32_t dev_cap, uint32_t dev_conns, uint64_t msg_cap, uint64_t byte_cap)
+{
+	LdtHostTail T;
+	T.msg_cap = (uint32_t)std::min<uint64_t>(msg_cap, dev_cap);                       // (a message has a START of its own)
+	T.byte_cap = std::min<uint64_t>(byte_cap, 255ull * dev_cap);                     // (and a fragment at most 255 octets)
+	size_t at = 0;
+	auto take = [&](size_t bytes) { const size_t here = at; at += ld_up(bytes); return here; };
+	T.scratch = take(le_data_layout(dev_cap, dev_conns).total);
+	T.data = take((size_t)dev_conns * sizeof(btbbx_le_data));
+	T.dpkts = take((size_t)dev_cap * sizeof(btbbx_le_data_pkt));
+	T.msgs = take((size_t)T.msg_cap * sizeof(btbbx_le_msg));
+	T.counts = take(256);
+	T.bytes = take((size_t)T.byte_cap + 8);
+	T.total = at;
+	return T;
+}
+
+// the messages and their octets are copied behind the frame's synchronize: how many there are is known only then
+extern "C" int64_t btbbx_le_data_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				      uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+				      btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+				      uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+				      btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_data *data, btbbx_le_data_pkt *data_pkts,
+				      btbbx_le_msg *msgs, uint64_t msg_cap, uint64_t *n_msgs_out, uint8_t *bytes, uint64_t byte_cap,
+				      uint64_t *n_bytes_out)
+{
+	const LeHostArgs a = LE_HOST_ARGS("btbbx_le_data_host");
+	int rc = le_host_check(a, nullptr, (!data && conn_cap) || (!msgs && msg_cap) || (!bytes && byte_cap));
+	if (rc)
+		return rc;
+	if (n_msgs_out)
+		*n_msgs_out = 0;
+	if (n_bytes_out)
+		*n_bytes_out = 0;
+	CallScope scope;
+	LeHostRun r;
+	rc = le_host_begin(a, [&](uint32_t cap, uint32_t conns) { return le_data_host_layout(cap, conns, msg_cap, byte_cap).total; }, &r);
+	if (rc || !r.have)
+		return rc;
+	const LdtHostTail T = le_data_host_layout(r.dev_cap, r.dev_conns, msg_cap, byte_cap);
+	btbbx_le_msg *d_msgs = (btbbx_le_msg *)(r.own + T.msgs);
+	uint64_t *d_counts = (uint64_t *)(r.own + T.counts), counts[2] = {0, 0};
+	uint8_t *d_bytes = (uint8_t *)(r.own + T.bytes);
+	if (r.nc) {
+		if ((rc = le_host_track(a, r)))
+			return rc;
+		rc = le_data_launch(r.d_words, n_words, pitch_words, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count, r.dev_conns,
+				    r.d_pkts, (btbbx_le_data *)(r.own + T.data), (btbbx_le_data_pkt *)(r.own + T.dpkts), d_msgs, T.msg_cap,
+				    (uint32_t *)(d_counts + 1), d_bytes, T.byte_cap, d_counts, r.own + T.scratch, r.q);
+		if (rc)
+			return rc;
+		HIP_TRY(hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, r.q));
+	}
+	const LeHostOut outs[] = {{data, r.own + T.data, sizeof(btbbx_le_data), false}, {data_pkts, r.own + T.dpkts, sizeof(btbbx_le_data_pkt), true}};
+	const int64_t ret = le_host_finish(a, r, 0, outs, 2);
+	if (ret < 0 || !r.nc)
+		return ret;
+	const uint64_t n_msgs = (uint32_t)counts[1], have_msgs = std::min<uint64_t>(n_msgs, T.msg_cap);
+	if (n_msgs_out)
+		*n_msgs_out = n_msgs;
+	if (n_bytes_out)
+		*n_bytes_out = counts[0];
+	if (have_msgs) {
+		HIP_TRY(hipMemcpyAsync(msgs, d_msgs, (size_t)have_msgs * sizeof(btbbx_le_msg), hipMemcpyDeviceToHost, r.q));
+		HIP_TRY(hipStreamSynchronize(r.q));
+		uint64_t lo = 0, hi = have_msgs;                        // the stored messages are a prefix: the first that is not
+		while (lo < hi) {
+			const uint64_t mid = lo + (hi - lo) / 2;
+			if (msgs[mid].flags & BTBBX_LE_MSG_STORED)
+				lo = mid + 1;
+			else
+				hi = mid;
+		}
+		const uint64_t stored = lo ? msgs[lo - 1].byte_offset + msgs[lo - 1].bytes : 0;
+		if (stored) {
+			HIP_TRY(hipMemcpyAsync(bytes, d_bytes, (size_t)stored, hipMemcpyDeviceToHost, r.q));
+			HIP_TRY(hipStreamSynchronize(r.q));
+		}
+	}
+	return ret;
+}
+
+// ---- following: the follow stage or the span stage behind the seed stage ---------------------------------------------------------
+
+// the advertising scan's block: the counter, the hits, the ordering's scratch, the decoded records
+struct LfAdvLayout {
+	size_t hits, order, pkts, total;
+};
+
+static LfAdvLayout le_follow_adv_layout(uint32_t cap)
+{
+	LfAdvLayout A;
+	A.hits = 256;
+	A.order = A.hits + ld_up((size_t)cap * sizeof(btbbx_hit));
+	A.pkts = A.order + (cap >= 2 ? ld_up(btbbx_order_hits_scratch_bytes(cap)) : 0);
+	A.total = A.pkts + ld_up((size_t)cap * sizeof(btbbx_le_pkt));
+	return A;
+}
+
+// The advertising scan over the device copy of the capture, repeated with room for every match when `ablock` (room for adv_cap
+// hits) was too small -- in a block of its own then, *spill, which the caller frees behind its last synchronize --, ordered and
+// decoded.  On return ablock begins with the count, adv_cap is what it holds and *d_adv its decoded records
+static int le_follow_host_adv(const LeHostArgs &a, const LeHostRun &r, uint64_t pitch_words, int adv_errors, char *&ablock, uint32_t &adv_cap,
+			      void **spill, btbbx_le_pkt **d_adv)
+{
+	uint32_t adv_count = 0;
+	for (int pass = 0; pass < 2; pass++) {
+		HIP_TRY(hipMemsetAsync(ablock, 0, sizeof(uint32_t), r.q));
+		const int rc = le_launch_scan(r.d_words, a.n_words, pitch_words, a.n_streams, a.search_bits, BTBBX_LE_ADV_AA, adv_errors,
+					      (btbbx_hit *)(ablock + le_follow_adv_layout(adv_cap).hits), adv_cap, (uint32_t *)ablock, r.q);
+		if (rc)
+			return rc;
+		hipError_t e = hipMemcpyAsync(&adv_count, ablock, sizeof(adv_count), hipMemcpyDeviceToHost, r.q);
+		if (e == hipSuccess)
+			e = hipStreamSynchronize(r.q);
+		if (e != hipSuccess)
+			return hip_fail(e, "advertising scan");
+		if (adv_count <= adv_cap || pass)
+			break;
+		adv_cap = adv_count;
+		if (hipMalloc(spill, le_follow_adv_layout(adv_cap).total) != hipSuccess) {
+			set_error("%s: advertising block of %zu bytes failed", a.who, le_follow_adv_layout(adv_cap).total);
+			return BTBBX_E_NOMEM;
+		}
+		ablock = (char *)*spill;
+	}
+	const LfAdvLayout A = le_follow_adv_layout(adv_cap);
+	*d_adv = (btbbx_le_pkt *)(ablock + A.pkts);
+	if (std::min(adv_count, adv_cap) >= 2) {
+		const int rc = btbbx_order_hits_device((btbbx_hit *)(ablock + A.hits), (uint32_t *)ablock, adv_cap, ablock + A.order, A.pkts - A.order, r.q);
+		if (rc)
+			return rc;
+	}
+	return btbbx_le_decode_hits_device(r.d_words, a.n_words, pitch_words, (btbbx_hit *)(ablock + A.hits), (uint32_t *)ablock, adv_cap, r.d_phys,
+					   BTBBX_LE_ADV_CRC_INIT, *d_adv, r.q);
+}
+
+// The chain of btbbx_le_epoch_host and btbbx_le_span_host: the advertising scan, the tracking, the seed stage and the wrapper's
+// last stage -- last(r, pitch_words, d_seeds, d_scratch, d_out): its launches --, whose scratch takes last_scratch(dev_cap, dev_conns)
+// bytes.  outs: the last stage's outputs (at most three; src is not read): their device records stand behind the scratch in this
+// order, dev_conns or dev_cap of them each, and d_out[o] is where those of outs[o] begin.
+// A failed launch does not end the call at once: the stream is synchronised and a spilled advertising block freed first
+template <class Scratch, class Last>
+static int64_t le_follow_host_chain(const LeHostArgs &a, int adv_errors, btbbx_le_seed *seeds, bool missing, Scratch last_scratch,
+				    const LeHostOut *outs, int n_outs, Last last)
+{
+	int rc = le_host_check(a, &adv_errors, (!seeds && a.conn_cap) || missing);
+	if (rc)
+		return rc;
+	const uint64_t pitch_words = a.n_streams == 1 ? a.n_words : a.pitch_words;
+	CallScope scope;
+	// (a 40-bit pattern with up to four errors matches noise at one offset in ten million)
+	const uint64_t guess = a.search_bits / 16384 * a.n_streams + 4096;
+	uint32_t adv_cap = guess > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)guess;
+	// behind the tracking's part: the seeds, the last stage's scratch and records, the advertising scan's block
+	const auto records = [&](uint32_t cap, uint32_t conns, int upto) {
+		size_t at = ld_up((size_t)conns * sizeof(btbbx_le_seed)) + ld_up(last_scratch(cap, conns));
+		for (int o = 0; o < upto; o++)
+			at += ld_up((size_t)(outs[o].per_cand ? cap : conns) * outs[o].size);
+		return at;
+	};
+	LeHostRun r;
+	rc = le_host_begin(a, [&](uint32_t cap, uint32_t conns) { return records(cap, conns, n_outs) + le_follow_adv_layout(adv_cap).total; }, &r);
+	if (rc || !r.have)
+		return rc;
+	void *spill = nullptr;                                  // a second advertising block, when the first was too small
+	btbbx_le_seed *d_seeds = (btbbx_le_seed *)r.own;
+	LeHostOut all[4] = {{seeds, d_seeds, sizeof(btbbx_le_seed), false}};
+	char *d_out[3] = {nullptr, nullptr, nullptr};
+	for (int o = 0; o < n_outs; o++) {
+		d_out[o] = r.own + records(r.dev_cap, r.dev_conns, o);
+		all[o + 1] = {outs[o].dst, d_out[o], outs[o].size, outs[o].per_cand};
+	}
+	if (r.nc) {
+		char *ablock = r.own + records(r.dev_cap, r.dev_conns, n_outs);
+		btbbx_le_pkt *d_adv = nullptr;
+		rc = le_follow_host_adv(a, r, pitch_words, adv_errors, ablock, adv_cap, &spill, &d_adv);
+		if (!rc)
+			rc = le_host_track(a, r);
+		if (!rc)
+			rc = btbbx_le_seed_device(d_adv, (uint32_t *)ablock, adv_cap, r.d_conns, r.d_conn_count, r.dev_conns, r.d_tracks, a.unit_bits,
+						  d_seeds, r.q);
+		if (!rc)
+			rc = last(r, pitch_words, d_seeds, r.own + ld_up((size_t)r.dev_conns * sizeof(btbbx_le_seed)), d_out);
+	}
+	const int64_t ret = le_host_finish(a, r, rc, all, n_outs + 1);
+	if (spill)
+		(void)hipFree(spill);
+	return ret;
+}
+
+extern "C" int64_t btbbx_le_epoch_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+					uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+					btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+					uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+					int adv_errors, btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_seed *seeds,
+					btbbx_le_follow *follows, btbbx_le_follow_pkt *follow_pkts)
+{
+	const LeHostArgs a = LE_HOST_ARGS("btbbx_le_epoch_host");
+	const LeHostOut outs[] = {{follows, nullptr, sizeof(btbbx_le_follow), false}, {follow_pkts, nullptr, sizeof(btbbx_le_follow_pkt), true}};
+	return le_follow_host_chain(
+		a, adv_errors, seeds, !follows && conn_cap, [](uint32_t cap, uint32_t k) { return le_follow_layout(cap, k).total; }, outs, 2,
+		[&](const LeHostRun &r, uint64_t pitch, const btbbx_le_seed *d_seeds, char *d_scratch, char *const *d_out) {
+			return le_follow_launch(r.d_words, n_words, pitch, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count,
+						r.dev_conns, r.d_pkts, d_seeds, unit_bits, jitter_bits, (btbbx_le_follow *)d_out[0],
+						(btbbx_le_follow_pkt *)d_out[1], d_scratch, r.q);
+		});
+}
+
+extern "C" int64_t btbbx_le_span_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				      uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+				      btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+				      uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+				      int adv_errors, btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_seed *seeds,
+				      uint32_t max_updates, btbbx_le_span *spans, btbbx_le_span_pkt *span_pkts, btbbx_le_span_rec *span_recs)
+{
+	const LeHostArgs a = LE_HOST_ARGS("btbbx_le_span_host");
+	if (max_updates > LS_MAX_UPDATES) {
+		set_error("%s: max_updates must be 0..%u", a.who, LS_MAX_UPDATES);
+		return BTBBX_E_ARG;
+	}
+	// (the device records of connection g stand at g * (max_updates + 1), whatever dev_conns is: the first nc of them are copied)
+	const LeHostOut outs[] = {{spans, nullptr, sizeof(btbbx_le_span), false}, {span_pkts, nullptr, sizeof(btbbx_le_span_pkt), true},
+				  {span_recs, nullptr, (max_updates + 1) * sizeof(btbbx_le_span_rec), false}};
+	return le_follow_host_chain(
+		a, adv_errors, seeds, (!spans || !span_recs) && conn_cap,
+		[&](uint32_t cap, uint32_t k) { return le_span_layout(cap, k, max_updates).total; }, outs, 3,
+		[&](const LeHostRun &r, uint64_t pitch, const btbbx_le_seed *d_seeds, char *d_scratch, char *const *d_out) {
+			return le_span_launch(r.d_words, n_words, pitch, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count,
+					      r.dev_conns, r.d_pkts, d_seeds, unit_bits, jitter_bits, max_updates, (btbbx_le_span *)d_out[0],
+					      (btbbx_le_span_pkt *)d_out[1], (btbbx_le_span_rec *)d_out[2], d_scratch, r.q);
+		});
+}

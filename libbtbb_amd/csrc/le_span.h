@@ -15,9 +15,11 @@
 //        le_span_pick_kernel      one lane per candidate: among those with I = I_s in front of it, the largest rank
 //        le_span_bound_kernel     one lane per connection: L by a binary search of the counters, rule 5, f_(s+1) by a binary search of
 //                                 the anchors -- both rise with the event index --, the span's record; or rule 6
-//   d. le_span_mark_kernel, le_span_list_kernel, the radix passes, le_span_rekey_kernel, le_span_gather_kernel   the map updates, as
-//      the follow stage lists them, over the final counters; the list kernel also marks and counts the valid parameter updates
-//   e. le_span_predict_kernel, le_span_verdict_kernel, le_span_pkt_kernel   as the follow stage's 7-9, with the span and GAP
+//   d. le_span_mark_kernel, le_span_list_kernel, then the follow stage's sort (its radix passes, rekey and gather kernels)   the map
+//      updates, as the follow stage lists them, over the final counters; the list kernel also marks and counts the valid parameter
+//      updates
+//   e. le_span_predict_kernel, le_span_verdict_kernel, le_span_pkt_kernel   the follow stage's 7-9 (its lf_predict, lf_tallies,
+//      lf_verdict, lf_pdu_kind and lf_pkt_event), with the span and GAP
 //
 // The count of launches is 13 + 6 * (max_updates + 1) + 3 per radix pass: it depends on max_updates, on conn_cap through the radix
 // passes over its bytes, and on nothing else.  Every loop of a kernel is bounded by N, by max_updates + 1 or by a constant.
@@ -73,11 +75,6 @@ static LsLayout le_span_layout(uint32_t cand_cap, uint32_t conn_cap, uint32_t ma
 	S.sstart = take(k * ((size_t)max_updates + 1) * 4);
 	S.total = at;
 	return S;
-}
-
-static size_t le_span_scratch_total(uint32_t cand_cap, uint32_t conn_cap, uint32_t max_updates)
-{
-	return le_span_layout(cand_cap, conn_cap, max_updates).total;
 }
 
 // ---- a. the parameter updates' fields ---------------------------------------------------------------------------------------
@@ -442,26 +439,10 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_span_mark_kernel(con
 									     const btbbx_le_span_rec *recs, const unsigned long long *step,
 									     uint32_t max_updates, unsigned long long *utiles)
 {
-	__shared__ uint32_t count;
-	const uint32_t tid = threadIdx.x, n = params[0], k = params[1];
-	if (tid == 0)
-		count = 0;
-	__syncthreads();
-	uint32_t mine = 0;
-	for (uint32_t r = 0; r < LT_TILE / LE_THREADS; r++) {
-		const uint32_t q = blockIdx.x * LT_TILE + r * LE_THREADS + tid;
-		if (q >= n)
-			break;
-		uint32_t i, g;
-		unsigned long long at;
-		bool param;
-		mine += ls_update(cands, pkts, conns, seeds, slot, ctl, work, sc, sstart, recs, step, max_updates, q, n, k, i, g, at, param) ? 1u : 0u;
-	}
-	if (mine)
-		atomicAdd(&count, mine);
-	__syncthreads();
-	if (tid == 0)
-		utiles[blockIdx.x] = count;
+	const uint32_t n = params[0], k = params[1];
+	lf_mark_tile(n, utiles, [=](uint32_t q, uint32_t &i, uint32_t &g, unsigned long long &at, bool &param) __attribute__((always_inline)) {
+		return ls_update(cands, pkts, conns, seeds, slot, ctl, work, sc, sstart, recs, step, max_updates, q, n, k, i, g, at, param);
+	});
 }
 
 // as le_epoch_list_kernel; the last tile's carry is the list's length
@@ -473,56 +454,15 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_span_list_kernel(con
 									     const unsigned long long *utiles, uint32_t *uparams, uint64_t *keys,
 									     uint32_t *vals, uint64_t *u_i, uint64_t *u_map, uint32_t *u_conn)
 {
-	__shared__ uint32_t lds[LT_WAVES];
-	const uint32_t tid = threadIdx.x, n = params[0], k = params[1];
-	uint32_t carry = (uint32_t)utiles[blockIdx.x];
-	for (uint32_t r = 0; r < LT_TILE / LE_THREADS; r++) {
-		if (blockIdx.x * LT_TILE + r * LE_THREADS >= n)
-			break;                                          // (uniform over the workgroup)
-		const uint32_t q = blockIdx.x * LT_TILE + r * LE_THREADS + tid;
-		uint32_t i = LF_NONE, g = LF_NONE;
-		unsigned long long at = 0;
-		bool param = false;
-		const bool is = q < n && ls_update(cands, pkts, conns, seeds, slot, ctl, work, sc, sstart, recs, step, max_updates, q, n, k, i, g, at, param);
-		uint32_t sum;
-		const uint32_t ex = block_exclusive_scan<LT_WAVES>(is ? 1u : 0u, lds, sum);
-		if (is) {
-			const uint32_t u = carry + ex;
-			const uint4 info = ctl[i];
-			keys[u] = at;
-			vals[u] = u;
-			u_i[u] = at;
-			u_map[u] = ((uint64_t)info.w << 32) | info.z;
-			u_conn[u] = g;
-			ctl[i].x = info.x | LF_IS_MAP;
-			atomicAdd(&work[g].n_map, 1u);
-		}
-		if (param) {
-			ctl[i].x |= LF_IS_PARAM;
-			atomicAdd(&sc[g].n_param, 1u);
-		}
-		carry += sum;
-	}
-	if (blockIdx.x == gridDim.x - 1 && tid == 0)
-		uparams[0] = uparams[2] = carry;
-}
-
-extern "C" __global__ __launch_bounds__(LE_THREADS) void le_span_rekey_kernel(const uint32_t *uparams, const uint32_t *vals, const uint32_t *u_conn,
-									      uint64_t *keys)
-{
-	const uint32_t j = blockIdx.x * LE_THREADS + threadIdx.x;
-	if (j < uparams[0])
-		keys[j] = u_conn[vals[j]];
-}
-
-extern "C" __global__ __launch_bounds__(LE_THREADS) void le_span_gather_kernel(const uint32_t *uparams, const uint32_t *vals, const uint64_t *u_i,
-									       const uint64_t *u_map, uint64_t *s_i, uint64_t *s_map)
-{
-	const uint32_t j = blockIdx.x * LE_THREADS + threadIdx.x;
-	if (j < uparams[0]) {
-		s_i[j] = u_i[vals[j]];
-		s_map[j] = u_map[vals[j]];
-	}
+	const uint32_t n = params[0], k = params[1];
+	lf_list_tile<false>(n, utiles, uparams, ctl, work, keys, vals, u_i, u_map, u_conn,
+			    [=](uint32_t q, uint32_t &i, uint32_t &g, unsigned long long &at, bool &param) __attribute__((always_inline)) {
+				    return ls_update(cands, pkts, conns, seeds, slot, ctl, work, sc, sstart, recs, step, max_updates, q, n, k, i, g, at, param);
+			    },
+			    [=](uint32_t i, uint32_t g) __attribute__((always_inline)) {
+				    ctl[i].x |= LF_IS_PARAM;
+				    atomicAdd(&sc[g].n_param, 1u);
+			    });
 }
 
 // ---- e. prediction, verdict, packets ----------------------------------------------------------------------------------------------
@@ -543,58 +483,25 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_span_predict_kernel(
 	bool before = false, gap = false, beyond = false, pred = false, on1 = false, on2 = false;
 	uint32_t e = 0;
 	if (live) {
-		const uint32_t first = (uint32_t)conns[g].first, hop = seeds[g].hop;
+		LfEvent ev = {0, 0xff, 0xff};
+		const uint32_t first = (uint32_t)conns[g].first;
 		const uint64_t a = anchor[q];
-		const uint32_t ch = (uint32_t)(a >> 56);
 		e = q - first;
 		bool early;
 		const uint32_t span = ls_span_of(sc, sstart, recs, g, e, max_updates, early);
-		uint32_t exp1 = 0xff, exp2 = 0xff, epoch = 0, counter = 0, state = span ? BTBBX_LE_STATE_GAP : BTBBX_LE_STATE_BEFORE;
+		uint32_t counter = 0, state = span ? BTBBX_LE_STATE_GAP : BTBBX_LE_STATE_BEFORE;
 		before = early && !span;
 		gap = early && span;
 		if (!early) {
 			const unsigned long long c = lf_counter(step, first, q);
-			const uint32_t u = uparams[0], lo = lf_lower(s_conn, u, g), hi = lf_upper(s_conn, s_i, u, g, c);
-			epoch = hi - lo;
+			pred = lf_predict(seeds + g, conns + g, g, c, &sc[g].stop, (uint32_t)(a >> 56), s_conn, s_i, s_map, uparams[0], ev, on1, on2);
 			counter = (uint32_t)c;
-			beyond = c >= sc[g].stop;
+			beyond = !pred;
 			state = beyond ? BTBBX_LE_STATE_BEYOND : BTBBX_LE_STATE_COUNTED;
-			if (!beyond) {
-				const unsigned long long map = (epoch ? s_map[hi - 1] : seeds[g].map) & LC_MAP37;
-				const uint32_t n_used = (uint32_t)__popcll(map);
-				pred = true;
-				if (n_used) {
-					const uint32_t un = (hop * (uint32_t)((c + 1) % 37ull)) % 37u;
-					exp1 = (map >> un) & 1 ? un : lt_nth_bit(map, un % n_used);
-					uint32_t unmapped;
-					exp2 = lc_expected(lc_prn((uint32_t)c & 0xffffu, lc_channel_id(conns[g].access_address)), map, n_used,
-							   BTBBX_LE_CSA2_REMAP, unmapped);
-				}
-				on1 = exp1 == ch;
-				on2 = exp2 == ch;
-			}
 		}
-		evres[q] = make_uint4(exp1 | (exp2 << 8) | (state << 16), epoch, counter, span);
+		evres[q] = make_uint4(ev.exp1 | (ev.exp2 << 8) | (state << 16), ev.epoch, counter, span);
 	}
-	// (the runs of le_epoch_predict_kernel: one atomic per tally, connection and wave)
-	const uint32_t pg = __shfl_up(g, 1);
-	const bool head = live && (lane == 0 || pg != g);
-	const uint64_t heads = __ballot(head), upto = lane == 63 ? ~0ULL : (2ULL << lane) - 1;
-	uint64_t run = 0;
-	if (head) {
-		const uint64_t behind = heads & ~upto;
-		run = (behind ? (1ULL << __builtin_ctzll(behind)) - 1 : ~0ULL) & ~(upto >> 1);
-	}
-	LfConn *w = work + (live ? g : 0);
-	lf_tally(head, run, before, &w->n_before);
-	lf_tally(head, run, gap, &sc[live ? g : 0].n_gap);
-	lf_tally(head, run, beyond, &w->n_beyond);
-	lf_tally(head, run, pred, &w->n_pred);
-	lf_tally(head, run, on1, &w->on1);
-	lf_tally(head, run, on2, &w->on2);
-	const uint32_t ng = __shfl_down(g, 1), np = __shfl_down(pred ? 1u : 0u, 1);
-	if (pred && (lane == 63 || ng != g || !np))
-		atomicMax(&work[g].last_pred, e + 1);
+	lf_tallies(g, live, lane, e, before, gap, beyond, pred, on1, on2, work, &sc[live ? g : 0].n_gap);
 }
 
 extern "C" __global__ __launch_bounds__(LE_THREADS) void le_span_verdict_kernel(const btbbx_le_conn *conns, const btbbx_le_seed *seeds,
@@ -614,30 +521,17 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_span_verdict_kernel(
 		return;
 	}
 	const LfConn w = work[g];
-	const btbbx_le_seed s = seeds[g];
-	const uint2 f = reinterpret_cast<const uint2 *>(conns + g)[3];
-	const bool counted = w.n_pred + w.n_beyond != 0;
-	const uint32_t algorithm = s.chsel && w.on2 >= w.on1 ? 2u : 1u, n_on = algorithm == 2 ? w.on2 : w.on1;
-	uint32_t c_first = 0;
-	unsigned long long map = s.map;
-	if (counted && !f.y && f.x < n && w.n_before < n - f.x) {
-		c_first = (uint32_t)lf_counter(step, f.x, f.x + w.n_before);
-		if (w.last_pred) {
-			const uint32_t epoch = evres[f.x + w.last_pred - 1].y;
-			if (epoch)
-				map = s_map[lf_lower(s_conn, uparams[0], g) + epoch - 1] & LC_MAP37;
-		}
-	}
-	uint32_t flags = BTBBX_LE_FOLLOW_SEEDED | (counted ? BTBBX_LE_FOLLOW_COUNTED : 0u) | w.flags | sc[g].flags;
+	const LfVerdict v = lf_verdict(w, seeds[g], reinterpret_cast<const uint2 *>(conns + g)[3], g, n, uparams, step, s_conn, s_map, evres);
+	uint32_t flags = v.flags | sc[g].flags;
 	if (w.enc_rank != LF_NONE)
 		flags |= BTBBX_LE_FOLLOW_ENCRYPTED;
-	out[0] = make_uint2((uint32_t)map, (uint32_t)(map >> 32));
-	out[1] = make_uint2(c_first, (uint32_t)sc[g].stop);
-	out[2] = make_uint2(w.n_before, n_on);
-	out[3] = make_uint2(w.n_pred - n_on, w.n_beyond);
+	out[0] = make_uint2((uint32_t)v.map, (uint32_t)(v.map >> 32));
+	out[1] = make_uint2(v.c_first, (uint32_t)sc[g].stop);
+	out[2] = make_uint2(w.n_before, v.n_on);
+	out[3] = make_uint2(w.n_pred - v.n_on, w.n_beyond);
 	out[4] = make_uint2(sc[g].n_gap, w.n_control);
 	out[5] = make_uint2(w.n_map, sc[g].n_param);
-	out[6] = make_uint2(sc[g].s + 1, (sc[g].interval & 0xffffu) | (algorithm << 16) | (flags << 24));
+	out[6] = make_uint2(sc[g].s + 1, (sc[g].interval & 0xffffu) | (v.algorithm << 16) | (flags << 24));
 }
 
 extern "C" __global__ __launch_bounds__(LE_THREADS) void le_span_pkt_kernel(const btbbx_le_cand *cands, const btbbx_le_track_pkt *pkts,
@@ -651,38 +545,15 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_span_pkt_kernel(cons
 	uint32_t g, first;
 	uint4 p, o = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
 	if (lf_member(cands, pkts, conns, i, n, k, g, p, first)) {
-		const uint32_t x = ctl[i].x, opcode = (x >> 8) & 0xffu, len = (x >> 16) & 0xffu, enc = work[g].enc_rank;
-		uint32_t kind = BTBBX_LE_PDU_DATA, op = 0xff, applied = 0;
-		if (x & LF_CONTROL) {
-			if (p.x > enc) {
-				kind = BTBBX_LE_PDU_OPAQUE;
-			} else {
-				op = opcode;
-				kind = BTBBX_LE_PDU_CONTROL;
-				if (opcode == 5 && len == 1)
-					kind = BTBBX_LE_PDU_ENC_START;
-				else if (opcode == 2 && len == 2)
-					kind = BTBBX_LE_PDU_TERMINATE;
-				else if (x & LF_IS_MAP)
-					kind = BTBBX_LE_PDU_MAP_UPDATE;
-				else if (x & LF_IS_PARAM)
-					kind = BTBBX_LE_PDU_PARAM_UPDATE;
-			}
-		}
-		uint32_t counter = 0, epoch = 0, span = 0, expected = 0xff, on = 0, state = 0;
+		const uint32_t x = ctl[i].x;
+		uint32_t op, applied = 0;
+		const uint32_t kind = lf_pdu_kind(x, p.x, work[g].enc_rank, op);
+		LfPktEvent e = {0, 0, 0, 0, 0xff, 0};
 		if (lf_seeded(seeds, g)) {
-			const uint4 ev = evres[first + p.y];
-			state = (ev.x >> 16) & 0xffu;
-			epoch = ev.y < 0xffffu ? ev.y : 0xffffu;
-			counter = ev.z;
-			span = ev.w;
+			lf_pkt_event(evres[first + p.y], &spans[g].algorithm, p.w & 0xffu, e);
 			applied = (x & LS_APPLIED) ? 1u : 0u;
-			if (state == BTBBX_LE_STATE_COUNTED) {
-				expected = spans[g].algorithm == 2 ? (ev.x >> 8) & 0xffu : ev.x & 0xffu;
-				on = expected == (p.w & 0xffu) ? 1u : 0u;
-			}
 		}
-		o = make_uint4(counter, epoch | (span << 16), kind | (op << 8) | (expected << 16) | (on << 24), state | (applied << 8));
+		o = make_uint4(e.counter, e.epoch | (e.span << 16), kind | (op << 8) | (e.expected << 16) | (e.on << 24), e.state | (applied << 8));
 	}
 	reinterpret_cast<uint4 *>(out)[i] = o;
 }
@@ -694,76 +565,50 @@ extern "C" size_t btbbx_le_span_scratch_bytes(uint32_t cand_cap, uint32_t conn_c
 	return le_span_layout(cand_cap, conn_cap, max_updates > LS_MAX_UPDATES ? LS_MAX_UPDATES : max_updates).total;
 }
 
-// the launches of one run: 13 kernels, 6 per round, 3 per radix pass (6 over I, 1 to 4 over conn_cap)
+// the launches of one run: 13 kernels -- 5 of them the follow stage's, 1 the tracking's --, 6 per round, 3 per radix pass (6 over I, 1 to 4
+// over conn_cap)
 static int le_span_launch(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, const btbbx_le_cand *d_cands,
 			  const uint32_t *d_count, uint32_t cap, const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
 			  const btbbx_le_track_pkt *d_pkts, const btbbx_le_seed *d_seeds, uint32_t unit_bits, uint32_t jitter_bits,
 			  uint32_t max_updates, btbbx_le_span *d_spans, btbbx_le_span_pkt *d_spkts, btbbx_le_span_rec *d_recs, void *d_scratch,
 			  hipStream_t q)
 {
-	const LfLayout L = le_follow_layout(cap, conn_cap);
+	const LfBufs B = le_follow_bufs(d_scratch, cap, conn_cap);
 	const LsLayout S = le_span_layout(cap, conn_cap, max_updates);
 	char *s = (char *)d_scratch;
-	uint32_t *params = (uint32_t *)(s + L.params), *uparams = (uint32_t *)(s + L.uparams), *slot = (uint32_t *)(s + L.slot);
-	uint32_t *econn = (uint32_t *)(s + L.econn), *u_conn = (uint32_t *)(s + L.u_conn), *sstart = (uint32_t *)(s + S.sstart);
-	uint64_t *anchor = (uint64_t *)(s + L.anchor), *u_i = (uint64_t *)(s + L.u_i), *u_map = (uint64_t *)(s + L.u_map);
-	uint64_t *s_i = (uint64_t *)(s + L.s_i), *s_map = (uint64_t *)(s + L.s_map);
-	unsigned long long *step = (unsigned long long *)(s + L.step), *tiles64 = (unsigned long long *)(s + L.tiles64);
+	uint32_t *sstart = (uint32_t *)(s + S.sstart);
 	unsigned long long *kk = (unsigned long long *)(s + S.kk);
-	uint4 *ctl = (uint4 *)(s + L.ctl), *evres = (uint4 *)(s + L.evres);
 	uint2 *prm = (uint2 *)(s + S.prm);
-	LfConn *work = (LfConn *)(s + L.work);
 	LsConn *sc = (LsConn *)(s + S.sc);
-	RadixBufs b;
-	b.keys[0] = (uint64_t *)(s + L.keys[0]);
-	b.keys[1] = (uint64_t *)(s + L.keys[1]);
-	b.vals[0] = (uint32_t *)(s + L.vals[0]);
-	b.vals[1] = (uint32_t *)(s + L.vals[1]);
-	b.hist = (uint32_t *)(s + L.hist);
-	b.tot = (uint32_t *)(s + L.tot);
-	b.params = uparams;
-	b.cap = cap;
-	const dim3 per_cand((cap + LE_THREADS - 1) / LE_THREADS), per_tile(L.tiles_n), per_conn((conn_cap + LE_THREADS - 1) / LE_THREADS), wg(LE_THREADS);
-	const uint32_t init_grid = (uint32_t)(((uint64_t)std::max(cap, conn_cap) + LE_THREADS - 1) / LE_THREADS);
-	hipLaunchKernelGGL(le_epoch_init_kernel, dim3(init_grid), wg, 0, q, d_count, cap, d_conn_count, conn_cap, params, uparams, slot, econn, work);
-	hipLaunchKernelGGL(le_epoch_slot_kernel, per_cand, wg, 0, q, d_words, n_words, pitch_words, n_streams, d_cands, d_pkts, d_conns, params, slot,
-			   ctl, work);
-	hipLaunchKernelGGL(le_epoch_open_kernel, per_cand, wg, 0, q, d_cands, d_pkts, d_conns, params, slot, anchor, econn);
-	hipLaunchKernelGGL(le_span_param_kernel, per_cand, wg, 0, q, d_words, n_words, pitch_words, n_streams, d_cands, d_pkts, d_conns, d_seeds, params,
-			   ctl, prm, work);
-	hipLaunchKernelGGL(le_span_begin_kernel, per_conn, wg, 0, q, d_conns, d_seeds, params, econn, anchor, jitter_bits, max_updates, sc, sstart,
-			   d_recs);
+	const dim3 per_cand((cap + LE_THREADS - 1) / LE_THREADS), per_tile(B.tiles_n), per_conn((conn_cap + LE_THREADS - 1) / LE_THREADS), wg(LE_THREADS);
+	le_follow_open(B, d_words, n_words, pitch_words, n_streams, d_cands, d_count, cap, d_conns, d_conn_count, conn_cap, d_pkts, q);
+	hipLaunchKernelGGL(le_span_param_kernel, per_cand, wg, 0, q, d_words, n_words, pitch_words, n_streams, d_cands, d_pkts, d_conns, d_seeds,
+			   B.params, B.ctl, prm, B.work);
+	hipLaunchKernelGGL(le_span_begin_kernel, per_conn, wg, 0, q, d_conns, d_seeds, B.params, B.econn, B.anchor, jitter_bits, max_updates, sc,
+			   sstart, d_recs);
 	for (uint32_t round = 0; round <= max_updates; round++) {
-		hipLaunchKernelGGL(le_span_step_kernel, per_tile, wg, 0, q, anchor, econn, d_conns, d_seeds, params, sc, unit_bits, kk, step, tiles64);
-		hipLaunchKernelGGL(le_track_prefix64_kernel, dim3(1), wg, 0, q, tiles64, L.tiles_n);
-		hipLaunchKernelGGL(le_track_count_kernel, per_tile, wg, 0, q, params, tiles64, step);
-		hipLaunchKernelGGL(le_span_instant_kernel, per_cand, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, params, ctl, work, step, sc);
-		hipLaunchKernelGGL(le_span_pick_kernel, per_cand, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, params, ctl, work, step, sc);
-		hipLaunchKernelGGL(le_span_bound_kernel, per_conn, wg, 0, q, d_conns, params, slot, anchor, step, ctl, prm, unit_bits, jitter_bits,
-				   max_updates, sc, sstart, d_recs);
+		hipLaunchKernelGGL(le_span_step_kernel, per_tile, wg, 0, q, B.anchor, B.econn, d_conns, d_seeds, B.params, sc, unit_bits, kk, B.step,
+				   B.tiles64);
+		hipLaunchKernelGGL(le_track_prefix64_kernel, dim3(1), wg, 0, q, B.tiles64, B.tiles_n);
+		hipLaunchKernelGGL(le_track_count_kernel, per_tile, wg, 0, q, B.params, B.tiles64, B.step);
+		hipLaunchKernelGGL(le_span_instant_kernel, per_cand, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, B.params, B.ctl, B.work, B.step, sc);
+		hipLaunchKernelGGL(le_span_pick_kernel, per_cand, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, B.params, B.ctl, B.work, B.step, sc);
+		hipLaunchKernelGGL(le_span_bound_kernel, per_conn, wg, 0, q, d_conns, B.params, B.slot, B.anchor, B.step, B.ctl, prm, unit_bits,
+				   jitter_bits, max_updates, sc, sstart, d_recs);
 	}
 	// (the tile counts of the update list go through the 64-bit prefix sum, in the step's tile sums, which are free now)
-	hipLaunchKernelGGL(le_span_mark_kernel, per_tile, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, params, slot, ctl, work, sc, sstart, d_recs, step,
-			   max_updates, tiles64);
-	hipLaunchKernelGGL(le_track_prefix64_kernel, dim3(1), wg, 0, q, tiles64, L.tiles_n);
-	hipLaunchKernelGGL(le_span_list_kernel, per_tile, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, params, slot, ctl, work, sc, sstart, d_recs, step,
-			   max_updates, tiles64, uparams, b.keys[0], b.vals[0], u_i, u_map, u_conn);
-	RadixPass passes[6];
-	for (int p = 0; p < 6; p++)
-		passes[p] = {0, 8u * p};
-	int cur = radix_sort_passes(b, nullptr, passes, 6, 0, q);
-	hipLaunchKernelGGL(le_span_rekey_kernel, per_cand, wg, 0, q, uparams, b.vals[cur], u_conn, b.keys[cur]);
-	int conn_passes = 1;
-	while (conn_passes < 4 && (conn_cap >> (8 * conn_passes)))
-		conn_passes++;
-	cur = radix_sort_passes(b, nullptr, passes, conn_passes, cur, q);
-	const uint64_t *s_conn = b.keys[cur];
-	hipLaunchKernelGGL(le_span_gather_kernel, per_cand, wg, 0, q, uparams, b.vals[cur], u_i, u_map, s_i, s_map);
-	hipLaunchKernelGGL(le_span_predict_kernel, per_cand, wg, 0, q, d_conns, d_seeds, params, uparams, anchor, econn, step, s_conn, s_i, s_map,
-			   sstart, d_recs, max_updates, evres, work, sc);
-	hipLaunchKernelGGL(le_span_verdict_kernel, per_conn, wg, 0, q, d_conns, d_seeds, params, uparams, step, s_conn, s_map, evres, work, sc,
-			   d_spans);
-	hipLaunchKernelGGL(le_span_pkt_kernel, per_cand, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, params, ctl, evres, work, d_spans, d_spkts);
+	hipLaunchKernelGGL(le_span_mark_kernel, per_tile, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, B.params, B.slot, B.ctl, B.work, sc, sstart,
+			   d_recs, B.step, max_updates, B.tiles64);
+	hipLaunchKernelGGL(le_track_prefix64_kernel, dim3(1), wg, 0, q, B.tiles64, B.tiles_n);
+	hipLaunchKernelGGL(le_span_list_kernel, per_tile, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, B.params, B.slot, B.ctl, B.work, sc, sstart,
+			   d_recs, B.step, max_updates, B.tiles64, B.uparams, B.b.keys[0], B.b.vals[0], B.u_i, B.u_map, B.u_conn);
+	const uint64_t *s_conn = le_follow_sort_updates(B, cap, conn_cap, q);
+	hipLaunchKernelGGL(le_span_predict_kernel, per_cand, wg, 0, q, d_conns, d_seeds, B.params, B.uparams, B.anchor, B.econn, B.step, s_conn, B.s_i,
+			   B.s_map, sstart, d_recs, max_updates, B.evres, B.work, sc);
+	hipLaunchKernelGGL(le_span_verdict_kernel, per_conn, wg, 0, q, d_conns, d_seeds, B.params, B.uparams, B.step, s_conn, B.s_map, B.evres, B.work,
+			   sc, d_spans);
+	hipLaunchKernelGGL(le_span_pkt_kernel, per_cand, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, B.params, B.ctl, B.evres, B.work, d_spans,
+			   d_spkts);
 	HIP_TRY(hipGetLastError());
 	return BTBBX_OK;
 }
@@ -809,23 +654,4 @@ extern "C" int btbbx_le_span_device(const uint64_t *d_words, uint64_t n_words, u
 		return BTBBX_OK;
 	return le_span_launch(d_words, n_words, pitch_words, n_streams, d_cands, d_cand_count, cand_cap, d_conns, d_conn_count, conn_cap, d_pkts,
 			      d_seeds, unit_bits, jitter_bits, max_updates, d_spans, d_span_pkts, d_span_recs, d_scratch, (hipStream_t)hip_stream);
-}
-
-// Host wrapper: btbbx_le_epoch_host's chain up to the seed stage (le_follow_host_chain), this stage in the follow stage's place.
-extern "C" int64_t btbbx_le_span_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
-				      uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
-				      btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
-				      uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
-				      int adv_errors, btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_seed *seeds,
-				      uint32_t max_updates, btbbx_le_span *spans, btbbx_le_span_pkt *span_pkts, btbbx_le_span_rec *span_recs)
-{
-	const char *who = "btbbx_le_span_host";
-	if (max_updates > LS_MAX_UPDATES) {
-		set_error("%s: max_updates must be 0..%u", who, LS_MAX_UPDATES);
-		return BTBBX_E_ARG;
-	}
-	LfSpanOut span = {max_updates, spans, span_pkts, span_recs};
-	return le_follow_host_chain(who, words, n_words, pitch_words, n_streams, search_bits, phys_channel, max_len, min_count, conns, conn_cap, cands,
-				    cand_cap, n_cands_out, unit_bits, ifs_bits, jitter_bits, flags, adv_errors, tracks, pkts, seeds, nullptr, nullptr,
-				    &span);
 }

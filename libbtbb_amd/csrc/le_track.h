@@ -609,6 +609,15 @@ static int le_track_check_args(const char *who, uint32_t n_streams, uint32_t uni
 	return BTBBX_OK;
 }
 
+// the bytes of a connection index, whose largest value is conn_cap: the radix passes a sort by the connection takes
+static int le_conn_passes(uint32_t conn_cap)
+{
+	int passes = 1;
+	while (passes < 4 && (conn_cap >> (8 * passes)))
+		passes++;
+	return passes;
+}
+
 // the launches of one tracking run: 24 + 3 per eight bits of conn_cap for the two sorts, 13 of its own
 static int le_track_launch(const btbbx_le_cand *d_cands, const uint32_t *d_count, uint32_t cap, const uint32_t *d_conn_count, uint32_t conn_cap,
 			   const uint16_t *d_phys, uint32_t n_streams, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
@@ -621,29 +630,15 @@ static int le_track_launch(const btbbx_le_cand *d_cands, const uint32_t *d_count
 	uint64_t *ekey = (uint64_t *)(s + L.ekey);
 	unsigned long long *step = (unsigned long long *)(s + L.step), *tiles64 = (unsigned long long *)(s + L.tiles64);
 	LtConn *work = (LtConn *)(s + L.work);
-	RadixBufs b;
-	b.keys[0] = (uint64_t *)(s + L.keys[0]);
-	b.keys[1] = (uint64_t *)(s + L.keys[1]);
-	b.vals[0] = (uint32_t *)(s + L.vals[0]);
-	b.vals[1] = (uint32_t *)(s + L.vals[1]);
-	b.hist = (uint32_t *)(s + L.hist);
-	b.tot = (uint32_t *)(s + L.tot);
-	b.params = params;
-	b.cap = cap;
+	const RadixBufs b = le_radix_bufs(s, L, params, cap);
 	const dim3 per_cand((cap + LE_THREADS - 1) / LE_THREADS), per_tile(L.tiles_n), wg(LE_THREADS);
 	const size_t init_items = ((size_t)conn_cap * LT_PAIRS + LE_THREADS - 1) / LE_THREADS;
 	hipLaunchKernelGGL(le_track_init_kernel, dim3((uint32_t)std::min<size_t>(init_items, 4096)), wg, 0, q, d_conn_count, conn_cap, work, score);
 	hipLaunchKernelGGL(le_track_key_kernel, per_cand, wg, 0, q, d_cands, d_count, cap, d_conn_count, conn_cap, params, b.keys[0], b.vals[0]);
 	// least significant first: the stream number and the 48 offset bits, then -- rekeyed -- the connection index, whose largest value is conn_cap
-	RadixPass passes[8];
-	for (int p = 0; p < 8; p++)
-		passes[p] = {0, 8u * p};
-	int cur = radix_sort_passes(b, nullptr, passes, 8, 0, q);
+	int cur = le_sort_bytes(b, 8, 0, q);
 	hipLaunchKernelGGL(le_track_rekey_kernel, per_cand, wg, 0, q, d_cands, params, b.vals[cur], d_phys, n_streams, b.keys[cur]);
-	int conn_passes = 1;
-	while (conn_passes < 4 && (conn_cap >> (8 * conn_passes)))
-		conn_passes++;
-	cur = radix_sort_passes(b, nullptr, passes, conn_passes, cur, q);
+	cur = le_sort_bytes(b, le_conn_passes(conn_cap), cur, q);
 	const uint64_t *keys = b.keys[cur];
 	const uint32_t *vals = b.vals[cur];
 	hipLaunchKernelGGL(le_track_flag_kernel, per_tile, wg, 0, q, d_cands, keys, vals, params, d_phys, n_streams, ifs_bits, info, tiles);
@@ -689,66 +684,4 @@ extern "C" int btbbx_le_track_device(const btbbx_le_cand *d_cands, const uint32_
 		return BTBBX_OK;
 	return le_track_launch(d_cands, d_cand_count, cand_cap, d_conn_count, conn_cap, d_phys_channel, n_streams, unit_bits, ifs_bits,
 			       jitter_bits, flags, d_tracks, d_pkts, d_scratch, (hipStream_t)hip_stream);
-}
-
-static size_t le_track_host_tail(uint32_t dev_cap, uint32_t dev_conns)
-{
-	return ld_up(le_track_layout(dev_cap, dev_conns).total) + ld_up((size_t)dev_conns * sizeof(btbbx_le_track)) +
-	       ld_up((size_t)dev_cap * sizeof(btbbx_le_track_pkt));
-}
-
-// Host wrapper: the discovery's host chain with room behind its block, the tracking, copy out.
-extern "C" int64_t btbbx_le_track_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
-				       uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
-				       btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
-				       uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
-				       btbbx_le_track *tracks, btbbx_le_track_pkt *pkts)
-{
-	const char *who = "btbbx_le_track_host";
-	int rc = le_disc_check_args(who, n_words, pitch_words, n_streams, search_bits, max_len);
-	if (rc)
-		return rc;
-	rc = le_track_check_args(who, n_streams, unit_bits, jitter_bits);
-	if (rc)
-		return rc;
-	if (!words || !phys_channel || ((!conns || !tracks) && conn_cap) || (!cands && cand_cap)) {
-		set_error("%s: null pointer", who);
-		return BTBBX_E_ARG;
-	}
-	rc = ctx_require();
-	if (rc)
-		return rc;
-	if (n_cands_out)
-		*n_cands_out = 0;
-	CallScope scope;
-	hipStream_t q = scope_stream();
-	LeDiscHostRun r;
-	rc = le_disc_host_chain(words, n_words, pitch_words, n_streams, search_bits, phys_channel, max_len, min_count, conn_cap,
-				le_track_host_tail, &r);
-	if (rc)
-		return rc;
-	if (n_cands_out)
-		*n_cands_out = r.count;
-	if (!r.have)
-		return 0;
-	const uint64_t nc = std::min<uint64_t>(r.n_conns, r.dev_conns), nk = std::min<uint64_t>(r.have, cand_cap);
-	if (nc) {
-		char *scratch = r.tail;
-		btbbx_le_track *d_tracks = (btbbx_le_track *)(scratch + ld_up(le_track_layout(r.dev_cap, r.dev_conns).total));
-		btbbx_le_track_pkt *d_pkts = (btbbx_le_track_pkt *)((char *)d_tracks + ld_up((size_t)r.dev_conns * sizeof(btbbx_le_track)));
-		rc = le_track_launch(r.d_cands, r.d_count, r.dev_cap, r.d_conn_count, r.dev_conns, r.d_phys, n_streams, unit_bits, ifs_bits,
-				     jitter_bits, flags, d_tracks, d_pkts, scratch, q);
-		if (rc)
-			return rc;
-		HIP_TRY(hipMemcpyAsync(conns, r.d_conns, (size_t)nc * sizeof(btbbx_le_conn), hipMemcpyDeviceToHost, q));
-		HIP_TRY(hipMemcpyAsync(tracks, d_tracks, (size_t)nc * sizeof(btbbx_le_track), hipMemcpyDeviceToHost, q));
-		if (nk && pkts)
-			HIP_TRY(hipMemcpyAsync(pkts, d_pkts, (size_t)nk * sizeof(btbbx_le_track_pkt), hipMemcpyDeviceToHost, q));
-	} else if (nk && pkts) {
-		memset(pkts, 0xff, (size_t)nk * sizeof(btbbx_le_track_pkt));       // (no connection stored: no candidate is a member)
-	}
-	if (nk)
-		HIP_TRY(hipMemcpyAsync(cands, r.d_cands, (size_t)nk * sizeof(btbbx_le_cand), hipMemcpyDeviceToHost, q));
-	HIP_TRY(hipStreamSynchronize(q));
-	return (int64_t)r.n_conns;
 }

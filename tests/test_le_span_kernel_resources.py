@@ -1,5 +1,5 @@
 """Registers, LDS and scratch of the kernels of LE following through connection parameter updates (le_span.h), read from the built
-library as tests/test_le_follow_kernel_resources.py does for the follow stage: DESIGN 3.8.5 names thirteen kernels, none of them
+library as tests/test_le_follow_kernel_resources.py does for the follow stage: DESIGN 3.8.5 names eleven kernels, none of them
 with scratch or a spilled register, and states their VGPR and LDS figures; none needs more than 64 VGPRs -- eight waves per SIMD."""
 import os
 import re
@@ -13,8 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DOCUMENTED = {
     "le_span_param_kernel": (23, 0), "le_span_begin_kernel": (24, 0), "le_span_step_kernel": (26, 8), "le_span_instant_kernel": (12, 0),
     "le_span_pick_kernel": (14, 0), "le_span_bound_kernel": (33, 0), "le_span_mark_kernel": (19, 4), "le_span_list_kernel": (34, 16),
-    "le_span_rekey_kernel": (6, 0), "le_span_gather_kernel": (8, 0), "le_span_predict_kernel": (24, 0), "le_span_verdict_kernel": (25, 0),
-    "le_span_pkt_kernel": (18, 0),
+    "le_span_predict_kernel": (24, 0), "le_span_verdict_kernel": (25, 0), "le_span_pkt_kernel": (18, 0),
 }
 
 
