@@ -143,6 +143,13 @@ __device__ __forceinline__ void lds_st_rec(uint32_t byte_off, u32x4 v)
 	lds_st(byte_off + 8u, v.z);
 	lds_st(byte_off + 12u, v.w);
 }
+// ... as written here: where several branches store to one slot the compiler hoists slot + 4 / 8 / 12 out of them as three
+// registers and stores four single dwords per branch (scan_slide_kernel's append of a trip's notes)
+__device__ __forceinline__ void lds_st_rec2(uint32_t byte_off, uint32_t x, uint32_t y, uint32_t z, uint32_t w)
+{
+	asm volatile("ds_write2_b32 %0, %1, %2 offset1:1\n\tds_write2_b32 %0, %3, %4 offset0:2 offset1:3"
+		     : : "v"(byte_off), "v"(x), "v"(y), "v"(z), "v"(w) : "memory");
+}
 
 // w = the 64-symbol window at `offset` (the kernel keeps it with the candidate: by the time a
 // batch is verified the stream words have long left the L2, and re-reading them cost 40 % extra

@@ -9,7 +9,7 @@
 // TILES tiles: the bit-sliced barker filter (barker32) and the check stream (slide32, slide.h) for both
 // halves of the lane's words, then the lock-step survivor loop -- eight vector instructions and ONE read of the
 // 2^SLIDE_BITS-bit candidate set in LDS per survivor (chains as shift registers, round 5).  A candidate goes straight to
-// the wave's ring in LDS (the membership compare's lane mask + mbcnt, no atomics); the exact reference rule (verify_lap_any, syndrome tables read
+// the wave's ring in LDS (the membership compare's lane mask + mbcnt, no atomics; the one-level form notes it in a register and appends a trip's notes at once, round 7); the exact reference rule (verify_lap_any, syndrome tables read
 // through L2) runs on ring batches of up to 64.  The ring is the only LDS besides the set, so TWO workgroups
 // fit a CU: 2 x 768 threads = 6 waves per SIMD at <= 80 VGPRs (76 KiB of LDS each; a wave owns 63 words of a tile of 756).  Measured on one box,
 // 4 GiB, ms per launch (profiles/r03_ab/): one 1024-thread workgroup per CU (4 waves per SIMD) 4.12, 2 x 1024
@@ -36,6 +36,15 @@
 //     returning atomics on one address serialise (SQ_WAIT_ANY 2.7 x).
 //   * two chains per word walking towards each other (6.09 passes instead of 6.99): not built -- tools/lockstep_model.py prices it at +34 % per
 //     chain and pass (64-bit survivor masks, 82 check bits per chain) for -13 % passes.
+// Round 7 (profiles/r07_events): the one-level form's passes only NOTE a candidate -- one v_or under the chain's lane mask and two or
+//   three scalar ORs -- and the trip appends its notes to the ring once, behind the sparse tail: one rank, one address, one code for
+//   the wave, two ds_write2_b32 per chain under lane masks kept on the scalar side.  "No candidate events at all" (timing only) put
+//   the ceiling at 7.8 % (2.538 against 2.753 ms); the change is worth 2.7 % (2.698 -> 2.626 ms; 1 540 -> 1 511 M vector and
+//   842 -> 775 M scalar instructions per launch) over six alternating pairs on one box, bit-exact -- short of the 3 % in every pair
+//   it was specified to reach.  Three forms were timed: what the launch paid for was the VECTOR instructions of the append, not the scalar work moved out of the priority-2 loop (13 + one
+//   compare per chain seen: -1.1 %; 9 + a compare: -1.9 %; 6 and no compare: -2.8 %); four lane masks instead of two cost ten
+//   v_readlane of spilled scalars per trip and were not timed.  v_add_co_u32 (m - 1 with "m was not zero" as its carry) issues at the
+//   slow rate, 4.3 cycles against 2.6 for v_add_u32: the sparse tail keeps its compares.
 // The kernel's two cuts.
 // SlideStd: tables for <= 2 errors (0.3 % of the survivors are members of the set).  Two workgroups per CU around a 2^19-bit set; six
 //   passes run blind, a candidate the ring has no room for is checked in place.
@@ -367,7 +376,71 @@ void scan_slide_kernel(ScanArgs a)
 			return __ballot(any != 0) != 0;
 		};
 		uint32_t pos2[TILES][2];                     // (two-level form) where the chains stood when their pending look-ups were sent
-		auto events = [&](const uint64_t (&cms)[TILES][2]) {   // append the wave's candidates of one pass to its ring
+		auto event_chain = [&](int u, int h, uint64_t cm) {    // append one chain's candidates of one pass (lanes cm) to the wave's ring
+			const bool cand = __builtin_amdgcn_inverse_ballot_w64(cm);
+			// ring entries left for this chain; candidates ranked beyond them (a stream made of
+			// sync words: tests/test_gpu_scan.py adversarial cases) go through the exact rule in place
+			const uint32_t room = RING - (q_tail - q_head);
+			uint32_t in_wave;                       // (asm: the compiler turns `popcount == 1` into a 64-bit VECTOR compare)
+			asm("s_bcnt1_i32_b64 %0, %1" : "=s"(in_wave) : "s"(cm) : "scc");
+			const uint32_t n = min(in_wave, room);
+			if (cand) {
+				uint32_t lane6 = lane << 6;
+				asm volatile("" : "+v"(lane6));         // (otherwise four loop-invariant code bases sit in VGPRs through the pass loop)
+				// the marker planted above the chain's check bits has moved down by exactly the offsets passed
+				uint32_t pos;
+				if constexpr (ABS)
+					pos = pos2[u][h];                   // (a candidate's chain was not empty: 0 .. 31)
+				else if constexpr (CFG::LEVEL2)
+					pos = pos2[u][h];
+				else
+					asm("v_ffbh_u32 %0, %1" : "=v"(pos) : "v"((uint32_t)(C[u][h] >> 32)));
+				// the record carries the three stream dwords the window lies in; the drain cuts it out (for sixty
+				// candidates at once) instead of this branch (for one)
+				const uint32_t code = pos | lane6 | (((it + u) << 12) | (h << 5));
+				const u32x4 rec = {code, d[u][h], d[u][h + 1], d[u][h + 2]};
+				if (in_wave == 1 && room) {
+					// one candidate in the wave (nine events in ten): its slot is the ring tail, no ranking
+					lds_st_rec(ring_off + CAND_BYTES * (q_tail & (RING - 1)), rec);
+				} else {
+					const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32),
+							__builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0));
+					if (rank < room) {
+						lds_st_rec(ring_off + CAND_BYTES * ((q_tail + rank) & (RING - 1)), rec);
+					} else {
+						uint32_t stream, lap, nerr, cold = code;
+						asm volatile("" : "+v"(cold));      // keeps the tile -> stream division of this cold path out of every trip
+						const uint64_t word = code_word(cold, stream);
+						const uint32_t wlo = alignbit(rec.z, rec.y, pos), whi = alignbit(rec.w, rec.z, pos);
+						if (verify_lap_any<false>(a, ((uint64_t)whi << 32) | wlo, lap, nerr)) {
+							if constexpr (ORD)
+								*a.irregular = 1u;          // a hit outside the drains: its segment cannot be ranked here
+							else
+								emit_hit(a, stream, word * 64 + (cold & 63), lap, nerr);
+						}
+					}
+				}
+			}
+			q_tail += n;
+		};
+		auto events = [&](const uint64_t (&cms)[TILES][2]) {   // ... every chain's (the two-level form)
+#pragma unroll
+			for (int u = 0; u < TILES; u++)
+#pragma unroll
+				for (int h = 0; h < 2; h++)
+					if (cms[u][h])
+						event_chain(u, h, cms[u][h]);
+		};
+		// One-level form (round 7): a pass only NOTES its candidates -- one dword per lane: where the chain stood and which chain -- and
+		// the trip appends them once behind the tail (append_noted): one rank, one ring address, one code, and per chain one record
+		// store under that chain's lanes, instead of rank, room, address and store per chain and pass inside the priority-2 loop.
+		// A lane holds one note: a chain whose candidates meet a lane that already has one goes through event_chain as before.
+		static_assert(CFG::DENSE || TILES == 2, "a note's tile bit is OR-ed into the trip's (even) tile iteration");
+		uint64_t noted = 0;                          // lanes that hold a note ...
+		uint64_t noted_h = 0, noted_u = 0;           // ... of an upper half / of the trip's second tile (a chain's lanes on the scalar side: no compare)
+		uint32_t note;
+		asm volatile("" : "=v"(note));               // (no instruction: a lane's note is read only while its bit of `noted` is set)
+		auto note_events = [&](const uint64_t (&cms)[TILES][2]) {
 #pragma unroll
 			for (int u = 0; u < TILES; u++)
 #pragma unroll
@@ -375,52 +448,75 @@ void scan_slide_kernel(ScanArgs a)
 					const uint64_t cm = cms[u][h];
 					if (!cm)
 						continue;
-					const bool cand = __builtin_amdgcn_inverse_ballot_w64(cm);
-					// ring entries left for this chain; candidates ranked beyond them (a stream made of
-					// sync words: tests/test_gpu_scan.py adversarial cases) go through the exact rule in place
-					const uint32_t room = RING - (q_tail - q_head);
-					uint32_t in_wave;                       // (asm: the compiler turns `popcount == 1` into a 64-bit VECTOR compare)
-					asm("s_bcnt1_i32_b64 %0, %1" : "=s"(in_wave) : "s"(cm) : "scc");
-					const uint32_t n = min(in_wave, room);
-					if (cand) {
-						uint32_t lane6 = lane << 6;
-						asm volatile("" : "+v"(lane6));         // (otherwise four loop-invariant code bases sit in VGPRs through the pass loop)
-						// the marker planted above the chain's check bits has moved down by exactly the offsets passed
-						uint32_t pos;
-						if constexpr (ABS)
-							pos = pos2[u][h];                   // (a candidate's chain was not empty: 0 .. 31)
-						else if constexpr (CFG::LEVEL2)
-							pos = pos2[u][h];
-						else
-							asm("v_ffbh_u32 %0, %1" : "=v"(pos) : "v"((uint32_t)(C[u][h] >> 32)));
-						// the record carries the three stream dwords the window lies in; the drain cuts it out (for sixty
-						// candidates at once) instead of this branch (for one)
-						const uint32_t code = pos | lane6 | (((it + u) << 12) | (h << 5));
-						const u32x4 rec = {code, d[u][h], d[u][h + 1], d[u][h + 2]};
-						if (in_wave == 1 && room) {
-							// one candidate in the wave (nine events in ten): its slot is the ring tail, no ranking
-							lds_st_rec(ring_off + CAND_BYTES * (q_tail & (RING - 1)), rec);
-						} else {
-							const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32),
-									__builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0));
-							if (rank < room) {
-								lds_st_rec(ring_off + CAND_BYTES * ((q_tail + rank) & (RING - 1)), rec);
-							} else {
-								uint32_t stream, lap, nerr, cold = code;
-								asm volatile("" : "+v"(cold));      // keeps the tile -> stream division of this cold path out of every trip
-								const uint64_t word = code_word(cold, stream);
-								const uint32_t wlo = alignbit(rec.z, rec.y, pos), whi = alignbit(rec.w, rec.z, pos);
-								if (verify_lap_any<false>(a, ((uint64_t)whi << 32) | wlo, lap, nerr)) {
-									if constexpr (ORD)
-										*a.irregular = 1u;          // a hit outside the drains: its segment cannot be ranked here
-									else
-										emit_hit(a, stream, word * 64 + (cold & 63), lap, nerr);
-								}
+					if (cm & noted) {
+						event_chain(u, h, cm);
+						continue;
+					}
+					// the note = the candidate's code without lane and trip: offset in the half, half (bit 5), tile of the trip (bit 12)
+					// (asm: one v_or under the chain's lane mask; as C the compiler may make it a select over all lanes)
+					if (__builtin_amdgcn_inverse_ballot_w64(cm))
+						asm volatile("v_or_b32 %0, %1, %2" : "+v"(note) : "i"((uint32_t)(h << 5) | (uint32_t)(u << 12)), "v"(pos2[u][h]));
+					noted |= cm;
+					if (h)
+						noted_h |= cm;
+					if (u)
+						noted_u |= cm;
+				}
+		};
+		auto append_noted = [&]() {                  // the trip's notes -> ring, in one go (the order inside a trip is free: the drain ranks by code)
+			if (!noted)
+				return;
+			const uint32_t room = RING - (q_tail - q_head);
+			uint32_t in_wave;
+			asm("s_bcnt1_i32_b64 %0, %1" : "=s"(in_wave) : "s"(noted) : "scc");
+			const uint32_t n = min(in_wave, room);
+			if (__builtin_amdgcn_inverse_ballot_w64(noted)) {
+				const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(noted >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)noted, 0));
+				const uint32_t code = note | (lane << 6) | (it << 12);
+				const uint32_t slot = ring_off + CAND_BYTES * ((q_tail + rank) & (RING - 1));
+				auto lanes_of = [&](int u, int h) {
+					return (h ? noted_h : noted & ~noted_h) & (u ? noted_u : ~noted_u);
+				};
+				if (in_wave <= room) {
+#pragma unroll
+					for (int u = 0; u < TILES; u++)
+#pragma unroll
+						for (int h = 0; h < 2; h++) {
+							const uint64_t mine = lanes_of(u, h);
+							if (mine) {
+								asm volatile("" : : "s"(mine));         // (a scalar branch around the chain, not one more term of its lane mask)
+								if (__builtin_amdgcn_inverse_ballot_w64(mine))
+									lds_st_rec2(slot, code, d[u][h], d[u][h + 1], d[u][h + 2]);
 							}
 						}
+				} else {
+					// a ring with fewer free entries than the trip has notes (a stream made of sync words): those ranked beyond them go
+					// through the exact rule in place, as in event_chain
+					uint32_t y = 0, z = 0, w = 0;
+#pragma unroll
+					for (int u = 0; u < TILES; u++)
+#pragma unroll
+						for (int h = 0; h < 2; h++)
+							if (__builtin_amdgcn_inverse_ballot_w64(lanes_of(u, h))) {
+								y = d[u][h]; z = d[u][h + 1]; w = d[u][h + 2];
+							}
+					if (rank < room) {
+						lds_st_rec2(slot, code, y, z, w);
+					} else {
+						uint32_t stream, lap, nerr, cold = code;
+						asm volatile("" : "+v"(cold));
+						const uint64_t word = code_word(cold, stream);
+						const uint32_t wlo = alignbit(z, y, cold), whi = alignbit(w, z, cold);      // (shift = the low five bits)
+						if (verify_lap_any<false>(a, ((uint64_t)whi << 32) | wlo, lap, nerr)) {
+							if constexpr (ORD)
+								*a.irregular = 1u;
+							else
+								emit_hit(a, stream, word * 64 + (cold & 63), lap, nerr);
+						}
 					}
-					q_tail += n;
 				}
+			}
+			q_tail += n;
 		};
 		// (An empty chain shifts itself out: its index becomes 0 or 1, which no table set contains -- context.cpp asserts it --,
 		// so a lane without a survivor never looks like a candidate and the test needs no "this lane has one" term.)
@@ -508,7 +604,7 @@ void scan_slide_kernel(ScanArgs a)
 				if (any2)
 					level2_send(cms);
 			} else if (any) {                            // some lane of the wave holds a candidate (half of the passes)
-				events(cms);
+				note_events(cms);
 			}
 		};
 		// Behind the fixed passes a handful of the wave's 2 * TILES * 64 chains still hold survivors (0.8 % have seven or more):
@@ -542,7 +638,7 @@ void scan_slide_kernel(ScanArgs a)
 						anyl |= live[u][h];
 					}
 				if (anyc)
-					events(cms);
+					note_events(cms);
 			}
 		};
 #ifdef SCAN_PROFILE
@@ -562,6 +658,7 @@ void scan_slide_kernel(ScanArgs a)
 				pass_no++;
 			}
 			sparse_tail();
+			append_noted();
 			PROF_MARK(pass_no < 13 ? pass_no : 13);
 			__builtin_amdgcn_s_setprio(PRIO_CAND);
 			PROF_MARK(16);

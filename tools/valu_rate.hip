@@ -236,6 +236,16 @@ BANK_KERNEL(k_cmp_sel_sgpr, "v_cmp_gt_u32 s[20:21], v8, v9", "v_cndmask_b32_e64 
 BANK_KERNEL(k_addc_vcc, "v_add_co_u32 v20, vcc, v8, v9", "v_addc_co_u32 v21, vcc, v10, v11, vcc", "v_add_co_u32 v22, vcc, v12, v13", "v_addc_co_u32 v23, vcc, v14, v15, vcc",
 	    "v_add_co_u32 v24, vcc, v9, v10", "v_addc_co_u32 v25, vcc, v11, v12, vcc", "v_add_co_u32 v26, vcc, v13, v14", "v_addc_co_u32 v27, vcc, v15, v16, vcc")
 
+// v_add_co_u32 x, -1 (round 7): `m - 1` with the borrow as a lane mask -- the carry-out is "m was not zero", the mask the sparse tail
+// of scan_slide_kernel forms with one v_cmp_ne per chain and round.  Alone (no addc behind it), to vcc and to an SGPR pair.
+#define OP8_CO(dst) asm volatile("v_add_co_u32 %0, " dst ", -1, %0\n v_add_co_u32 %1, " dst ", -1, %1\n v_add_co_u32 %2, " dst ", -1, %2\n" \
+	"v_add_co_u32 %3, " dst ", -1, %3\n v_add_co_u32 %4, " dst ", -1, %4\n v_add_co_u32 %5, " dst ", -1, %5\n" \
+	"v_add_co_u32 %6, " dst ", -1, %6\n v_add_co_u32 %7, " dst ", -1, %7\n" \
+	: "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h) : : "vcc", "s20", "s21");
+KERNEL(k_add_co_vcc, OP8_CO("vcc"))
+KERNEL(k_add_co_sgpr, OP8_CO("s[20:21]"))
+KERNEL(k_add_m1, OP8_LIT("v_add_u32", "-1"))
+
 template <typename K>
 static void run(const char *name, K kernel, uint32_t *d_out, int waves_per_simd)
 {
@@ -333,6 +343,9 @@ int main()
 		run("cmp+cndmask via vcc", k_cmp_sel_vcc, d_out, w);
 		run("cmp+cndmask via sgpr pair", k_cmp_sel_sgpr, d_out, w);
 		run("add_co+addc via vcc", k_addc_vcc, d_out, w);
+		run("v_add_u32 -1", k_add_m1, d_out, w);
+		run("v_add_co_u32 -1 -> vcc", k_add_co_vcc, d_out, w);
+		run("v_add_co_u32 -1 -> sgpr pair", k_add_co_sgpr, d_out, w);
 	}
 	return 0;
 }
