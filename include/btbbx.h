@@ -1042,6 +1042,120 @@ int64_t btbbx_le_data_host(const uint64_t *words, uint64_t n_words, uint64_t pit
 			   btbbx_le_msg *msgs, uint64_t msg_cap, uint64_t *n_msgs_out, uint8_t *bytes, uint64_t byte_cap,
 			   uint64_t *n_bytes_out);
 
+/* ---- LE decryption: session keys, packet counters, AES-CCM, plain L2CAP ----------------------
+ * Behind the data stage, on the device: for every connection whose encryption start procedure is in the capture the session key
+ * under one of the caller's long-term keys, for every encrypted packet its packet counter, and the data stage's messages once more,
+ * over plaintext.  It changes nothing of its input.
+ *
+ * The input is the data stage's (streams, d_cands, d_conns, d_pkts and the counters), the data stage's d_data_pkts, read for role,
+ * kind and bits, and the keys: key k is the 16 octets at d_keys + 16k in AES key byte order, that is the LTK most significant octet
+ * first, as the Core Specification prints it.  Membership, time order, slot order first + rank, the payload octet rule (data stage
+ * rule 6: dewhitening continued behind the header, zeros beyond the stream's end) and all guards for a list from elsewhere are the
+ * data stage's.  "Octet j" below is payload octet j.  All arithmetic is integer arithmetic; counters are 64 bits wide.
+ *   1. COUNTING members.  A member COUNTS iff its data-stage role is CENTRAL or PERIPHERAL and its data-stage kind is neither
+ *      RETRANSMIT nor UNKNOWN.  Every other member never gets a counter.
+ *   2. PROCEDURE PDUs, among COUNTING members with llid == 3.  ENC_REQ: role CENTRAL, L == 23, octet 0 == 0x03; SKDm = octets
+ *      11..18, IVm = octets 19..22.  ENC_RSP: role PERIPHERAL, L == 13, octet 0 == 0x04; SKDs = octets 1..8, IVs = octets 9..12.
+ *      START: role PERIPHERAL, L == 1, octet 0 == 0x05.  The connection's REQ is the ENC_REQ of the smallest rank, its RSP the
+ *      ENC_RSP of the smallest rank above REQ's, its START the START of the smallest rank above RSP's.  It is ARMED iff all three
+ *      exist.
+ *   3. SESSION KEY.  skd[0..7] = SKDm as received, skd[8..15] = SKDs as received; the AES input block is block[j] = skd[15 - j];
+ *      SK_k = AES-128(key_k, block), and the output block, octet 0 first, is the CCM key.  iv[0..3] = IVm as received, iv[4..7] = IVs.
+ *   4. ENCRYPTED members.  In an ARMED connection a COUNTING member of rank above START's with llid != 0 is ENCRYPTED iff L >= 5
+ *      and SHORT iff 1 <= L <= 4; a member of rank above START's that does not COUNT and has L >= 1 is SKIPPED.  Everything else is
+ *      CLEAR: empty PDUs, everything up to START, every member of a connection that is not ARMED.  The ordinal n of an ENCRYPTED
+ *      member is the number of ENCRYPTED members of the same (connection, role) of smaller rank.  SHORT, SKIPPED and CLEAR members
+ *      take no ordinal.
+ *   5. TRIAL of an ENCRYPTED member under key K and skew d.  c = n + d; dir = 1 for CENTRAL, 0 for PERIPHERAL.  nonce[0..3] = LE32 of
+ *      c's low 32 bits, nonce[4] = ((c >> 32) & 0x7f) | dir << 7, nonce[5..12] = iv.  m = L - 4.  B0 = 0x49 | nonce | BE16(m);
+ *      B1 = 00 01 (header0 & 0xE3) and 13 zero octets; S_i = AES(K, 0x01 | nonce | BE16(i)).  Plaintext octet j = octet j ^
+ *      S_(1 + j/16)[j % 16] for j < m.  X = AES(K, B0); X = AES(K, X ^ B1); X = AES(K, X ^ P) for every 16-octet plaintext block P,
+ *      the last one padded with zeros.  The trial VERIFIES iff X[0..3] ^ S_0[0..3] equals octets m .. m + 3.
+ *   6. KEY.  The probes are the first min(4, .) ENCRYPTED members of the connection in time order, either role.  score_k = the number
+ *      of probes that verify under SK_k at some d < window.  The connection's key is the smallest k of the largest score, if that
+ *      score is >= 1: the connection is KEYED.  Otherwise every ENCRYPTED member of it is FAILED with skew 0xff.
+ *   7. SKEW, in a KEYED connection.  An ENCRYPTED member is VERIFIED at the smallest d < window that verifies under the connection's
+ *      key, and its counter is n + d; without one it is FAILED, its skew 0xff and its counter n.  Each member is searched on its
+ *      own: no member's result depends on another's.
+ *   8. MESSAGES: the data stage's rules 5 to 7 once more, over EFFECTIVE members.  A VERIFIED member has L' = L - 4, its own llid
+ *      (START iff llid == 2, CONTINUATION or ORPHAN iff llid == 1, CONTROL iff llid == 3) and its plaintext as octets.  A CLEAR member
+ *      is as in the data stage.  FAILED, SKIPPED and SHORT members have kind IGNORED: they are no fragment and break nothing.  The
+ *      outputs have the data stage's shapes: d_msgs, d_plain_pkts (role and bits as in d_data_pkts, kind, msg and pos under the
+ *      effective members), d_bytes and both counts, which the stage WRITES; msg_cap and byte_cap cut a prefix as there.  If no
+ *      connection is ARMED, every message record, every octet, every d_plain_pkts record and both counts equal
+ *      btbbx_le_data_device's on the same input, byte for byte.
+ *   9. RECORDS.  Every byte of d_crypt[0 .. K) and d_crypt_pkts[0 .. N) is written, nothing behind them.  btbbx_le_crypt of a
+ *      connection without a member: zeros; otherwise session_key = the connection's key's SK (zeros unless KEYED), iv (zeros
+ *      unless ARMED), req / rsp / start = list indices, 0xffffffff if none, n_encrypted = n_verified + n_failed, n_skipped,
+ *      key (0xff: none), max_skew = the largest skew of a VERIFIED member.  btbbx_le_crypt_pkt of a candidate that is no member:
+ *      sixteen 0xff; of a VERIFIED or FAILED member counter (low 32 bits), counter_hi (bits 32..38), ordinal and skew; of every
+ *      other member these are 0.  opcode = plaintext octet 0 of a VERIFIED member with llid == 3, else 0xff.
+ * LIMITS: a connection whose LL_ENC_REQ / LL_ENC_RSP are not in the capture stays unarmed; LL_PAUSE_ENC and a second encryption
+ * start are not tracked; a lost packet shows as skew and is found only within window; the roles' limits are the data stage's; an
+ * update PDU decrypted here is not fed back to the follow or span stage. */
+#define BTBBX_LE_CRYPT_CLEAR    0u   /* btbbx_le_crypt_pkt.state */
+#define BTBBX_LE_CRYPT_VERIFIED 1u
+#define BTBBX_LE_CRYPT_FAILED   2u
+#define BTBBX_LE_CRYPT_SKIPPED  3u
+#define BTBBX_LE_CRYPT_SHORT    4u
+#define BTBBX_LE_CRYPT_REQ      1u   /* btbbx_le_crypt.flags */
+#define BTBBX_LE_CRYPT_RSP      2u
+#define BTBBX_LE_CRYPT_START    4u
+#define BTBBX_LE_CRYPT_ARMED    8u
+#define BTBBX_LE_CRYPT_KEYED    16u
+
+typedef struct btbbx_le_crypt {      /* 56 bytes, parallel to conns; a connection without a member: zeros */
+	uint8_t  session_key[16];
+	uint8_t  iv[8];
+	uint32_t req, rsp, start;    /* list indices, 0xffffffff if none */
+	uint32_t n_encrypted, n_verified, n_failed, n_skipped;
+	uint8_t  key;                /* index of the connection's key, 0xff: none */
+	uint8_t  max_skew;
+	uint8_t  flags;              /* REQ 1, RSP 2, START 4, ARMED 8, KEYED 16 */
+	uint8_t  reserved;           /* 0 */
+} btbbx_le_crypt;
+typedef struct btbbx_le_crypt_pkt {  /* 16 bytes, parallel to the sorted candidate list; no member: sixteen 0xff bytes */
+	uint32_t counter;            /* low 32 bits of the packet counter */
+	uint32_t ordinal;
+	uint8_t  state;              /* CLEAR, VERIFIED, FAILED, SKIPPED, SHORT */
+	uint8_t  skew;               /* 0xff: FAILED */
+	uint8_t  opcode;             /* of a VERIFIED control PDU, else 0xff */
+	uint8_t  counter_hi;         /* bits 32..38 of the packet counter */
+	uint8_t  reserved[4];        /* written as 0 */
+} btbbx_le_crypt_pkt;
+
+/* d_tracks and d_phys_channel are taken for the chain's sake and not read.  n_keys: 1..64, window: 1..32.  Nothing is read back and
+ * the call is asynchronous on hip_stream.  d_scratch: btbbx_le_crypt_scratch_bytes(cand_cap, conn_cap, n_keys) bytes (about 76 per
+ * candidate and 180 per connection and key), 16-byte aligned.  The count of launches, 24, depends on nothing.
+ * BTBBX_E_ARG, before any launch: btbbx_le_data_device's conditions, n_keys or window out of range, a null pointer (d_msgs may be null
+ * with msg_cap 0, d_bytes with byte_cap 0), d_crypt_pkts not 16-byte aligned, d_crypt not 8-byte, d_data_pkts or d_plain_pkts not
+ * 4-byte aligned.  cand_cap == 0 or conn_cap == 0 succeeds and writes only the two counts, as 0. */
+size_t btbbx_le_crypt_scratch_bytes(uint32_t cand_cap, uint32_t conn_cap, uint32_t n_keys);
+int btbbx_le_crypt_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			  const uint16_t *d_phys_channel,
+			  const btbbx_le_cand *d_cands, const uint32_t *d_cand_count, uint32_t cand_cap,
+			  const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
+			  const btbbx_le_track *d_tracks, const btbbx_le_track_pkt *d_pkts, const btbbx_le_data_pkt *d_data_pkts,
+			  const uint8_t *d_keys, uint32_t n_keys, uint32_t window,
+			  btbbx_le_crypt *d_crypt, btbbx_le_crypt_pkt *d_crypt_pkts, btbbx_le_data_pkt *d_plain_pkts,
+			  btbbx_le_msg *d_msgs, uint32_t msg_cap, uint32_t *d_msg_count, uint8_t *d_bytes, uint64_t byte_cap,
+			  uint64_t *d_byte_count, void *d_scratch, size_t scratch_bytes, void *hip_stream);
+
+/* Host wrapper: btbbx_le_data_host's chain with this stage behind the data stage on the same stream.  The data wrapper's arguments
+ * and return value, with keys (16 * n_keys octets), n_keys and window behind data_pkts; data and data_pkts are the data stage's
+ * records; crypt: conn_cap records; crypt_pkts and plain_pkts (either may be NULL): cand_cap records; msgs, bytes and the two
+ * counts are rule 8's.  max_len is not raised: an encrypted PDU is 4 octets longer than its plaintext, so a 27-octet connection
+ * needs max_len >= 31 and data length extension 255.  BTBBX_E_ARG: the data wrapper's conditions, keys NULL, crypt NULL with
+ * conn_cap != 0, n_keys outside 1..64, window outside 1..32. */
+int64_t btbbx_le_crypt_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			    uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+			    btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+			    uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+			    btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_data *data, btbbx_le_data_pkt *data_pkts,
+			    const uint8_t *keys, uint32_t n_keys, uint32_t window, btbbx_le_crypt *crypt, btbbx_le_crypt_pkt *crypt_pkts,
+			    btbbx_le_data_pkt *plain_pkts, btbbx_le_msg *msgs, uint64_t msg_cap, uint64_t *n_msgs_out, uint8_t *bytes,
+			    uint64_t byte_cap, uint64_t *n_bytes_out);
+
 /* ---- hop selection and CLK1-27 reversal ------------------------- */
 #define BTBBX_SEQUENCE_LENGTH 134217728u   /* values of CLK1-27, bluetooth_piconet.h:102 */
 

@@ -154,6 +154,16 @@ LE_DATA_PKT_DTYPE = np.dtype([("msg", "<u4"), ("pos", "<u4"), ("role", "u1"), ("
 LE_MSG_DTYPE = np.dtype([("byte_offset", "<u8"), ("conn", "<u4"), ("start", "<u4"), ("n_fragments", "<u4"), ("bytes", "<u4"),
                          ("l2cap_len", "<u2"), ("cid", "<u2"), ("role", "u1"), ("flags", "u1"), ("reserved", "u1", (2,))])
 assert LE_DATA_DTYPE.itemsize == 48 and LE_DATA_PKT_DTYPE.itemsize == 12 and LE_MSG_DTYPE.itemsize == 32
+# LE decryption (include/btbbx.h btbbx_le_crypt / btbbx_le_crypt_pkt; le_crypt.h checks the C layout with static_asserts): a
+# packet's state, a connection's flags
+LE_CRYPT_CLEAR, LE_CRYPT_VERIFIED, LE_CRYPT_FAILED, LE_CRYPT_SKIPPED, LE_CRYPT_SHORT = range(5)
+LE_CRYPT_REQ, LE_CRYPT_RSP, LE_CRYPT_START, LE_CRYPT_ARMED, LE_CRYPT_KEYED = 1, 2, 4, 8, 16
+LE_CRYPT_DTYPE = np.dtype([("session_key", "u1", (16,)), ("iv", "u1", (8,)), ("req", "<u4"), ("rsp", "<u4"), ("start", "<u4"),
+                           ("n_encrypted", "<u4"), ("n_verified", "<u4"), ("n_failed", "<u4"), ("n_skipped", "<u4"), ("key", "u1"),
+                           ("max_skew", "u1"), ("flags", "u1"), ("reserved", "u1")])
+LE_CRYPT_PKT_DTYPE = np.dtype([("counter", "<u4"), ("ordinal", "<u4"), ("state", "u1"), ("skew", "u1"), ("opcode", "u1"),
+                               ("counter_hi", "u1"), ("reserved", "u1", (4,))])
+assert LE_CRYPT_DTYPE.itemsize == 56 and LE_CRYPT_PKT_DTYPE.itemsize == 16
 
 # one surveyed piconet (include/btbbx.h btbbx_survey_rec; survey.hip checks the C layout with static_asserts)
 SURVEY_DTYPE = np.dtype([("lap", "<u4"), ("flags", "<u4"), ("uap", "u1"), ("clk_offset", "u1"), ("used_channels", "u1"),
@@ -266,6 +276,11 @@ SIGNATURES = {
                                        _vp, _u64, _vp, _vp, C.c_size_t, _vp]),
     "btbbx_le_data_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
                                        _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "btbbx_le_crypt_scratch_bytes": (C.c_size_t, [_u32, _u32, _u32]),
+    "btbbx_le_crypt_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp,
+                                        _vp, _vp, _vp, _u32, _vp, _vp, _u64, _vp, _vp, C.c_size_t, _vp]),
+    "btbbx_le_crypt_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
+                                        _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),
     "btbbx_survey_scratch_bytes": (C.c_size_t, [_u32]),
     "btbbx_survey_hits_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp,
                                            _vp, C.c_size_t, _vp]),
@@ -661,6 +676,57 @@ def le_data(words, search_bits, phys_channels, max_len=27, min_count=2, n_stream
     kept = int(stored["byte_offset"][-1]) + int(stored["bytes"][-1]) if len(stored) else 0
     return (conns[:nc].copy(), cands[:nk].copy(), tracks[:nc].copy(), pkts[:nk].copy(), data[:nc].copy(), data_pkts[:nk].copy(), msgs,
             payload[:kept].copy())
+
+
+def le_decrypt(words, search_bits, phys_channels, keys, window=8, max_len=27, min_count=2, n_streams=1, pitch_words=None, n_words=None,
+               unit_bits=1250, ifs_bits=200, jitter_bits=50, flags=LE_TRACK_REMAP, conn_cap=1 << 12, cand_cap=1 << 20, truncate=False,
+               msg_cap=1 << 16, byte_cap=1 << 22):
+    """le_data, then the decryption of every connection whose encryption start is in the capture (include/btbbx.h
+    btbbx_le_crypt_device).  keys: the candidate long-term keys, 1 to 64 of them, each 16 octets most significant octet first, as
+    bytes objects or one (n, 16) uint8 array; window: the packet counter skews 0 .. window - 1 that are tried per packet (1..32).
+    An encrypted PDU is 4 octets longer than its plaintext and max_len is NOT raised for the caller: the discovery's default of 27
+    drops every encrypted PDU of more than 23 plaintext octets.  Pass max_len >= 31 for a connection of 27-octet PDUs and 255 with
+    data length extension.
+    Returns (conns, cands, tracks, pkts, data, data_pkts, msgs, payload, crypt, crypt_pkts, plain_pkts): le_data's tuple, in which
+    data and data_pkts are the data stage's records and msgs and payload the messages over PLAINTEXT (rule 8), then LE_CRYPT_DTYPE
+    records parallel to conns, LE_CRYPT_PKT_DTYPE records parallel to cands and the LE_DATA_PKT_DTYPE records under the effective
+    members, parallel to cands."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if pitch_words is None:
+        pitch_words = len(words) // n_streams
+    if n_words is None:
+        n_words = pitch_words
+    assert n_words <= pitch_words and (n_streams - 1) * pitch_words + n_words <= len(words)
+    phys = np.ascontiguousarray(np.broadcast_to(np.asarray(phys_channels, dtype=np.uint16), (n_streams,)))
+    if not isinstance(keys, np.ndarray):
+        keys = np.frombuffer(b"".join(bytes(k) for k in keys), np.uint8)
+    keys = np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1, 16)
+    conns = np.empty(max(conn_cap, 1), dtype=LE_CONN_DTYPE)
+    tracks = np.empty(max(conn_cap, 1), dtype=LE_TRACK_DTYPE)
+    data = np.empty(max(conn_cap, 1), dtype=LE_DATA_DTYPE)
+    crypt = np.empty(max(conn_cap, 1), dtype=LE_CRYPT_DTYPE)
+    cands = np.empty(max(cand_cap, 1), dtype=LE_CAND_DTYPE)
+    pkts = np.empty(max(cand_cap, 1), dtype=LE_TRACK_PKT_DTYPE)
+    data_pkts = np.empty(max(cand_cap, 1), dtype=LE_DATA_PKT_DTYPE)
+    crypt_pkts = np.empty(max(cand_cap, 1), dtype=LE_CRYPT_PKT_DTYPE)
+    plain_pkts = np.empty(max(cand_cap, 1), dtype=LE_DATA_PKT_DTYPE)
+    msgs = np.empty(max(msg_cap, 1), dtype=LE_MSG_DTYPE)
+    payload = np.empty(max(byte_cap, 1), dtype=np.uint8)
+    n_cands, n_msgs, n_bytes = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    n = check(lib().btbbx_le_crypt_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, _ptr(phys), max_len, min_count,
+                                        _ptr(conns), conn_cap, _ptr(cands), cand_cap, C.byref(n_cands), unit_bits, ifs_bits, jitter_bits,
+                                        flags, _ptr(tracks), _ptr(pkts), _ptr(data), _ptr(data_pkts), _ptr(keys), len(keys), window,
+                                        _ptr(crypt), _ptr(crypt_pkts), _ptr(plain_pkts), _ptr(msgs), msg_cap, C.byref(n_msgs),
+                                        _ptr(payload), byte_cap, C.byref(n_bytes)), "btbbx_le_crypt_host")
+    if (n > conn_cap or n_cands.value > cand_cap or n_msgs.value > msg_cap or n_bytes.value > byte_cap) and not truncate:
+        raise BtbbError("buffers too small: %d connections > %d, %d candidates > %d, %d messages > %d or %d octets > %d" % (
+            n, conn_cap, n_cands.value, cand_cap, n_msgs.value, msg_cap, n_bytes.value, byte_cap))
+    nc, nk, nm = min(n, conn_cap), min(n_cands.value, cand_cap), min(n_msgs.value, msg_cap)
+    msgs = msgs[:nm].copy()
+    stored = msgs[(msgs["flags"] & LE_MSG_STORED) != 0]
+    kept = int(stored["byte_offset"][-1]) + int(stored["bytes"][-1]) if len(stored) else 0
+    return (conns[:nc].copy(), cands[:nk].copy(), tracks[:nc].copy(), pkts[:nk].copy(), data[:nc].copy(), data_pkts[:nk].copy(), msgs,
+            payload[:kept].copy(), crypt[:nc].copy(), crypt_pkts[:nk].copy(), plain_pkts[:nk].copy())
 
 
 class DeviceBuffer:

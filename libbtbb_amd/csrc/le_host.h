@@ -1,4 +1,4 @@
-// le_host.h -- the host wrappers of the LE stages (included by le.hip, behind le_data.h).  Every wrapper runs one chain: the
+// le_host.h -- the host wrappers of the LE stages (included by le.hip, behind le_crypt.h).  Every wrapper runs one chain: the
 // capture goes to the device, the discovery scans and groups it, the tracking works on what the discovery stored, the wrapper's own
 // stages follow on the same stream and the records are copied out.  The chain is written here once:
 //
@@ -11,7 +11,7 @@
 // A wrapper calls these in this order, launches its own stages between le_host_track and le_host_finish, and names its own
 // outputs (LeHostOut).  Nothing of one call outlives it: what a tail's size depends on is captured by the callable that computes it.
 #pragma once
-#include "le_data.h"
+#include "le_crypt.h"
 
 // What the discovery leaves on the device, inside the caller's CallScope: the counters, the sorted candidates, the connection
 // records and, behind them, `tail` (tail_bytes(dev_cap, dev_conns) bytes for what a caller runs next on the same stream).
@@ -350,7 +350,31 @@ static LdtHostTail le_data_host_layout(uint32_t dev_cap, uint32_t dev_conns, uin
 	return T;
 }
 
-// the messages and their octets are copied behind the frame's synchronize: how many there are is known only then
+// the first have_msgs message records and the stored prefix of their octets, copied out behind the frame's synchronize: how many
+// there are is known only then
+static int le_host_messages(btbbx_le_msg *msgs, const btbbx_le_msg *d_msgs, uint64_t have_msgs, uint8_t *bytes, const uint8_t *d_bytes,
+			    hipStream_t q)
+{
+	if (!have_msgs)
+		return BTBBX_OK;
+	HIP_TRY(hipMemcpyAsync(msgs, d_msgs, (size_t)have_msgs * sizeof(btbbx_le_msg), hipMemcpyDeviceToHost, q));
+	HIP_TRY(hipStreamSynchronize(q));
+	uint64_t lo = 0, hi = have_msgs;                                // the stored messages are a prefix: the first that is not
+	while (lo < hi) {
+		const uint64_t mid = lo + (hi - lo) / 2;
+		if (msgs[mid].flags & BTBBX_LE_MSG_STORED)
+			lo = mid + 1;
+		else
+			hi = mid;
+	}
+	const uint64_t stored = lo ? msgs[lo - 1].byte_offset + msgs[lo - 1].bytes : 0;
+	if (stored) {
+		HIP_TRY(hipMemcpyAsync(bytes, d_bytes, (size_t)stored, hipMemcpyDeviceToHost, q));
+		HIP_TRY(hipStreamSynchronize(q));
+	}
+	return BTBBX_OK;
+}
+
 extern "C" int64_t btbbx_le_data_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
 				      uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
 				      btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
@@ -390,29 +414,99 @@ extern "C" int64_t btbbx_le_data_host(const uint64_t *words, uint64_t n_words, u
 	const int64_t ret = le_host_finish(a, r, 0, outs, 2);
 	if (ret < 0 || !r.nc)
 		return ret;
-	const uint64_t n_msgs = (uint32_t)counts[1], have_msgs = std::min<uint64_t>(n_msgs, T.msg_cap);
+	const uint64_t n_msgs = (uint32_t)counts[1];
 	if (n_msgs_out)
 		*n_msgs_out = n_msgs;
 	if (n_bytes_out)
 		*n_bytes_out = counts[0];
-	if (have_msgs) {
-		HIP_TRY(hipMemcpyAsync(msgs, d_msgs, (size_t)have_msgs * sizeof(btbbx_le_msg), hipMemcpyDeviceToHost, r.q));
-		HIP_TRY(hipStreamSynchronize(r.q));
-		uint64_t lo = 0, hi = have_msgs;                        // the stored messages are a prefix: the first that is not
-		while (lo < hi) {
-			const uint64_t mid = lo + (hi - lo) / 2;
-			if (msgs[mid].flags & BTBBX_LE_MSG_STORED)
-				lo = mid + 1;
-			else
-				hi = mid;
-		}
-		const uint64_t stored = lo ? msgs[lo - 1].byte_offset + msgs[lo - 1].bytes : 0;
-		if (stored) {
-			HIP_TRY(hipMemcpyAsync(bytes, d_bytes, (size_t)stored, hipMemcpyDeviceToHost, r.q));
-			HIP_TRY(hipStreamSynchronize(r.q));
-		}
+	rc = le_host_messages(msgs, d_msgs, std::min<uint64_t>(n_msgs, T.msg_cap), bytes, d_bytes, r.q);
+	return rc ? rc : ret;
+}
+
+// ---- decryption -------------------------------------------------------------------------------------------------------------------
+
+// this stage's part of the tail, behind the data stage's (whose messages and octets are not kept: its caps are 0 here)
+struct LxHostTail {
+	size_t scratch, crypt, cpkts, ppkts, msgs, counts, bytes, keys, total;
+};
+
+static LxHostTail le_crypt_host_layout(uint32_t dev_cap, uint32_t dev_conns, uint32_t n_keys, const LdtHostTail &T)
+{
+	LxHostTail C;
+	size_t at = le_data_host_layout(dev_cap, dev_conns, 0, 0).total;
+	auto take = [&](size_t bytes) { const size_t here = at; at += ld_up(bytes); return here; };
+	C.scratch = take(le_crypt_layout(dev_cap, dev_conns, n_keys).total);
+	C.crypt = take((size_t)dev_conns * sizeof(btbbx_le_crypt));
+	C.cpkts = take((size_t)dev_cap * sizeof(btbbx_le_crypt_pkt));
+	C.ppkts = take((size_t)dev_cap * sizeof(btbbx_le_data_pkt));
+	C.msgs = take((size_t)T.msg_cap * sizeof(btbbx_le_msg));
+	C.counts = take(256);
+	C.bytes = take((size_t)T.byte_cap + 8);
+	C.keys = take(16 * (size_t)n_keys);
+	C.total = at;
+	return C;
+}
+
+extern "C" int64_t btbbx_le_crypt_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				       uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+				       btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+				       uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+				       btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_data *data, btbbx_le_data_pkt *data_pkts,
+				       const uint8_t *keys, uint32_t n_keys, uint32_t window, btbbx_le_crypt *crypt,
+				       btbbx_le_crypt_pkt *crypt_pkts, btbbx_le_data_pkt *plain_pkts, btbbx_le_msg *msgs, uint64_t msg_cap,
+				       uint64_t *n_msgs_out, uint8_t *bytes, uint64_t byte_cap, uint64_t *n_bytes_out)
+{
+	const LeHostArgs a = LE_HOST_ARGS("btbbx_le_crypt_host");
+	int rc = le_crypt_check_keys(a.who, n_keys, window);
+	if (!rc)
+		rc = le_host_check(a, nullptr, (!data && conn_cap) || (!crypt && conn_cap) || !keys || (!msgs && msg_cap) || (!bytes && byte_cap));
+	if (rc)
+		return rc;
+	if (n_msgs_out)
+		*n_msgs_out = 0;
+	if (n_bytes_out)
+		*n_bytes_out = 0;
+	CallScope scope;
+	LeHostRun r;
+	const auto caps = [&](uint32_t cap, uint32_t k) { return le_data_host_layout(cap, k, msg_cap, byte_cap); };   // (the caps as the data wrapper cuts them)
+	rc = le_host_begin(a, [&](uint32_t cap, uint32_t k) { return le_crypt_host_layout(cap, k, n_keys, caps(cap, k)).total; }, &r);
+	if (rc || !r.have)
+		return rc;
+	const LdtHostTail T = caps(r.dev_cap, r.dev_conns), D = le_data_host_layout(r.dev_cap, r.dev_conns, 0, 0);
+	const LxHostTail C = le_crypt_host_layout(r.dev_cap, r.dev_conns, n_keys, T);
+	btbbx_le_data_pkt *d_dpkts = (btbbx_le_data_pkt *)(r.own + D.dpkts);
+	btbbx_le_msg *d_msgs = (btbbx_le_msg *)(r.own + C.msgs);
+	uint64_t *d_counts = (uint64_t *)(r.own + C.counts), *d_data_counts = (uint64_t *)(r.own + D.counts), counts[2] = {0, 0};
+	uint8_t *d_bytes = (uint8_t *)(r.own + C.bytes), *d_keys = (uint8_t *)(r.own + C.keys);
+	if (r.nc) {
+		HIP_TRY(hipMemcpyAsync(d_keys, keys, 16 * (size_t)n_keys, hipMemcpyHostToDevice, r.q));
+		if ((rc = le_host_track(a, r)))
+			return rc;
+		rc = le_data_launch(r.d_words, n_words, pitch_words, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count, r.dev_conns,
+				    r.d_pkts, (btbbx_le_data *)(r.own + D.data), d_dpkts, (btbbx_le_msg *)(r.own + D.msgs), 0,
+				    (uint32_t *)(d_data_counts + 1), (uint8_t *)(r.own + D.bytes), 0, d_data_counts, r.own + D.scratch, r.q);
+		if (!rc)
+			rc = le_crypt_launch(r.d_words, n_words, pitch_words, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count,
+					     r.dev_conns, r.d_pkts, d_dpkts, d_keys, n_keys, window, (btbbx_le_crypt *)(r.own + C.crypt),
+					     (btbbx_le_crypt_pkt *)(r.own + C.cpkts), (btbbx_le_data_pkt *)(r.own + C.ppkts), d_msgs, T.msg_cap,
+					     (uint32_t *)(d_counts + 1), d_bytes, T.byte_cap, d_counts, r.own + C.scratch, r.q);
+		if (rc)
+			return rc;
+		HIP_TRY(hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, r.q));
 	}
-	return ret;
+	const LeHostOut outs[] = {{data, r.own + D.data, sizeof(btbbx_le_data), false}, {data_pkts, d_dpkts, sizeof(btbbx_le_data_pkt), true},
+				  {crypt, r.own + C.crypt, sizeof(btbbx_le_crypt), false}, {crypt_pkts, r.own + C.cpkts, sizeof(btbbx_le_crypt_pkt), true},
+				  {plain_pkts, r.own + C.ppkts, sizeof(btbbx_le_data_pkt), true}};
+	const int64_t ret = le_host_finish(a, r, 0, outs, 5);
+	if (ret < 0 || !r.nc)
+		return ret;
+	const uint64_t n_msgs = (uint32_t)counts[1];
+	if (n_msgs_out)
+		*n_msgs_out = n_msgs;
+	if (n_bytes_out)
+		*n_bytes_out = counts[0];
+	rc = le_host_messages(msgs, d_msgs, std::min<uint64_t>(n_msgs, T.msg_cap), bytes, d_bytes, r.q);
+	return rc ? rc : ret;
 }
 
 // ---- following: the follow stage or the span stage behind the seed stage ---------------------------------------------------------
