@@ -1156,6 +1156,115 @@ int64_t btbbx_le_crypt_host(const uint64_t *words, uint64_t n_words, uint64_t pi
 			    btbbx_le_data_pkt *plain_pkts, btbbx_le_msg *msgs, uint64_t msg_cap, uint64_t *n_msgs_out, uint8_t *bytes,
 			    uint64_t byte_cap, uint64_t *n_bytes_out);
 
+/* ---- LE legacy pairing key recovery: SMP exchange, TK search, STK --------------------------
+ * Behind the data stage or the decryption stage, on the device: for every connection the Security Manager exchange among its
+ * L2CAP messages (CID 0x0006), the temporary key (TK) of an LE legacy pairing -- 0 for Just Works or a six-digit passkey -- by
+ * trying every value below tk_limit against the Confirm values, the short-term key (STK) under it as a key table that
+ * btbbx_le_crypt_device takes as it is, and the long-term keys the peers distribute.  It changes nothing of its input.
+ *
+ * The input is the data stage's message outputs, or the decryption stage's, which have the same shapes (d_msgs, d_msg_count,
+ * msg_cap, d_bytes, byte_cap), the connection count (d_conn_count, conn_cap; K = the smaller of the two) and the seed stage's
+ * d_seeds, parallel to the connections.  A caller may write the seeds itself: the stage reads flags, init_a, adv_a, tx_add and
+ * rx_add, nothing else.  The first W = min(*d_msg_count, msg_cap) message records are looked at.  A record is skipped if its
+ * conn >= K, its byte_offset + bytes > byte_cap, or its bytes < 4 + l2cap_len: this guards a list from elsewhere (the data stage
+ * writes none of these).  All arithmetic is integer arithmetic.
+ *   1. SMP MESSAGE.  Record M is an SMP message iff its flags have COMPLETE and STORED, cid == 0x0006 and l2cap_len >= 1.  Its
+ *      octets are v[k] = d_bytes[byte_offset + 4 + k], its code is v[0].
+ *   2. PROCEDURE, per connection, by ascending M (the data stage's rule 6 makes that the time order within a connection):
+ *        PREQ   role CENTRAL     code 0x01  l2cap_len 7    the first such SMP message
+ *        PRSP   role PERIPHERAL  code 0x02  l2cap_len 7    the first above PREQ
+ *        MCONF  role CENTRAL     code 0x03  l2cap_len 17   the first above PRSP
+ *        SCONF  role PERIPHERAL  code 0x03  l2cap_len 17   the first above MCONF
+ *        MRAND  role CENTRAL     code 0x04  l2cap_len 17   the first above SCONF if SCONF exists, else above MCONF
+ *        SRAND  role PERIPHERAL  code 0x04  l2cap_len 17   the first above MRAND
+ *      A missing message leaves everything that is defined "above" it missing too, except where the table says otherwise.
+ *   3. METHOD.  Without PREQ and PRSP: NONE.  preq[j] and pres[j] are the octets v[j] of PREQ and PRSP.  ks = min(preq[4],
+ *      pres[4]); INVALID iff ks < 7 or ks > 16; otherwise SECURE iff both preq[3] and pres[3] have bit 3 set (LE Secure
+ *      Connections: there is no TK and nothing is searched); otherwise OOB iff preq[2] == 1 and pres[2] == 1 (the TK is 128 bits
+ *      and is not searched); otherwise LEGACY.
+ *   4. CHECKS.  The central's check exists iff MCONF and MRAND do, the peripheral's iff SCONF and SRAND do.  A connection is
+ *      ARMED iff its method is LEGACY, its seed is SEEDED, at least one check exists and tk_limit >= 1.  With 16-octet arrays
+ *      written least significant octet first: a = iat, rat, preq[0..6], pres[0..6] with iat = seed.tx_add & 1 and rat =
+ *      seed.rx_add & 1; b = adv_a[0..5], init_a[0..5], 0, 0, 0, 0; r = the octets 1..16 of the check's Random message; conf = the
+ *      octets 1..16 of its Confirm message.  The AES input of an array x is block[j] = x[15 - j], and an output block o reads
+ *      back as x[i] = o[15 - i].  Key octets, most significant first: 0..11 are zero and 12..15 are BE32(tk).  A check HOLDS
+ *      under tk iff AES(key(tk), AES(key(tk), r ^ a) ^ b) == conf.
+ *   5. SEARCH.  The connection's TK is the smallest tk < tk_limit under which every check that exists holds; if there is one the
+ *      connection is CRACKED, otherwise tk = 0xffffffff.  tk_limit is 0..1000000: 1 tries Just Works only, 0 searches nothing.
+ *   6. STK.  Iff CRACKED and both MRAND and SRAND exist: c = mrand[0..7], srand[0..7], least significant first, the octets 1..8
+ *      of each Random message.  The STK is AES(key(tk), block(c)), output octet 0 first, with its octets 0 .. 15 - ks set to
+ *      zero.  Output octet 0 first is the byte order btbbx_le_crypt_device takes for d_keys.
+ *   7. KEY TABLE.  The connections that have an STK take, by ascending connection index, the slots 0, 1, ... of d_keys; key_cap
+ *      is 0..64.  *d_key_count = the number of all connections with an STK: the stage WRITES it, it does not add to it.  The slots
+ *      from min(count, key_cap) to key_cap are written as zeros, so the table can go to the decryption stage as it is, with
+ *      n_keys = key_cap.  A connection beyond key_cap keeps its STK in its record and gets key = 0xff.
+ *   8. DISTRIBUTED KEYS.  Per (connection, role) the first SMP message with code 0x06 and l2cap_len 17: ltk[role][j] = v[16 - j],
+ *      which is AES key byte order, and the keys flag LTK_CENTRAL or LTK_PERIPHERAL is set.  This is found wherever the messages
+ *      are readable, in practice when the stage runs over the decryption stage's output.  With tk_limit == 0 the stage does
+ *      rules 1 to 3, 8 and 9 only.
+ *   9. RECORDS.  Every byte of d_pairs[0 .. K) is written, nothing behind it.  A connection without any of the above gets zeros,
+ *      the six message indices and tk as 0xffffffff and key as 0xff.
+ * LIMITS: only the first pairing of a connection is recognised, a failed pairing followed by a second one is not followed; a
+ * connection that is not SEEDED is never ARMED, its procedure is still reported; SECURE and OOB pairings are named, not broken;
+ * EDIV / Rand, IRK and CSRK are not extracted; SMP messages that the data stage left unstored (msg_cap, byte_cap) or incomplete
+ * (a lost fragment) do not count. */
+#define BTBBX_LE_PAIR_NONE     0u    /* btbbx_le_pair.method */
+#define BTBBX_LE_PAIR_LEGACY   1u
+#define BTBBX_LE_PAIR_SECURE   2u
+#define BTBBX_LE_PAIR_OOB      3u
+#define BTBBX_LE_PAIR_INVALID  4u
+#define BTBBX_LE_PAIR_PREQ     1u    /* btbbx_le_pair.flags */
+#define BTBBX_LE_PAIR_PRSP     2u
+#define BTBBX_LE_PAIR_MCONF    4u
+#define BTBBX_LE_PAIR_SCONF    8u
+#define BTBBX_LE_PAIR_MRAND    16u
+#define BTBBX_LE_PAIR_SRAND    32u
+#define BTBBX_LE_PAIR_ARMED    64u
+#define BTBBX_LE_PAIR_CRACKED  128u
+#define BTBBX_LE_PAIR_KEY_STK            1u   /* btbbx_le_pair.keys */
+#define BTBBX_LE_PAIR_KEY_LTK_CENTRAL    2u
+#define BTBBX_LE_PAIR_KEY_LTK_PERIPHERAL 4u
+
+typedef struct btbbx_le_pair {       /* 88 bytes, parallel to conns */
+	uint8_t  stk[16];            /* the STK, rule 6 */
+	uint8_t  ltk[2][16];         /* distributed LTKs, CENTRAL then PERIPHERAL, rule 8 */
+	uint32_t preq, prsp, mconf, sconf, mrand, srand;   /* message indices, 0xffffffff if none */
+	uint32_t tk;                 /* rule 5 */
+	uint8_t  method;             /* NONE 0, LEGACY 1, SECURE 2, OOB 3, INVALID 4 */
+	uint8_t  flags;              /* PREQ 1, PRSP 2, MCONF 4, SCONF 8, MRAND 16, SRAND 32, ARMED 64, CRACKED 128 */
+	uint8_t  keys;               /* STK 1, LTK_CENTRAL 2, LTK_PERIPHERAL 4 */
+	uint8_t  key_size;           /* ks, rule 3 */
+	uint8_t  key;                /* slot in the key table, 0xff if none */
+	uint8_t  reserved[7];        /* written as 0 */
+} btbbx_le_pair;
+
+/* Nothing is read back and the call is asynchronous on hip_stream.  d_scratch: btbbx_le_pair_scratch_bytes(conn_cap) bytes (about
+ * 150 per connection), 16-byte aligned.  The count of launches, 12, depends on nothing.
+ * BTBBX_E_ARG, before any launch: a null pointer (d_msgs may be null with msg_cap 0, d_bytes with byte_cap 0, d_keys with key_cap
+ * 0), tk_limit > 1000000, key_cap > 64, d_seeds, d_msgs or d_pairs not 8-byte aligned (the counters: 4), a scratch that is too small
+ * or not 16-byte aligned.  conn_cap == 0 succeeds and writes only the key count, as 0, and the zeroed key table. */
+size_t btbbx_le_pair_scratch_bytes(uint32_t conn_cap);
+int btbbx_le_pair_device(const uint32_t *d_conn_count, uint32_t conn_cap, const btbbx_le_seed *d_seeds,
+			 const btbbx_le_msg *d_msgs, const uint32_t *d_msg_count, uint32_t msg_cap,
+			 const uint8_t *d_bytes, uint64_t byte_cap, uint32_t tk_limit,
+			 btbbx_le_pair *d_pairs, uint8_t *d_keys, uint32_t key_cap, uint32_t *d_key_count,
+			 void *d_scratch, size_t scratch_bytes, void *hip_stream);
+
+/* Host wrapper: btbbx_le_epoch_host's chain (advertising scan, tracking, seed stage) with the data stage and this stage as its
+ * last stage on the same stream.  btbbx_le_epoch_host's arguments up to and including seeds and its return value; msg_cap and
+ * byte_cap: the device-side room for the data stage's messages, which are not copied out; pairs: conn_cap records, parallel to
+ * conns; keys: 16 * key_cap octets (may be NULL with key_cap 0), the key table of rule 7; *n_keys_out (may be NULL) =
+ * *d_key_count.  A capture without a candidate or without a stored connection gives a zeroed table and the count 0.
+ * BTBBX_E_ARG: btbbx_le_epoch_host's conditions, pairs NULL with conn_cap != 0, keys NULL with key_cap != 0, tk_limit > 1000000,
+ * key_cap > 64. */
+int64_t btbbx_le_pair_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			   uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+			   btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+			   uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+			   int adv_errors, btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_seed *seeds,
+			   uint64_t msg_cap, uint64_t byte_cap, uint32_t tk_limit, btbbx_le_pair *pairs, uint8_t *keys,
+			   uint32_t key_cap, uint32_t *n_keys_out);
+
 /* ---- hop selection and CLK1-27 reversal ------------------------- */
 #define BTBBX_SEQUENCE_LENGTH 134217728u   /* values of CLK1-27, bluetooth_piconet.h:102 */
 

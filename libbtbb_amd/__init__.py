@@ -164,6 +164,17 @@ LE_CRYPT_DTYPE = np.dtype([("session_key", "u1", (16,)), ("iv", "u1", (8,)), ("r
 LE_CRYPT_PKT_DTYPE = np.dtype([("counter", "<u4"), ("ordinal", "<u4"), ("state", "u1"), ("skew", "u1"), ("opcode", "u1"),
                                ("counter_hi", "u1"), ("reserved", "u1", (4,))])
 assert LE_CRYPT_DTYPE.itemsize == 56 and LE_CRYPT_PKT_DTYPE.itemsize == 16
+# LE legacy pairing key recovery (include/btbbx.h btbbx_le_pair; le_pair.h checks the C layout with a static_assert): a
+# connection's pairing method, what of the exchange was found, which keys its record holds
+LE_PAIR_NONE, LE_PAIR_LEGACY, LE_PAIR_SECURE, LE_PAIR_OOB, LE_PAIR_INVALID = range(5)
+(LE_PAIR_PREQ, LE_PAIR_PRSP, LE_PAIR_MCONF, LE_PAIR_SCONF, LE_PAIR_MRAND, LE_PAIR_SRAND, LE_PAIR_ARMED,
+ LE_PAIR_CRACKED) = 1, 2, 4, 8, 16, 32, 64, 128
+LE_PAIR_KEY_STK, LE_PAIR_KEY_LTK_CENTRAL, LE_PAIR_KEY_LTK_PERIPHERAL = 1, 2, 4
+LE_PAIR_MAX_TK, LE_PAIR_MAX_KEYS = 1000000, 64
+LE_PAIR_DTYPE = np.dtype([("stk", "u1", (16,)), ("ltk", "u1", (2, 16)), ("preq", "<u4"), ("prsp", "<u4"), ("mconf", "<u4"),
+                          ("sconf", "<u4"), ("mrand", "<u4"), ("srand", "<u4"), ("tk", "<u4"), ("method", "u1"), ("flags", "u1"),
+                          ("keys", "u1"), ("key_size", "u1"), ("key", "u1"), ("reserved", "u1", (7,))])
+assert LE_PAIR_DTYPE.itemsize == 88
 
 # one surveyed piconet (include/btbbx.h btbbx_survey_rec; survey.hip checks the C layout with static_asserts)
 SURVEY_DTYPE = np.dtype([("lap", "<u4"), ("flags", "<u4"), ("uap", "u1"), ("clk_offset", "u1"), ("used_channels", "u1"),
@@ -281,6 +292,10 @@ SIGNATURES = {
                                         _vp, _vp, _vp, _u32, _vp, _vp, _u64, _vp, _vp, C.c_size_t, _vp]),
     "btbbx_le_crypt_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
                                         _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "btbbx_le_pair_scratch_bytes": (C.c_size_t, [_u32]),
+    "btbbx_le_pair_device": (C.c_int, [_vp, _u32, _vp, _vp, _vp, _u32, _vp, _u64, _u32, _vp, _vp, _u32, _vp, _vp, C.c_size_t, _vp]),
+    "btbbx_le_pair_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
+                                       C.c_int, _vp, _vp, _vp, _u64, _u64, _u32, _vp, _vp, _u32, _vp]),
     "btbbx_survey_scratch_bytes": (C.c_size_t, [_u32]),
     "btbbx_survey_hits_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp,
                                            _vp, C.c_size_t, _vp]),
@@ -727,6 +742,54 @@ def le_decrypt(words, search_bits, phys_channels, keys, window=8, max_len=27, mi
     kept = int(stored["byte_offset"][-1]) + int(stored["bytes"][-1]) if len(stored) else 0
     return (conns[:nc].copy(), cands[:nk].copy(), tracks[:nc].copy(), pkts[:nk].copy(), data[:nc].copy(), data_pkts[:nk].copy(), msgs,
             payload[:kept].copy(), crypt[:nc].copy(), crypt_pkts[:nk].copy(), plain_pkts[:nk].copy())
+
+
+def le_pair(words, search_bits, phys_channels, tk_limit=LE_PAIR_MAX_TK, key_cap=LE_PAIR_MAX_KEYS, max_len=27, min_count=2, n_streams=1,
+            pitch_words=None, n_words=None, unit_bits=1250, ifs_bits=200, jitter_bits=50, flags=LE_TRACK_REMAP, adv_errors=0,
+            conn_cap=1 << 12, cand_cap=1 << 20, truncate=False, msg_cap=1 << 16, byte_cap=1 << 22):
+    """le_follow's chain up to the seeds, then the data stage and LE legacy pairing key recovery (include/btbbx.h
+    btbbx_le_pair_device): for every connection whose CONNECT_IND and Security Manager exchange are in the capture the temporary key
+    -- every value below tk_limit (0..1000000; 1: Just Works only, 0: search nothing) is tried against the Confirm values -- and the
+    short-term key under it.  key_cap (0..64): the slots of the key table; msg_cap and byte_cap: the device-side room for the
+    messages that are searched for the exchange, which are not returned.  le_follow's other parameters.
+    Returns (conns, cands, tracks, pkts, seeds, pairs, keys, n_keys): le_follow's arrays up to seeds, LE_PAIR_DTYPE records parallel
+    to conns, the key table as a (key_cap, 16) uint8 array in the byte order le_decrypt takes, unused slots zero, and the number of
+    connections with a short-term key, which may exceed key_cap."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if pitch_words is None:
+        pitch_words = len(words) // n_streams
+    if n_words is None:
+        n_words = pitch_words
+    assert n_words <= pitch_words and (n_streams - 1) * pitch_words + n_words <= len(words)
+    phys = np.ascontiguousarray(np.broadcast_to(np.asarray(phys_channels, dtype=np.uint16), (n_streams,)))
+    conns = np.empty(max(conn_cap, 1), dtype=LE_CONN_DTYPE)
+    tracks = np.empty(max(conn_cap, 1), dtype=LE_TRACK_DTYPE)
+    seeds = np.empty(max(conn_cap, 1), dtype=LE_SEED_DTYPE)
+    pairs = np.empty(max(conn_cap, 1), dtype=LE_PAIR_DTYPE)
+    cands = np.empty(max(cand_cap, 1), dtype=LE_CAND_DTYPE)
+    pkts = np.empty(max(cand_cap, 1), dtype=LE_TRACK_PKT_DTYPE)
+    keys = np.zeros((max(key_cap, 1), 16), dtype=np.uint8)
+    n_cands, n_keys = C.c_uint64(0), C.c_uint32(0)
+    n = check(lib().btbbx_le_pair_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, _ptr(phys), max_len, min_count,
+                                       _ptr(conns), conn_cap, _ptr(cands), cand_cap, C.byref(n_cands), unit_bits, ifs_bits, jitter_bits,
+                                       flags, adv_errors, _ptr(tracks), _ptr(pkts), _ptr(seeds), msg_cap, byte_cap, tk_limit, _ptr(pairs),
+                                       _ptr(keys), key_cap, C.byref(n_keys)), "btbbx_le_pair_host")
+    if (n > conn_cap or n_cands.value > cand_cap) and not truncate:
+        raise BtbbError("buffers too small: %d connections > %d or %d candidates > %d" % (n, conn_cap, n_cands.value, cand_cap))
+    nc, nk = min(n, conn_cap), min(n_cands.value, cand_cap)
+    return (conns[:nc].copy(), cands[:nk].copy(), tracks[:nc].copy(), pkts[:nk].copy(), seeds[:nc].copy(), pairs[:nc].copy(),
+            keys[:key_cap].copy(), int(n_keys.value))
+
+
+def le_crack(words, search_bits, phys_channels, tk_limit=LE_PAIR_MAX_TK, key_cap=LE_PAIR_MAX_KEYS, window=8, adv_errors=0, **kw):
+    """le_pair, then le_decrypt under the short-term keys it recovered: capture in, plaintext out, no key given.  kw: what both take
+    (max_len, min_count, n_streams, pitch_words, n_words, the timing, flags, the caps, truncate); max_len is le_decrypt's, see there.
+    Returns (pair, plain): le_pair's tuple and le_decrypt's.  When no key was found nothing is raised and plain is None."""
+    pair = le_pair(words, search_bits, phys_channels, tk_limit=tk_limit, key_cap=key_cap, adv_errors=adv_errors, **kw)
+    found = min(pair[7], key_cap)
+    if not found:
+        return pair, None
+    return pair, le_decrypt(words, search_bits, phys_channels, pair[6][:found], window=window, **kw)
 
 
 class DeviceBuffer:

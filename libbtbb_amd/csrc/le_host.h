@@ -1,4 +1,4 @@
-// le_host.h -- the host wrappers of the LE stages (included by le.hip, behind le_crypt.h).  Every wrapper runs one chain: the
+// le_host.h -- the host wrappers of the LE stages (included by le.hip, behind le_pair.h).  Every wrapper runs one chain: the
 // capture goes to the device, the discovery scans and groups it, the tracking works on what the discovery stored, the wrapper's own
 // stages follow on the same stream and the records are copied out.  The chain is written here once:
 //
@@ -11,7 +11,7 @@
 // A wrapper calls these in this order, launches its own stages between le_host_track and le_host_finish, and names its own
 // outputs (LeHostOut).  Nothing of one call outlives it: what a tail's size depends on is captured by the callable that computes it.
 #pragma once
-#include "le_crypt.h"
+#include "le_pair.h"
 
 // What the discovery leaves on the device, inside the caller's CallScope: the counters, the sorted candidates, the connection
 // records and, behind them, `tail` (tail_bytes(dev_cap, dev_conns) bytes for what a caller runs next on the same stream).
@@ -145,12 +145,15 @@ struct LeHostRun : LeDiscHostRun {
 };
 
 // an output of a wrapper beyond conns / tracks / pkts / cands: one record of `size` bytes per connection, or per candidate; a
-// per-candidate array is filled with 0xff when no connection was stored (no candidate is a member then)
+// per-candidate array is filled with 0xff when no connection was stored (no candidate is a member then).  fixed >= 0: a table of
+// that many records whatever was found (the pairing stage's key table and its count), zeros when no connection was stored
 struct LeHostOut {
 	void *dst;
 	const void *src;
 	size_t size;
 	bool per_cand;
+	int64_t fixed = -1;
+	size_t count(size_t per_conn, size_t per_candidate) const { return fixed >= 0 ? (size_t)fixed : (per_cand ? per_candidate : per_conn); }
 };
 
 // adv_errors: NULL when the wrapper scans no advertising channel; missing: one of the wrapper's own outputs is NULL and must not be
@@ -215,12 +218,14 @@ static int64_t le_host_finish(const LeHostArgs &a, const LeHostRun &r, int rc, c
 		out(a.tracks, r.d_tracks, (size_t)r.nc * sizeof(btbbx_le_track));
 		out(a.pkts, r.d_pkts, (size_t)r.nk * sizeof(btbbx_le_track_pkt));
 		for (int o = 0; o < n_outs; o++)
-			out(outs[o].dst, outs[o].src, (size_t)(outs[o].per_cand ? r.nk : r.nc) * outs[o].size);
+			out(outs[o].dst, outs[o].src, outs[o].count(r.nc, r.nk) * outs[o].size);
 	} else {
 		if (a.pkts)
 			memset(a.pkts, 0xff, (size_t)r.nk * sizeof(btbbx_le_track_pkt));
 		for (int o = 0; o < n_outs; o++)
-			if (outs[o].per_cand && outs[o].dst)
+			if (outs[o].fixed >= 0 && outs[o].dst)
+				memset(outs[o].dst, 0, (size_t)outs[o].fixed * outs[o].size);
+			else if (outs[o].per_cand && outs[o].dst)
 				memset(outs[o].dst, 0xff, (size_t)r.nk * outs[o].size);
 	}
 	out(a.cands, r.d_cands, (size_t)r.nk * sizeof(btbbx_le_cand));
@@ -567,7 +572,7 @@ static int le_follow_host_adv(const LeHostArgs &a, const LeHostRun &r, uint64_t 
 // The chain of btbbx_le_epoch_host and btbbx_le_span_host: the advertising scan, the tracking, the seed stage and the wrapper's
 // last stage -- last(r, pitch_words, d_seeds, d_scratch, d_out): its launches --, whose scratch takes last_scratch(dev_cap, dev_conns)
 // bytes.  outs: the last stage's outputs (at most three; src is not read): their device records stand behind the scratch in this
-// order, dev_conns or dev_cap of them each, and d_out[o] is where those of outs[o] begin.
+// order, dev_conns or dev_cap of them each (or `fixed` of them), and d_out[o] is where those of outs[o] begin.
 // A failed launch does not end the call at once: the stream is synchronised and a spilled advertising block freed first
 template <class Scratch, class Last>
 static int64_t le_follow_host_chain(const LeHostArgs &a, int adv_errors, btbbx_le_seed *seeds, bool missing, Scratch last_scratch,
@@ -585,20 +590,26 @@ static int64_t le_follow_host_chain(const LeHostArgs &a, int adv_errors, btbbx_l
 	const auto records = [&](uint32_t cap, uint32_t conns, int upto) {
 		size_t at = ld_up((size_t)conns * sizeof(btbbx_le_seed)) + ld_up(last_scratch(cap, conns));
 		for (int o = 0; o < upto; o++)
-			at += ld_up((size_t)(outs[o].per_cand ? cap : conns) * outs[o].size);
+			at += ld_up(outs[o].count(conns, cap) * outs[o].size);
 		return at;
 	};
 	LeHostRun r;
 	rc = le_host_begin(a, [&](uint32_t cap, uint32_t conns) { return records(cap, conns, n_outs) + le_follow_adv_layout(adv_cap).total; }, &r);
-	if (rc || !r.have)
+	if (rc)
 		return rc;
+	if (!r.have) {                                          // no candidate: nothing to copy, a fixed table is zeros
+		for (int o = 0; o < n_outs; o++)
+			if (outs[o].fixed >= 0 && outs[o].dst)
+				memset(outs[o].dst, 0, (size_t)outs[o].fixed * outs[o].size);
+		return BTBBX_OK;
+	}
 	void *spill = nullptr;                                  // a second advertising block, when the first was too small
 	btbbx_le_seed *d_seeds = (btbbx_le_seed *)r.own;
 	LeHostOut all[4] = {{seeds, d_seeds, sizeof(btbbx_le_seed), false}};
 	char *d_out[3] = {nullptr, nullptr, nullptr};
 	for (int o = 0; o < n_outs; o++) {
 		d_out[o] = r.own + records(r.dev_cap, r.dev_conns, o);
-		all[o + 1] = {outs[o].dst, d_out[o], outs[o].size, outs[o].per_cand};
+		all[o + 1] = {outs[o].dst, d_out[o], outs[o].size, outs[o].per_cand, outs[o].fixed};
 	}
 	if (r.nc) {
 		char *ablock = r.own + records(r.dev_cap, r.dev_conns, n_outs);
@@ -659,4 +670,45 @@ extern "C" int64_t btbbx_le_span_host(const uint64_t *words, uint64_t n_words, u
 					      r.dev_conns, r.d_pkts, d_seeds, unit_bits, jitter_bits, max_updates, (btbbx_le_span *)d_out[0],
 					      (btbbx_le_span_pkt *)d_out[1], (btbbx_le_span_rec *)d_out[2], d_scratch, r.q);
 		});
+}
+
+// ---- pairing: the data stage and the pairing stage behind the seed stage ----------------------------------------------------------
+
+extern "C" int64_t btbbx_le_pair_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				       uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+				       btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+				       uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+				       int adv_errors, btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_seed *seeds,
+				       uint64_t msg_cap, uint64_t byte_cap, uint32_t tk_limit, btbbx_le_pair *pairs, uint8_t *keys,
+				       uint32_t key_cap, uint32_t *n_keys_out)
+{
+	const LeHostArgs a = LE_HOST_ARGS("btbbx_le_pair_host");
+	const int rc = le_pair_check_limits(a.who, tk_limit, key_cap);
+	if (rc)
+		return rc;
+	uint32_t n_keys = 0;
+	// the data stage's part (its scratch, records, messages and octets, none of them copied out), then this stage's scratch
+	const auto caps = [&](uint32_t cap, uint32_t k) { return le_data_host_layout(cap, k, msg_cap, byte_cap); };
+	const LeHostOut outs[] = {{pairs, nullptr, sizeof(btbbx_le_pair), false}, {keys, nullptr, 16, false, (int64_t)key_cap},
+				  {&n_keys, nullptr, sizeof(uint32_t), false, 1}};
+	const int64_t ret = le_follow_host_chain(
+		a, adv_errors, seeds, (!pairs && conn_cap) || (!keys && key_cap),
+		[&](uint32_t cap, uint32_t k) { return ld_up(caps(cap, k).total) + le_pair_layout(k).total; }, outs, 3,
+		[&](const LeHostRun &r, uint64_t pitch, const btbbx_le_seed *d_seeds, char *d_scratch, char *const *d_out) {
+			const LdtHostTail T = caps(r.dev_cap, r.dev_conns);
+			btbbx_le_msg *d_msgs = (btbbx_le_msg *)(d_scratch + T.msgs);
+			uint64_t *d_counts = (uint64_t *)(d_scratch + T.counts);
+			uint8_t *d_bytes = (uint8_t *)(d_scratch + T.bytes);
+			int rc2 = le_data_launch(r.d_words, n_words, pitch, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count,
+						 r.dev_conns, r.d_pkts, (btbbx_le_data *)(d_scratch + T.data), (btbbx_le_data_pkt *)(d_scratch + T.dpkts),
+						 d_msgs, T.msg_cap, (uint32_t *)(d_counts + 1), d_bytes, T.byte_cap, d_counts, d_scratch + T.scratch, r.q);
+			if (!rc2)
+				rc2 = le_pair_launch(r.d_conn_count, r.dev_conns, d_seeds, d_msgs, (uint32_t *)(d_counts + 1), T.msg_cap, d_bytes,
+						     T.byte_cap, tk_limit, (btbbx_le_pair *)d_out[0], (uint8_t *)d_out[1], key_cap, (uint32_t *)d_out[2],
+						     d_scratch + ld_up(T.total), r.q);
+			return rc2;
+		});
+	if (ret >= 0 && n_keys_out)
+		*n_keys_out = n_keys;
+	return ret;
 }
