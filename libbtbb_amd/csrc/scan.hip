@@ -25,7 +25,7 @@
 // Known LAP: a bit-sliced mismatch count of the top 16 (12 for max_ac_errors < 2) sync-word bits prunes (0.2 % left for
 // max_ac_errors = 2), the survivors get the full popcount(window ^ syncword) of :433.
 //
-// scan_slide_kernel: two persistent 768-thread workgroups per CU (6 waves per SIMD; 64 KiB set + 12 KiB rings of LDS
+// scan_slide_kernel: two persistent 768-thread workgroups per CU (6 waves per SIMD; 64 KiB set + 12 KiB rings + 2.5 KiB syndrome tables of LDS
 // each) stride over tiles of 756 words (63 per wave); scan_known_lap_kernel: 256-thread workgroups, tiles of 512 words.  Pure integer
 // work, no MFMA; bound by VALU issue, not by HBM (DESIGN.md 3.1 and 6 say what it is bound by).
 //

@@ -154,8 +154,29 @@ __device__ __forceinline__ void lds_st_rec2(uint32_t byte_off, uint32_t x, uint3
 // w = the 64-symbol window at `offset` (the kernel keeps it with the candidate: by the time a
 // batch is verified the stream words have long left the L2, and re-reading them cost 40 % extra
 // HBM traffic).
-template <bool LDS_TABLES = true>
-__device__ __forceinline__ bool verify_lap_any(const ScanArgs &a, uint64_t w, uint32_t &lap, uint32_t &nerr_out)
+// TWO: the tables hold patterns of two errors or fewer (scan_slide_kernel's one-level form, the only caller that says so: the
+// launcher gives it no other tables).  context.cpp builds no second-level bitmap for them, so there is no test for one; a slot
+// holds two error positions, not five; and each of the two high syndrome bits is ONE v_bcnt of the XOR of the window's masked
+// halves instead of two chained ones (the drain's vector instructions by cause: profiles/r08_drain).  Its syndrome tables are
+// the three SYN3 tables at LDS byte `syn3_off` (below), not tabA / tabB in global memory: a drain is a chain of dependent
+// loads at the wave's highest priority, and with the tables in LDS it waits for one round trip to the L2 (the pattern table)
+// instead of two -- 0.3 to 0.6 % of a launch beside the same rule with global tables, ahead in eight rotations of nine
+// (profiles/r08_drain; the drains are 4.8 % of a launch, 2.5 of them the pattern look-up).
+// SYN3: tabA and tabB (window bits 34 .. 44 and 45 .. 56, 24 KiB) cut again into three tables of 8 + 8 + 7 bits, 2.5 KiB -- the
+// syndrome is linear in the window, tabB affine (it carries the class-0 constant, which stays in the last table alone).
+#define SYN3_WORDS 640u
+#define SYN3_BYTES (4u * SYN3_WORDS)
+static_assert(TABA_FIRST == 34 && TABA_BITS == 11 && TABB_BITS == 12, "the SYN3 tables are cut for window bits 34 .. 56 as 8 + 8 + 7");
+__device__ __forceinline__ uint32_t syn3_entry(const ScanTables &t, uint32_t i)
+{
+	if (i < 256u)
+		return t.tabA[i];                                                      // window bits 34 .. 41
+	if (i < 512u)
+		return t.tabA[((i - 256u) & 7u) << 8] ^ t.tabB[(i - 256u) >> 3] ^ t.tabB[0];   // 42 .. 44 (tabA) and 45 .. 49 (tabB, linear part)
+	return t.tabB[(i - 512u) << 5];                                            // 50 .. 56, with tabB's constant
+}
+template <bool LDS_TABLES = true, bool TWO = false>
+__device__ __forceinline__ bool verify_lap_any(const ScanArgs &a, uint64_t w, uint32_t &lap, uint32_t &nerr_out, uint32_t syn3_off = 0)
 {
 	uint32_t win = (uint32_t)(w >> 57);
 	uint32_t cls = __popc(win ^ BARKER1) <= 1 ? 1u : 0u;
@@ -166,12 +187,27 @@ __device__ __forceinline__ bool verify_lap_any(const ScanArgs &a, uint64_t w, ui
 	// the scan for tables built for three or more errors.)
 	const uint64_t low = w & LOW57;
 	const uint32_t ia = (uint32_t)(low >> TABA_FIRST) & ((1u << TABA_BITS) - 1), ib = (uint32_t)(low >> (TABA_FIRST + TABA_BITS));
-	const uint32_t s_lo = (uint32_t)low ^ (LDS_TABLES ? lds_ld(LDS_OFF_TABA + (ia << 2)) : a.t.tabA[ia])
-			      ^ (LDS_TABLES ? lds_ld(LDS_OFF_TABB + (ib << 2)) : a.t.tabB[ib]) ^ (cls ? a.t.kdiff : 0u);
-	const uint32_t s_hi = ((uint32_t)(a.t.kclass[cls] >> 32) ^ (__popcll(low & a.t.hi_mask[0]) & 1)
-			       ^ ((__popcll(low & a.t.hi_mask[1]) & 1) << 1)) & 3;
+	uint32_t s_lo;
+	if constexpr (TWO) {
+		const uint32_t hi = (uint32_t)(low >> 32);                                 // window bits 32 .. 56; a table index as a byte offset
+		s_lo = (uint32_t)low ^ lds_ld(syn3_off + (hi & 0x3fcu)) ^ lds_ld(syn3_off + 1024u + ((hi >> 8) & 0x3fcu))
+		       ^ lds_ld(syn3_off + 2048u + ((hi >> 16) & 0x1fcu)) ^ (cls ? a.t.kdiff : 0u);
+	} else {
+		s_lo = (uint32_t)low ^ (LDS_TABLES ? lds_ld(LDS_OFF_TABA + (ia << 2)) : a.t.tabA[ia])
+		       ^ (LDS_TABLES ? lds_ld(LDS_OFF_TABB + (ib << 2)) : a.t.tabB[ib]) ^ (cls ? a.t.kdiff : 0u);
+	}
+	uint32_t s_hi;
+	if constexpr (TWO) {
+		const uint32_t l0 = (uint32_t)low, l1 = (uint32_t)(low >> 32);
+		const uint32_t f0 = (l0 & (uint32_t)a.t.hi_mask[0]) ^ (l1 & (uint32_t)(a.t.hi_mask[0] >> 32));
+		const uint32_t f1 = (l0 & (uint32_t)a.t.hi_mask[1]) ^ (l1 & (uint32_t)(a.t.hi_mask[1] >> 32));
+		s_hi = ((uint32_t)(a.t.kclass[cls] >> 32) ^ (__popc(f0) & 1) ^ ((__popc(f1) & 1) << 1)) & 3;
+	} else {
+		s_hi = ((uint32_t)(a.t.kclass[cls] >> 32) ^ (__popcll(low & a.t.hi_mask[0]) & 1)
+			^ ((__popcll(low & a.t.hi_mask[1]) & 1) << 1)) & 3;
+	}
 	const uint64_t syn = ((uint64_t)s_hi << 32) | s_lo;
-	if (a.t.bitmap2) {
+	if (!TWO && a.t.bitmap2) {
 		const uint32_t i2 = (s_lo * 0x9E3779B1u) >> a.t.bitmap2_shift;
 		if (!((a.t.bitmap2[i2 >> 5] >> (i2 & 31)) & 1))
 			return false;
@@ -184,6 +220,14 @@ __device__ __forceinline__ bool verify_lap_any(const ScanArgs &a, uint64_t w, ui
 			if (slot == HSLOT_EMPTY)
 				return false;                         // no pattern -> ac_errors = 0xff -> reject
 			if ((slot & 0x3ffffffffULL) == syn) {
+				if constexpr (TWO) {
+					// a stored pattern has a first position (0 .. 57) and a second one or 63; bit 63 of the window is a barker bit
+					// that the LAP below does not read, so "no second error" needs no select, only the count does
+					const uint32_t p0 = (uint32_t)(slot >> 34) & 63, p1 = (uint32_t)(slot >> 40) & 63;
+					sw ^= (1ULL << p0) | (1ULL << p1);
+					nerr = p1 != 63 ? 2u : 1u;
+					break;
+				}
 				uint64_t err = 0;
 #pragma unroll
 				for (int i = 0; i < 5; i++) {

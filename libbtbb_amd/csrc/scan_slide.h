@@ -10,8 +10,8 @@
 // halves of the lane's words, then the lock-step survivor loop -- eight vector instructions and ONE read of the
 // 2^SLIDE_BITS-bit candidate set in LDS per survivor (chains as shift registers, round 5).  A candidate goes straight to
 // the wave's ring in LDS (the membership compare's lane mask + mbcnt, no atomics; the one-level form notes it in a register and appends a trip's notes at once, round 7); the exact reference rule (verify_lap_any, syndrome tables read
-// through L2) runs on ring batches of up to 64.  The ring is the only LDS besides the set, so TWO workgroups
-// fit a CU: 2 x 768 threads = 6 waves per SIMD at <= 80 VGPRs (76 KiB of LDS each; a wave owns 63 words of a tile of 756).  Measured on one box,
+// through L2; the one-level form's syndrome tables in LDS, round 8) runs on ring batches of up to 64.  The ring and those 2.5 KiB are the only LDS besides the set, so TWO workgroups
+// fit a CU: 2 x 768 threads = 6 waves per SIMD at <= 80 VGPRs (78.5 KiB of LDS each; a wave owns 63 words of a tile of 756).  Measured on one box,
 // 4 GiB, ms per launch (profiles/r03_ab/): one 1024-thread workgroup per CU (4 waves per SIMD) 4.12, 2 x 1024
 // (8 waves, 64 VGPRs, spills outside the loop) 3.82-3.90, 2 x 768 3.59, 2 x 896 / 832 / 704 / 640 (waves that do
 // not divide evenly over the four SIMDs) 4.4-5.6; the 2^20-bit set (128 KiB, one workgroup per CU only) 3.81.
@@ -45,6 +45,19 @@
 //   compare per chain seen: -1.1 %; 9 + a compare: -1.9 %; 6 and no compare: -2.8 %); four lane masks instead of two cost ten
 //   v_readlane of spilled scalars per trip and were not timed.  v_add_co_u32 (m - 1 with "m was not zero" as its carry) issues at the
 //   slow rate, 4.3 cycles against 2.6 for v_add_u32: the sparse tail keeps its compares.
+// Round 8 (profiles/r08_drain): what is behind a trip's notes, taken apart by timing-only builds of the parent (2.629 ms, its three
+//   runs 0.5 % apart): no drain at all -4.8 %; drains without the hit queue -0.55 %; no drain and an append that only moves the tail
+//   another -4.2 % (it also frees the raw dwords and the notes' masks); a drain without its pattern look-up -2.5 %, without
+//   its syndrome tables as well -1.3 % more.  Skipping a lane's second candidate, and the round-5 "no filter" build, both came out
+//   SLOWER than the parent (+6 %, +4.5 %): they measure another register allocation, not the work left out.  Built: the exact rule in
+//   a form for tables of two errors or fewer (verify_lap_any<.., TWO>: no second-level bitmap, two error positions per slot, one
+//   v_bcnt per high syndrome bit) with its syndrome tables in LDS as three small ones (SYN3, 2.5 KiB in the 4 KiB two workgroups leave
+//   of a CU) -- a drain is 110 vector instructions for 136, ten fewer scalar registers spilled (16 for 26) and none of the six v_readlane of spilled scalars left in a drain's
+//   exact rule: 1 510.6 -> 1 498.0 M vector instructions per launch, 2.6245 -> 2.5984 ms (-1.0 %, every one of six pairs, three times the
+//   parent's spread of 0.32 %; on a noisier box -1.4 % inside a spread of 1.6 %).  Not built: the second note (no ceiling could be
+//   measured, the count says <= 0.8 %), the hit queue (0.55 % is its whole cost), the append ranked once per two trips (the first
+//   trip's raw dwords would have to live through the second).  Probing two slots per round trip, and pattern tables of a quarter
+//   to sixteen times the slots, changed nothing: the look-up's 2.5 % is one dependent round trip to the L2 per drain and the loop around it.
 // The kernel's two cuts.
 // SlideStd: tables for <= 2 errors (0.3 % of the survivors are members of the set).  Two workgroups per CU around a 2^19-bit set; six
 //   passes run blind, a candidate the ring has no room for is checked in place.
@@ -60,11 +73,13 @@ struct SlideStd {
 	static constexpr int BITS = SLIDE_BITS, THREADS = SLIDE_THREADS, WGS = SLIDE_WGS;
 	static constexpr uint64_t TAPS = SLIDE_TAPS, TAPS_B = 0;
 	static constexpr bool LEVEL2 = false, INVERT = false, DENSE = false;
+	static constexpr bool TWO_ERRORS = true;   // its tables hold patterns of <= 2 errors (scan.hip launches it with no others): verify_lap_any's lighter form
 };
 struct Slide4 {
 	static constexpr int BITS = SLIDE4_BITS, THREADS = 1024, WGS = 1;
 	static constexpr uint64_t TAPS = SLIDE4_TAPS, TAPS_B = SLIDE4B_TAPS;
 	static constexpr bool LEVEL2 = true, INVERT = true, DENSE = true;
+	static constexpr bool TWO_ERRORS = false;
 };
 template <class CFG> struct SlideGeom {
 	static constexpr uint32_t SET_WORDS = 1u << (CFG::BITS - 5), SET_BYTES = 4u * SET_WORDS;
@@ -77,10 +92,12 @@ template <class CFG> struct SlideGeom {
 	static constexpr uint32_t LANE_WORDS = 63;                              // words of a tile a wave owns (see the kernel)
 	static constexpr uint32_t TILE_WORDS = CFG::THREADS / 64 * LANE_WORDS;
 	static constexpr uint32_t RING_END = SET_BYTES + CAND_BYTES * (CFG::THREADS / 64) * RING;
+	static constexpr uint32_t SYN3_OFF = RING_END;                          // (one-level form) the exact rule's syndrome tables, scan_core.h SYN3
+	static constexpr uint32_t PROF_OFF = SYN3_OFF + (CFG::TWO_ERRORS ? SYN3_BYTES : 0u);
 #ifdef SCAN_PROFILE
-	static constexpr uint32_t LDS_BYTES = RING_END + 128u * (CFG::THREADS / 64);     // 32 phase counters per wave
+	static constexpr uint32_t LDS_BYTES = PROF_OFF + 128u * (CFG::THREADS / 64);     // 32 phase counters per wave
 #else
-	static constexpr uint32_t LDS_BYTES = RING_END;
+	static constexpr uint32_t LDS_BYTES = PROF_OFF;
 #endif
 	static_assert((uint64_t)LDS_BYTES * CFG::WGS <= 160u * 1024u, "the workgroups a CU is cut for must fit its 160 KiB of LDS");
 };
@@ -134,12 +151,19 @@ void scan_slide_kernel(ScanArgs a)
 			dst[i] = make_uint4(rev16(v.x), rev16(v.y), rev16(v.z), rev16(v.w));
 		}
 	}
+	constexpr uint32_t SYN3_OFF = SlideGeom<CFG>::SYN3_OFF;
+	if constexpr (CFG::TWO_ERRORS) {
+		// the exact rule's syndrome tables, in the 4 KiB two workgroups of this cut leave of a CU's LDS: a drain then waits for
+		// one round trip to the L2 (the pattern table), not two
+		for (uint32_t i = tid; i < SYN3_WORDS; i += THREADS)
+			lds_st(SYN3_OFF + 4u * i, syn3_entry(a.t, i));
+	}
 	__syncthreads();
 
 #ifdef SCAN_PROFILE
 	// phases: 0 = tile loads + barker filter + check stream, 1 .. 13 = survivor pass k, 16 = loop exit, 18 = ring drain,
 	// 19 = hand-over to the next trip
-	const uint32_t prof_off = SlideGeom<CFG>::RING_END + 128u * wave;
+	const uint32_t prof_off = SlideGeom<CFG>::PROF_OFF + 128u * wave;
 	if (lane < 32)
 		lds_st(prof_off + 4u * lane, 0u);
 	uint64_t prof_t;
@@ -163,7 +187,7 @@ void scan_slide_kernel(ScanArgs a)
 		if (lane < n) {
 			const uint64_t w = ((uint64_t)alignbit(rec.w, rec.z, code) << 32) | alignbit(rec.z, rec.y, code);   // (shift = the low five bits)
 			offset = word * 64 + (code & 63);
-			hit = verify_lap_any<false>(a, w, lap, nerr);
+			hit = verify_lap_any<false, CFG::TWO_ERRORS>(a, w, lap, nerr, SYN3_OFF);
 		}
 		if constexpr (ORD) {
 			// A drain takes whole trips, so every hit of a segment (tile iteration code >> 12 of this wave) is in this batch: its
@@ -412,7 +436,7 @@ void scan_slide_kernel(ScanArgs a)
 						asm volatile("" : "+v"(cold));      // keeps the tile -> stream division of this cold path out of every trip
 						const uint64_t word = code_word(cold, stream);
 						const uint32_t wlo = alignbit(rec.z, rec.y, pos), whi = alignbit(rec.w, rec.z, pos);
-						if (verify_lap_any<false>(a, ((uint64_t)whi << 32) | wlo, lap, nerr)) {
+						if (verify_lap_any<false, CFG::TWO_ERRORS>(a, ((uint64_t)whi << 32) | wlo, lap, nerr, SYN3_OFF)) {
 							if constexpr (ORD)
 								*a.irregular = 1u;          // a hit outside the drains: its segment cannot be ranked here
 							else
@@ -507,7 +531,7 @@ void scan_slide_kernel(ScanArgs a)
 						asm volatile("" : "+v"(cold));
 						const uint64_t word = code_word(cold, stream);
 						const uint32_t wlo = alignbit(z, y, cold), whi = alignbit(w, z, cold);      // (shift = the low five bits)
-						if (verify_lap_any<false>(a, ((uint64_t)whi << 32) | wlo, lap, nerr)) {
+						if (verify_lap_any<false, CFG::TWO_ERRORS>(a, ((uint64_t)whi << 32) | wlo, lap, nerr, SYN3_OFF)) {
 							if constexpr (ORD)
 								*a.irregular = 1u;
 							else
