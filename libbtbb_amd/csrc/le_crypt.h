@@ -6,25 +6,26 @@
 // The slot table is the data stage's (slot first + rank holds the member of that rank) and is built again from the same input, so
 // the stage reads nothing of the data stage's scratch.  The scans run on le_data.h's frame (ldt_tile, ldt_prefix, ldt_block_scan):
 //
-//   1. le_crypt_init_kernel, le_crypt_slot_kernel    the slot table; the whitening table; AES's round table, from the field's definition
+//   1. le_crypt_init_kernel, le_data_slot_kernel     the slot table; the whitening table; AES's round table, from the field's definition
 //   2. le_crypt_find_kernel, _rsp_, _begin_          rule 2: a slot's packed state, the procedure PDUs; REQ, RSP above it, START above that
 //   3. le_crypt_sched_kernel                         rule 3: per (connection, key) the session key and its schedule
 //   4. le_crypt_ord_*    (sum, prefix, apply)        rule 4: a member's state, its ordinal per (connection, role), the four probes
 //   5. le_crypt_probe_kernel, le_crypt_key_kernel    rule 6: one lane per (probe, key), the skews in turn; the connection's key
 //   6. le_crypt_first_kernel, le_crypt_retry_kernel  rule 7: skew 0 for every member; (member, skew >= 1) for those still unverified
 //   7. le_crypt_effect_kernel                        rule 8: the effective length and kind, a VERIFIED member's first four octets
-//   8. le_crypt_msg_*, le_crypt_close_kernel, le_crypt_number_*   the data stage's rules 5 and 6 over the effective members
+//   8. le_data_msg_*, le_data_close_kernel, le_crypt_number_*     the data stage's rules 5 and 6 over the effective members: its own
+//                                                     kernels where the rule reads nothing of this stage's, launched with the frame's part of the arguments
 //   9. le_crypt_pkt_kernel, le_crypt_conn_kernel     the records
 //  10. le_crypt_plain_kernel                         one lane per 16 octets of a fragment: keystream, plaintext to its place in d_bytes
 //
 // 24 launches, whatever the counts, caps, keys and window.  Nothing here synchronises or reads back but the host wrapper.
 #pragma once
 #include "le_data.h"
+#include "le_aes.h"
 
 #define LX_NONE      0xffffffffu
 #define LX_MAX_KEYS  64u
 #define LX_MAX_SKEW  32u
-#define LX_RK        44u                   // words of an AES-128 key schedule
 #define LX_GRID      (1u << 20)            // workgroups of a grid-stride launch, at most
 // base[q]: sinfo's fields (length | (header0 & 0x1f) << 8 | role << 14 | kind << 17 | phase << 24) and the procedure class << 21
 #define LX_CLASS(x)  (((x) >> 21) & 3u)    // 1 ENC_REQ, 2 ENC_RSP, 3 START_ENC_REQ
@@ -86,84 +87,6 @@ static LxLayout le_crypt_layout(uint32_t cand_cap, uint32_t conn_cap, uint32_t n
 
 __device__ __forceinline__ const LxArgs &lx_args(const LdtArgs &a) { return static_cast<const LxArgs &>(a); }
 
-// ---- AES-128: one round table in LDS, te[x] = 2s | s << 8 | s << 16 | 3s << 24 with s = S(x); a block is four little-endian words ----
-
-__device__ __forceinline__ uint32_t lx_rotl(uint32_t v, uint32_t s) { return (v << s) | (v >> (32u - s)); }
-
-__device__ __forceinline__ uint32_t lx_gmul(uint32_t x, uint32_t y)
-{
-	uint32_t r = 0;
-	for (int j = 0; j < 8; j++) {
-		if (y & 1u)
-			r ^= x;
-		x = (x << 1) ^ ((x & 0x80u) ? 0x11bu : 0u);
-		y >>= 1;
-	}
-	return r;
-}
-
-// the S-box from its definition: the inverse in GF(2^8) modulo x^8 + x^4 + x^3 + x + 1, then the affine map
-__device__ __forceinline__ uint32_t lx_te_entry(uint32_t x)
-{
-	uint32_t inv = 0;
-	for (uint32_t y = 1; y < 256; y++)
-		if (lx_gmul(x, y) == 1u)
-			inv = y;
-	const uint32_t w = inv | (inv << 8);
-	const uint32_t s = (inv ^ (w >> 7) ^ (w >> 6) ^ (w >> 5) ^ (w >> 4) ^ 0x63u) & 0xffu;
-	const uint32_t s2 = lx_gmul(s, 2);
-	return s2 | (s << 8) | (s << 16) | ((s2 ^ s) << 24);
-}
-
-__device__ __forceinline__ uint32_t lx_sub(const uint32_t *te, uint32_t x) { return (te[x] >> 8) & 0xffu; }
-
-__device__ __forceinline__ uint32_t lx_sub_word(const uint32_t *te, uint32_t w)
-{
-	return lx_sub(te, w & 0xffu) | (lx_sub(te, (w >> 8) & 0xffu) << 8) | (lx_sub(te, (w >> 16) & 0xffu) << 16) | (lx_sub(te, w >> 24) << 24);
-}
-
-// rk[0..3] = the key -> the schedule
-__device__ __forceinline__ void lx_expand(const uint32_t *te, uint32_t (&rk)[LX_RK])
-{
-	uint32_t rc = 1;
-#pragma unroll
-	for (int i = 4; i < (int)LX_RK; i++) {
-		uint32_t t = rk[i - 1];
-		if ((i & 3) == 0) {
-			t = lx_sub_word(te, (t >> 8) | (t << 24)) ^ rc;
-			rc = ((rc << 1) ^ ((rc & 0x80u) ? 0x11bu : 0u)) & 0xffu;
-		}
-		rk[i] = rk[i - 4] ^ t;
-	}
-}
-
-struct LxBlock { uint32_t w[4]; };
-
-__device__ __forceinline__ uint32_t lx_col(const uint32_t *te, uint32_t a, uint32_t b, uint32_t c, uint32_t d)
-{
-	return te[a & 0xffu] ^ lx_rotl(te[(b >> 8) & 0xffu], 8) ^ lx_rotl(te[(c >> 16) & 0xffu], 16) ^ lx_rotl(te[d >> 24], 24);
-}
-
-__device__ __forceinline__ LxBlock lx_aes(const uint32_t *te, const uint32_t (&rk)[LX_RK], const LxBlock &in)
-{
-	uint32_t s0 = in.w[0] ^ rk[0], s1 = in.w[1] ^ rk[1], s2 = in.w[2] ^ rk[2], s3 = in.w[3] ^ rk[3];
-#pragma unroll
-	for (int r = 1; r < 10; r++) {
-		const uint32_t t0 = lx_col(te, s0, s1, s2, s3) ^ rk[4 * r], t1 = lx_col(te, s1, s2, s3, s0) ^ rk[4 * r + 1];
-		const uint32_t t2 = lx_col(te, s2, s3, s0, s1) ^ rk[4 * r + 2], t3 = lx_col(te, s3, s0, s1, s2) ^ rk[4 * r + 3];
-		s0 = t0;
-		s1 = t1;
-		s2 = t2;
-		s3 = t3;
-	}
-	LxBlock o;
-	o.w[0] = (lx_sub(te, s0 & 0xffu) | (lx_sub(te, (s1 >> 8) & 0xffu) << 8) | (lx_sub(te, (s2 >> 16) & 0xffu) << 16) | (lx_sub(te, s3 >> 24) << 24)) ^ rk[40];
-	o.w[1] = (lx_sub(te, s1 & 0xffu) | (lx_sub(te, (s2 >> 8) & 0xffu) << 8) | (lx_sub(te, (s3 >> 16) & 0xffu) << 16) | (lx_sub(te, s0 >> 24) << 24)) ^ rk[41];
-	o.w[2] = (lx_sub(te, s2 & 0xffu) | (lx_sub(te, (s3 >> 8) & 0xffu) << 8) | (lx_sub(te, (s0 >> 16) & 0xffu) << 16) | (lx_sub(te, s1 >> 24) << 24)) ^ rk[42];
-	o.w[3] = (lx_sub(te, s3 & 0xffu) | (lx_sub(te, (s0 >> 8) & 0xffu) << 8) | (lx_sub(te, (s1 >> 16) & 0xffu) << 16) | (lx_sub(te, s2 >> 24) << 24)) ^ rk[43];
-	return o;
-}
-
 // the tables of a workgroup: te and the data stage's whitening table.  Every thread of the workgroup calls it, before any return
 __device__ __forceinline__ void lx_tables(const LxArgs &a, uint32_t *te, unsigned long long *wt)
 {
@@ -173,36 +96,7 @@ __device__ __forceinline__ void lx_tables(const LxArgs &a, uint32_t *te, unsigne
 	__syncthreads();
 }
 
-// ---- a member's payload --------------------------------------------------------------------------------------------------------
-
-// where the payload of the member in slot q begins, and the whitening phase there (rule 6 of the data stage)
-struct LxWhere {
-	const uint64_t *w;
-	uint64_t bit0;
-	uint32_t phase, h0;
-	bool in_range;
-};
-
-__device__ __forceinline__ LxWhere lx_where(const LxArgs &a, uint32_t q, uint32_t x)
-{
-	LxWhere p;
-	const uint32_t i = a.slot[q];
-	const uint2 where = reinterpret_cast<const uint2 *>(a.cands + i)[0];
-	const uint32_t c = reinterpret_cast<const uint2 *>(a.cands + i)[2].x, stream = c & 0xffffu;
-	p.in_range = stream < a.n_streams;
-	p.w = a.words + (p.in_range ? (uint64_t)stream * a.pitch_words : 0);
-	p.bit0 = ((((uint64_t)where.y << 32) | where.x) & LT_OFF_MASK) + 56;
-	p.phase = (x >> 24) + 16u;
-	p.h0 = (c >> 16) & 0xffu;
-	return p;
-}
-
-// payload octets k .. k + 7, dewhitened; zeros beyond the stream's end
-__device__ __forceinline__ unsigned long long lx_octets(const LxArgs &a, const LxWhere &p, const unsigned long long *wt, uint32_t k)
-{
-	const unsigned long long v = p.in_range ? ldt_read64(p.w, a.n_words, p.bit0 + 8ull * k) : 0;
-	return v ^ wt[(p.phase + 8u * k) % 127u];
-}
+// ---- rule 5: a trial (a member's payload is read by the data stage's ldt_where and ldt_octets) --------------------------------------
 
 // A_i (flags 0x01) or B0 (flags 0x49) of rule 5: flags | nonce | BE16(last)
 __device__ __forceinline__ LxBlock lx_nonce_block(uint32_t flags, unsigned long long c, uint32_t dir, uint32_t ivm, uint32_t ivs, uint32_t last)
@@ -216,23 +110,11 @@ __device__ __forceinline__ LxBlock lx_nonce_block(uint32_t flags, unsigned long 
 	return b;
 }
 
-__device__ __forceinline__ void lx_load_rk(const uint32_t *sched, uint32_t (&rk)[LX_RK])
-{
-#pragma unroll
-	for (int j = 0; j < (int)LX_RK / 4; j++) {
-		const uint4 v = reinterpret_cast<const uint4 *>(sched)[j];
-		rk[4 * j] = v.x;
-		rk[4 * j + 1] = v.y;
-		rk[4 * j + 2] = v.z;
-		rk[4 * j + 3] = v.w;
-	}
-}
-
 // Rule 5: does the member in slot q (L >= 5) verify under the schedule rk with counter c?
 __device__ __forceinline__ bool lx_trial(const LxArgs &a, const uint32_t *te, const unsigned long long *wt, const uint32_t (&rk)[LX_RK], uint32_t q,
 					 uint32_t x, uint32_t g, unsigned long long c)
 {
-	const LxWhere p = lx_where(a, q, x);
+	const LdtWhere p = ldt_where(a, q, x);
 	const uint32_t m = (x & 0xffu) - 4u, dir = LDT_ROLE(x) == BTBBX_LE_ROLE_CENTRAL ? 1u : 0u;
 	const uint32_t ivm = a.civ[2 * (size_t)g], ivs = a.civ[2 * (size_t)g + 1];
 	const LxBlock s0 = lx_aes(te, rk, lx_nonce_block(0x01u, c, dir, ivm, ivs, 0));
@@ -242,8 +124,8 @@ __device__ __forceinline__ bool lx_trial(const LxArgs &a, const uint32_t *te, co
 #pragma unroll 1
 	for (uint32_t k = 0; k < m; k += 16) {
 		const LxBlock s = lx_aes(te, rk, lx_nonce_block(0x01u, c, dir, ivm, ivs, k / 16 + 1));
-		unsigned long long lo = lx_octets(a, p, wt, k) ^ (((unsigned long long)s.w[1] << 32) | s.w[0]);
-		unsigned long long hi = lx_octets(a, p, wt, k + 8) ^ (((unsigned long long)s.w[3] << 32) | s.w[2]);
+		unsigned long long lo = ldt_octets(a, p, wt, k) ^ (((unsigned long long)s.w[1] << 32) | s.w[0]);
+		unsigned long long hi = ldt_octets(a, p, wt, k + 8) ^ (((unsigned long long)s.w[3] << 32) | s.w[2]);
 		const uint32_t rem = m - k;                             // the last block is padded with zeros
 		if (rem < 8)
 			lo &= (1ull << (8 * rem)) - 1;
@@ -257,66 +139,30 @@ __device__ __forceinline__ bool lx_trial(const LxArgs &a, const uint32_t *te, co
 		xb.w[3] ^= (uint32_t)(hi >> 32);
 		xb = lx_aes(te, rk, xb);
 	}
-	return (xb.w[0] ^ s0.w[0]) == (uint32_t)lx_octets(a, p, wt, m);
+	return (xb.w[0] ^ s0.w[0]) == (uint32_t)ldt_octets(a, p, wt, m);
 }
 
 // ---- 1. slots, tables ------------------------------------------------------------------------------------------------------------
 
 extern "C" __global__ __launch_bounds__(LE_THREADS) void le_crypt_init_kernel(LxArgs a)
 {
-	const uint32_t nh = *a.d_cand_count, kh = *a.d_conn_count;
-	const uint32_t n = nh < a.cand_cap ? nh : a.cand_cap, k = kh < a.conn_cap ? kh : a.conn_cap;
-	const uint64_t i = (uint64_t)blockIdx.x * LE_THREADS + threadIdx.x;   // (the grid covers the larger of the two caps)
-	if (i == 0) {
-		a.params[0] = n;
-		a.params[1] = k;
-		a.wphase[0] = 0;
-		a.counts[0] = 0;
-	}
-	if (i < n)
-		a.slot[i] = LX_NONE;
-	if (i < k) {
-		uint4 *c = reinterpret_cast<uint4 *>(a.cend + i * 8), *t = reinterpret_cast<uint4 *>(a.ctal + i * 8);
-		c[0] = c[1] = t[0] = t[1] = make_uint4(0, 0, 0, 0);
+	const uint64_t i = (uint64_t)blockIdx.x * LE_THREADS + threadIdx.x;
+	ldt_init_frame(a, i, [=] {
+		uint4 *t = reinterpret_cast<uint4 *>(a.ctal + i * 8);
+		t[0] = t[1] = make_uint4(0, 0, 0, 0);
 		reinterpret_cast<uint4 *>(a.proc)[i] = reinterpret_cast<uint4 *>(a.probe)[i] = make_uint4(LX_NONE, LX_NONE, LX_NONE, LX_NONE);
 		a.ckey[i] = 0xffu;
 		a.civ[2 * i] = a.civ[2 * i + 1] = 0;
 		for (uint32_t j = 0; j < a.n_keys; j++)
 			a.score[i * a.n_keys + j] = 0;
-	}
+	});
+	if (i == 0)
+		a.counts[0] = 0;
 	if (blockIdx.x == 0) {
 		a.te[threadIdx.x] = lx_te_entry(threadIdx.x);
-		if (threadIdx.x < 127) {                                // (le_data_init_kernel's table)
-			uint32_t s = 0x40u;
-			for (uint32_t j = 0; j < threadIdx.x; j++) {
-				if (s & 1u)
-					s ^= 0x88u;
-				s >>= 1;
-			}
-			a.wphase[s] = threadIdx.x;
-			unsigned long long o = 0;
-			for (uint32_t j = 0; j < 64; j++) {
-				o |= (unsigned long long)(s & 1u) << j;
-				if (s & 1u)
-					s ^= 0x88u;
-				s >>= 1;
-			}
-			a.wtab[threadIdx.x] = o;
-		}
+		if (threadIdx.x < 127)
+			ldt_init_whitening(a, threadIdx.x);
 	}
-}
-
-extern "C" __global__ __launch_bounds__(LE_THREADS) void le_crypt_slot_kernel(LxArgs a)
-{
-	const uint64_t at = (uint64_t)blockIdx.x * LE_THREADS + threadIdx.x;
-	const uint32_t n = a.params[0], k = a.params[1];
-	if (at >= n)
-		return;
-	const uint32_t i = (uint32_t)at;
-	uint32_t g, first;
-	uint4 p;
-	if (lf_member(a.cands, a.pkts, a.conns, i, n, k, g, p, first))
-		a.slot[first + p.x] = i;
 }
 
 // ---- 2. rules 1 and 2: COUNTING members, the procedure PDUs ----------------------------------------------------------------------------
@@ -345,8 +191,8 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_crypt_find_kernel(Lx
 	const uint32_t len = c.x >> 24, llid = (c.x >> 16) & 3u;
 	uint32_t x = len | (((c.x >> 16) & 0x1fu) << 8) | (role << 14) | (kind << 17) | (a.wphase[0x40u | ch] << 24);
 	if (lx_counting(x) && llid == 3 && len >= 1) {
-		const LxWhere p = lx_where(a, q, x);
-		const uint32_t op = (uint32_t)lx_octets(a, p, a.wtab, 0) & 0xffu;
+		const LdtWhere p = ldt_where(a, q, x);
+		const uint32_t op = (uint32_t)ldt_octets(a, p, a.wtab, 0) & 0xffu;
 		uint32_t cls = 0;
 		if (role == BTBBX_LE_ROLE_CENTRAL && len == 23 && op == 0x03u)
 			cls = 1;
@@ -385,8 +231,6 @@ __device__ __forceinline__ bool lx_armed(const LxArgs &a, uint32_t g) { return a
 
 // ---- 3. rule 3: the session keys -----------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ uint32_t lx_bswap(uint32_t v) { return __builtin_bswap32(v); }
-
 // one lane per (ARMED connection, key): SK = AES(key, the reversed SKD); its schedule
 extern "C" __global__ __launch_bounds__(LE_THREADS) void le_crypt_sched_kernel(LxArgs a)
 {
@@ -399,8 +243,8 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_crypt_sched_kernel(L
 		if (!lx_armed(a, g))
 			continue;
 		const uint32_t q_req = a.proc[4 * (size_t)g], q_rsp = a.proc[4 * (size_t)g + 1];
-		const LxWhere req = lx_where(a, q_req, a.base[q_req]), rsp = lx_where(a, q_rsp, a.base[q_rsp]);
-		const unsigned long long skdm = lx_octets(a, req, wt, 11), skds = lx_octets(a, rsp, wt, 1);
+		const LdtWhere req = ldt_where(a, q_req, a.base[q_req]), rsp = ldt_where(a, q_rsp, a.base[q_rsp]);
+		const unsigned long long skdm = ldt_octets(a, req, wt, 11), skds = ldt_octets(a, rsp, wt, 1);
 		uint32_t rk[LX_RK];
 #pragma unroll
 		for (int w = 0; w < 4; w++) {
@@ -423,8 +267,8 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_crypt_sched_kernel(L
 		for (int j = 0; j < (int)LX_RK / 4; j++)
 			o[j] = make_uint4(rk[4 * j], rk[4 * j + 1], rk[4 * j + 2], rk[4 * j + 3]);
 		if (kk == 0) {
-			a.civ[2 * (size_t)g] = (uint32_t)lx_octets(a, req, wt, 19);
-			a.civ[2 * (size_t)g + 1] = (uint32_t)lx_octets(a, rsp, wt, 9);
+			a.civ[2 * (size_t)g] = (uint32_t)ldt_octets(a, req, wt, 19);
+			a.civ[2 * (size_t)g + 1] = (uint32_t)ldt_octets(a, rsp, wt, 9);
 		}
 	}
 }
@@ -605,7 +449,7 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_crypt_effect_kernel(
 		lx_load_rk(a.sched + ((size_t)g * a.n_keys + a.ckey[g]) * LX_RK, rk);
 		const LxBlock s = lx_aes(te, rk, lx_nonce_block(0x01u, (unsigned long long)a.ord[q] + skew, role == BTBBX_LE_ROLE_CENTRAL ? 1u : 0u,
 								 a.civ[2 * (size_t)g], a.civ[2 * (size_t)g + 1], 1));
-		const uint32_t plain = (uint32_t)lx_octets(a, lx_where(a, q, x), wt, 0) ^ s.w[0];
+		const uint32_t plain = (uint32_t)ldt_octets(a, ldt_where(a, q, x), wt, 0) ^ s.w[0];
 		a.hdr4[q] = plain;
 		if (llid == 3)
 			opcode = plain & 0xffu;
@@ -622,39 +466,8 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_crypt_effect_kernel(
 
 // ---- 8. the data stage's rules 5 and 6 over the effective members -------------------------------------------------------------------
 
-// (LdtMsg reads sg and sinfo and nothing of the streams: over this stage's sinfo it is rule 8 as it stands)
-extern "C" __global__ __launch_bounds__(LE_THREADS) void le_crypt_msg_sum_kernel(LxArgs a) { ldt_tile<LdtMsg, false>(a); }
-extern "C" __global__ __launch_bounds__(LE_THREADS) void le_crypt_msg_prefix_kernel(LxArgs a) { ldt_prefix<LdtMsg>(a); }
-extern "C" __global__ __launch_bounds__(LE_THREADS) void le_crypt_msg_kernel(LxArgs a) { ldt_tile<LdtMsg, true>(a); }
-
-// (le_data_close_kernel over this stage's arrays)
-extern "C" __global__ __launch_bounds__(LE_THREADS) void le_crypt_close_kernel(LxArgs a)
-{
-	const uint64_t at = (uint64_t)blockIdx.x * LE_THREADS + threadIdx.x;
-	const uint32_t n = a.params[0], q = (uint32_t)at;
-	if (at >= n)
-		return;
-	const uint32_t g = a.sg[q];
-	if (g == LX_NONE)
-		return;
-	const uint32_t x = a.sinfo[q];
-	if (LDT_KIND(x) == BTBBX_LE_DATA_START && LDT_ROLE(x) < 2) {
-		const uint32_t from = a.ps[q];
-		if (from != LX_NONE) {
-			a.mbytes[from] = a.sx[q] - a.sx[from];
-			a.mfrag[from] = a.cx[q] - a.cx[from];
-		}
-	}
-	if (ldt_last(a.sg, q, n, g)) {
-		const uint32_t *e = a.cend + (size_t)g * 8;
-		for (uint32_t r = 0; r < 2; r++)
-			if (e[0] & (2u << r)) {
-				const uint32_t from = e[1 + r];
-				a.mbytes[from] = e[3 + r] - a.sx[from];
-				a.mfrag[from] = e[5 + r] - a.cx[from];
-			}
-	}
-}
+// (LdtMsg and le_data_close_kernel read sg and sinfo and nothing of the streams: over this stage's sinfo they are rule 8 as it stands,
+// and le_crypt_launch launches the data stage's kernels)
 
 // LdtNumber without the data records' tallies; the L2CAP header of a VERIFIED START is its stashed plaintext
 struct LxNumber {
@@ -670,41 +483,14 @@ struct LxNumber {
 		a.gdst[q] = ~0ULL;                                      // (le_crypt_pkt_kernel sets it for a stored message's fragment)
 		if (sl.g == LX_NONE || LDT_KIND(sl.x) != BTBBX_LE_DATA_START || LDT_ROLE(sl.x) >= 2)
 			return;
-		const uint32_t m = ex.w[0], bytes = sl.y, len = sl.x & 0xffu, i = a.slot[q];
-		const unsigned long long off = ((unsigned long long)ex.w[2] << 32) | ex.w[1];
-		uint32_t flags = BTBBX_LE_MSG_RUNT, hdr = 0xffffffffu;
-		if (len >= 4) {
-			hdr = (a.cst[q] & 0xffu) == BTBBX_LE_CRYPT_VERIFIED ? a.hdr4[q] : (uint32_t)lx_octets(a, lx_where(a, q, sl.x), a.wtab, 0);
-			const unsigned long long whole = 4ull + (hdr & 0xffffu);
-			flags = bytes == whole ? BTBBX_LE_MSG_COMPLETE : (bytes > whole ? BTBBX_LE_MSG_OVERRUN : 0u);
-		}
-		if (m < a.msg_cap && off + bytes <= a.byte_cap) {
-			flags |= BTBBX_LE_MSG_STORED;
-			a.sinfo[q] = sl.x | LDT_STORED;
-		}
-		a.msgno[q] = m;
-		a.boff[q] = off;
-		if (m < a.msg_cap) {
-			uint2 *o = reinterpret_cast<uint2 *>(a.msgs + m);
-			o[0] = make_uint2((uint32_t)off, (uint32_t)(off >> 32));
-			o[1] = make_uint2(sl.g, i);
-			o[2] = make_uint2(a.mfrag[q], bytes);
-			o[3] = make_uint2(hdr, LDT_ROLE(sl.x) | (flags << 8));
-		}
+		ldt_start(a, q, sl, ex, (a.cst[q] & 0xffu) == BTBBX_LE_CRYPT_VERIFIED ? a.hdr4 + q : nullptr);
 	}
 };
 
 extern "C" __global__ __launch_bounds__(LE_THREADS) void le_crypt_number_sum_kernel(LxArgs a) { ldt_tile<LxNumber, false>(a); }
 extern "C" __global__ __launch_bounds__(LE_THREADS) void le_crypt_number_kernel(LxArgs a) { ldt_tile<LxNumber, true>(a); }
 
-extern "C" __global__ __launch_bounds__(LE_THREADS) void le_crypt_number_prefix_kernel(LxArgs a)
-{
-	const LdtState<3> all = ldt_prefix<LxNumber>(a);
-	if (threadIdx.x == 0) {
-		*a.msg_count = all.w[0];
-		*a.byte_count = ((unsigned long long)all.w[2] << 32) | all.w[1];
-	}
-}
+extern "C" __global__ __launch_bounds__(LE_THREADS) void le_crypt_number_prefix_kernel(LxArgs a) { ldt_totals(a); }
 
 // ---- 9. rule 9: the records ----------------------------------------------------------------------------------------------------------
 
@@ -714,28 +500,17 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_crypt_pkt_kernel(LxA
 	const uint32_t n = a.params[0], k = a.params[1], i = (uint32_t)at;
 	if (at >= n)
 		return;
-	uint32_t g, first, msg = LX_NONE, pos = 0, tail = 0xffffffffu;
+	uint32_t g, first;
 	uint4 p, rec = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
-	if (lf_member(a.cands, a.pkts, a.conns, i, n, k, g, p, first)) {
-		const uint32_t q = first + p.x, x = a.sinfo[q], kind = LDT_KIND(x), cs = a.cst[q], st = cs & 0xffu;
-		if (kind <= BTBBX_LE_DATA_CONTINUATION) {               // a fragment: its message; where le_crypt_plain_kernel puts it
-			const uint32_t from = kind == BTBBX_LE_DATA_START ? q : a.ps[q];
-			msg = a.msgno[from];
-			pos = a.sx[q] - a.sx[from];
-			if (a.sinfo[from] & LDT_STORED)
-				a.gdst[q] = a.boff[from] + pos;
-		}
-		tail = LDT_ROLE(x) | (kind << 8) | ((((x >> 11) & 1u) | (((x >> 10) & 1u) << 1) | (((x >> 12) & 1u) << 2)) << 16);
+	const bool member = lf_member(a.cands, a.pkts, a.conns, i, n, k, g, p, first);
+	const uint32_t q = first + p.x;
+	ldt_pkt(a, i, member, q);
+	if (member) {
+		const uint32_t cs = a.cst[q], st = cs & 0xffu;
 		const bool tried = st == BTBBX_LE_CRYPT_VERIFIED || st == BTBBX_LE_CRYPT_FAILED;
 		const unsigned long long c = tried ? (unsigned long long)a.ord[q] + (st == BTBBX_LE_CRYPT_VERIFIED ? (cs >> 8) & 0xffu : 0u) : 0ull;
 		rec = make_uint4((uint32_t)c, tried ? a.ord[q] : 0u, (cs & 0xffffffu) | (((uint32_t)(c >> 32) & 0x7fu) << 24), 0u);
-	} else {
-		pos = 0xffffffffu;
 	}
-	uint32_t *o = reinterpret_cast<uint32_t *>(a.dpkts + i);
-	o[0] = msg;
-	o[1] = pos;
-	o[2] = tail;
 	reinterpret_cast<uint4 *>(a.cpkts)[i] = rec;
 }
 
@@ -789,8 +564,8 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_crypt_plain_kernel(L
 	const uint32_t x = a.sinfo[q], len = x & 0xffu, cs = a.cst[q], g = a.sg[q];
 	if (k >= len)
 		return;
-	const LxWhere p = lx_where(a, q, x);
-	unsigned long long lo = lx_octets(a, p, wt, k), hi = lx_octets(a, p, wt, k + 8);
+	const LdtWhere p = ldt_where(a, q, x);
+	unsigned long long lo = ldt_octets(a, p, wt, k), hi = ldt_octets(a, p, wt, k + 8);
 	if ((cs & 0xffu) == BTBBX_LE_CRYPT_VERIFIED) {
 		uint32_t rk[LX_RK];
 		lx_load_rk(a.sched + ((size_t)g * a.n_keys + a.ckey[g]) * LX_RK, rk);
@@ -830,44 +605,9 @@ static int le_crypt_launch(const uint64_t *d_words, uint64_t n_words, uint64_t p
 	const LdtLayout &L = C.frame;
 	char *s = (char *)d_scratch;
 	LxArgs a;
-	a.words = d_words;
-	a.n_words = n_words;
-	a.pitch_words = n_streams > 1 ? pitch_words : n_words;
-	a.cands = d_cands;
-	a.pkts = d_pkts;
-	a.conns = d_conns;
-	a.d_cand_count = d_count;
-	a.d_conn_count = d_conn_count;
-	a.n_streams = n_streams;
-	a.cand_cap = cap;
-	a.conn_cap = conn_cap;
-	a.n_tiles = L.tiles_n;
-	a.msg_cap = msg_cap;
-	a.params = (uint32_t *)(s + L.params);
-	a.slot = (uint32_t *)(s + L.slot);
-	a.sg = (uint32_t *)(s + L.sg);
-	a.sinfo = (uint32_t *)(s + L.sinfo);
-	a.sx = (uint32_t *)(s + L.sx);
-	a.cx = (uint32_t *)(s + L.cx);
-	a.ps = (uint32_t *)(s + L.ps);
-	a.mbytes = (uint32_t *)(s + L.mbytes);
-	a.mfrag = (uint32_t *)(s + L.mfrag);
-	a.msgno = (uint32_t *)(s + L.msgno);
-	a.tiles = (uint32_t *)(s + L.tiles);
-	a.cend = (uint32_t *)(s + L.cend);
-	a.cnum = (uint32_t *)(s + L.cnum);
-	a.tally = (uint32_t *)(s + L.tally);
-	a.wphase = (uint32_t *)(s + L.wphase);
-	a.boff = (unsigned long long *)(s + L.boff);
-	a.gdst = (unsigned long long *)(s + L.gdst);
-	a.wtab = (unsigned long long *)(s + L.wtab);
-	a.data = nullptr;                                       // (the data records are the data stage's)
-	a.dpkts = d_plain_pkts;
-	a.msgs = d_msgs;
-	a.msg_count = d_msg_count;
-	a.bytes = d_bytes;
-	a.byte_cap = byte_cap;
-	a.byte_count = (unsigned long long *)d_byte_count;
+	// (the data records are the data stage's; dpkts: the records over plaintext)
+	static_cast<LdtArgs &>(a) = le_data_args(L, d_words, n_words, pitch_words, n_streams, d_cands, d_count, cap, d_conns, d_conn_count, conn_cap, d_pkts,
+						  nullptr, d_plain_pkts, d_msgs, msg_cap, d_msg_count, d_bytes, byte_cap, d_byte_count, d_scratch);
 	a.in_dpkts = d_data_pkts;
 	a.keys = d_keys;
 	a.n_keys = n_keys;
@@ -896,8 +636,9 @@ static int le_crypt_launch(const uint64_t *d_words, uint64_t n_words, uint64_t p
 	const dim3 init_grid((uint32_t)(((uint64_t)std::max(cap, conn_cap) + LE_THREADS - 1) / LE_THREADS));
 	const dim3 per_key(blocks((uint64_t)conn_cap * n_keys, LE_THREADS)), per_probe(blocks((uint64_t)conn_cap * 4 * n_keys, LE_THREADS));
 	const dim3 per_retry(blocks((uint64_t)cap * (window - 1) + 1, LE_THREADS));
+	const LdtArgs &frame = a;                               // what the data stage's kernels take
 	hipLaunchKernelGGL(le_crypt_init_kernel, init_grid, wg, 0, q, a);
-	hipLaunchKernelGGL(le_crypt_slot_kernel, per_cand, wg, 0, q, a);
+	hipLaunchKernelGGL(le_data_slot_kernel, per_cand, wg, 0, q, frame);
 	hipLaunchKernelGGL(le_crypt_find_kernel, per_cand, wg, 0, q, a);
 	hipLaunchKernelGGL(le_crypt_rsp_kernel, per_cand, wg, 0, q, a);
 	hipLaunchKernelGGL(le_crypt_begin_kernel, per_cand, wg, 0, q, a);
@@ -910,10 +651,10 @@ static int le_crypt_launch(const uint64_t *d_words, uint64_t n_words, uint64_t p
 	hipLaunchKernelGGL(le_crypt_first_kernel, per_cand, wg, 0, q, a);
 	hipLaunchKernelGGL(le_crypt_retry_kernel, per_retry, wg, 0, q, a);
 	hipLaunchKernelGGL(le_crypt_effect_kernel, per_cand, wg, 0, q, a);
-	hipLaunchKernelGGL(le_crypt_msg_sum_kernel, per_tile, wg, 0, q, a);
-	hipLaunchKernelGGL(le_crypt_msg_prefix_kernel, one, wg, 0, q, a);
-	hipLaunchKernelGGL(le_crypt_msg_kernel, per_tile, wg, 0, q, a);
-	hipLaunchKernelGGL(le_crypt_close_kernel, per_cand, wg, 0, q, a);
+	hipLaunchKernelGGL(le_data_msg_sum_kernel, per_tile, wg, 0, q, frame);
+	hipLaunchKernelGGL(le_data_msg_prefix_kernel, one, wg, 0, q, frame);
+	hipLaunchKernelGGL(le_data_msg_kernel, per_tile, wg, 0, q, frame);
+	hipLaunchKernelGGL(le_data_close_kernel, per_cand, wg, 0, q, frame);
 	hipLaunchKernelGGL(le_crypt_number_sum_kernel, per_tile, wg, 0, q, a);
 	hipLaunchKernelGGL(le_crypt_number_prefix_kernel, one, wg, 0, q, a);
 	hipLaunchKernelGGL(le_crypt_number_kernel, per_tile, wg, 0, q, a);
@@ -944,15 +685,9 @@ extern "C" int btbbx_le_crypt_device(const uint64_t *d_words, uint64_t n_words, 
 				     uint64_t *d_byte_count, void *d_scratch, size_t scratch_bytes, void *hip_stream)
 {
 	const char *who = "btbbx_le_crypt_device";
-	if (n_streams == 0) {
-		set_error("%s: n_streams must be >= 1", who);
-		return BTBBX_E_ARG;
-	}
-	if (n_words == 0 || (n_streams > 1 && pitch_words < n_words) || n_words > (1ull << 42)) {
-		set_error("%s: n_words must be 1 .. 2^42 and pitch_words >= n_words", who);
-		return BTBBX_E_ARG;
-	}
-	int rc = le_crypt_check_keys(who, n_keys, window);
+	int rc = le_check_streams(who, n_words, pitch_words, n_streams);
+	if (!rc)
+		rc = le_crypt_check_keys(who, n_keys, window);
 	if (rc)
 		return rc;
 	const LxLayout L = le_crypt_layout(cand_cap, conn_cap, n_keys);

@@ -233,15 +233,43 @@ __device__ __forceinline__ unsigned long long ldt_read64(const uint64_t *w, uint
 	return sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
 }
 
+// where the payload of the member in slot q begins, and the whitening phase there (x: the slot's sinfo)
+struct LdtWhere {
+	const uint64_t *w;
+	uint64_t bit0;
+	uint32_t phase, h0;
+	bool in_range;
+};
+
+__device__ __forceinline__ LdtWhere ldt_where(const LdtArgs &a, uint32_t q, uint32_t x)
+{
+	LdtWhere p;
+	const uint32_t i = a.slot[q];
+	const uint2 where = reinterpret_cast<const uint2 *>(a.cands + i)[0];
+	const uint32_t c = reinterpret_cast<const uint2 *>(a.cands + i)[2].x, stream = c & 0xffffu;
+	p.in_range = stream < a.n_streams;
+	p.w = a.words + (p.in_range ? (uint64_t)stream * a.pitch_words : 0);
+	p.bit0 = ((((uint64_t)where.y << 32) | where.x) & LT_OFF_MASK) + 56;
+	p.phase = (x >> 24) + 16u;
+	p.h0 = (c >> 16) & 0xffu;
+	return p;
+}
+
+// payload octets k .. k + 7, dewhitened; zeros beyond the stream's end
+__device__ __forceinline__ unsigned long long ldt_octets(const LdtArgs &a, const LdtWhere &p, const unsigned long long *wt, uint32_t k)
+{
+	const unsigned long long v = p.in_range ? ldt_read64(p.w, a.n_words, p.bit0 + 8ull * k) : 0;
+	return v ^ wt[(p.phase + 8u * k) % 127u];
+}
+
 // ---- 1. slots, the whitening table --------------------------------------------------------------------------------------------
 
-// wtab[t] = the 64 whitening bits behind t steps of the register from 0x40 (the reflected register of le_decode_kernel, period 127);
-// wphase[s] = the t at which the register holds s
-extern "C" __global__ __launch_bounds__(LE_THREADS) void le_data_init_kernel(LdtArgs a)
+// params, the empty slots and cend, cleared: the part of an init kernel every stage on this frame needs.  i: the thread's index in the
+// grid, which covers the larger of the two caps; own(): what the stage itself clears of connection i
+template <class Own> __device__ __forceinline__ void ldt_init_frame(const LdtArgs &a, uint64_t i, Own own)
 {
 	const uint32_t nh = *a.d_cand_count, kh = *a.d_conn_count;
 	const uint32_t n = nh < a.cand_cap ? nh : a.cand_cap, k = kh < a.conn_cap ? kh : a.conn_cap;
-	const uint64_t i = (uint64_t)blockIdx.x * LE_THREADS + threadIdx.x;   // (the grid covers the larger of the two caps)
 	if (i == 0) {
 		a.params[0] = n;
 		a.params[1] = k;
@@ -250,27 +278,42 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_data_init_kernel(Ldt
 	if (i < n)
 		a.slot[i] = LDT_NONE;
 	if (i < k) {
-		uint4 *c = reinterpret_cast<uint4 *>(a.cend + i * 8), *m = reinterpret_cast<uint4 *>(a.cnum + i * 8);
-		uint4 *t = reinterpret_cast<uint4 *>(a.tally + i * 8);
-		c[0] = c[1] = m[0] = m[1] = t[0] = t[1] = make_uint4(0, 0, 0, 0);
+		own();
+		uint4 *c = reinterpret_cast<uint4 *>(a.cend + i * 8);
+		c[0] = c[1] = make_uint4(0, 0, 0, 0);
 	}
-	if (blockIdx.x == 0 && threadIdx.x < 127) {
-		uint32_t s = 0x40u;
-		for (uint32_t j = 0; j < threadIdx.x; j++) {
-			if (s & 1u)
-				s ^= 0x88u;
-			s >>= 1;
-		}
-		a.wphase[s] = threadIdx.x;
-		unsigned long long o = 0;
-		for (uint32_t j = 0; j < 64; j++) {
-			o |= (unsigned long long)(s & 1u) << j;
-			if (s & 1u)
-				s ^= 0x88u;
-			s >>= 1;
-		}
-		a.wtab[threadIdx.x] = o;
+}
+
+// wtab[t] = the 64 whitening bits behind t steps of the register from 0x40 (the reflected register of le_decode_kernel, period 127);
+// wphase[s] = the t at which the register holds s.  For the threads t < 127 of one workgroup
+__device__ __forceinline__ void ldt_init_whitening(const LdtArgs &a, uint32_t t)
+{
+	uint32_t s = 0x40u;
+	for (uint32_t j = 0; j < t; j++) {
+		if (s & 1u)
+			s ^= 0x88u;
+		s >>= 1;
 	}
+	a.wphase[s] = t;
+	unsigned long long o = 0;
+	for (uint32_t j = 0; j < 64; j++) {
+		o |= (unsigned long long)(s & 1u) << j;
+		if (s & 1u)
+			s ^= 0x88u;
+		s >>= 1;
+	}
+	a.wtab[t] = o;
+}
+
+extern "C" __global__ __launch_bounds__(LE_THREADS) void le_data_init_kernel(LdtArgs a)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * LE_THREADS + threadIdx.x;
+	ldt_init_frame(a, i, [=] {
+		uint4 *m = reinterpret_cast<uint4 *>(a.cnum + i * 8), *t = reinterpret_cast<uint4 *>(a.tally + i * 8);
+		m[0] = m[1] = t[0] = t[1] = make_uint4(0, 0, 0, 0);
+	});
+	if (blockIdx.x == 0 && threadIdx.x < 127)
+		ldt_init_whitening(a, threadIdx.x);
 }
 
 extern "C" __global__ __launch_bounds__(LE_THREADS) void le_data_slot_kernel(LdtArgs a)
@@ -510,6 +553,37 @@ __device__ __forceinline__ void ldt_tally(bool mine, bool one, uint32_t lane, ui
 	}
 }
 
+// A START of role 0 or 1 in slot q (sl: what LdtNumber::value loaded, ex: the exclusive prefix): its message's number and offset,
+// RUNT / COMPLETE / OVERRUN from the L2CAP header, STORED under the caps, the message record.  plain: the header's four octets
+// where the caller has them, else NULL: they are read from the stream.  Returns whether the message is COMPLETE
+__device__ __forceinline__ bool ldt_start(const LdtArgs &a, uint32_t q, const LdtSlot &sl, const LdtState<3> &ex, const uint32_t *plain)
+{
+	const uint32_t m = ex.w[0], bytes = sl.y, len = sl.x & 0xffu, i = a.slot[q];
+	const unsigned long long off = ((unsigned long long)ex.w[2] << 32) | ex.w[1];
+	uint32_t flags = BTBBX_LE_MSG_RUNT, hdr = 0xffffffffu;
+	bool complete = false;
+	if (len >= 4) {
+		hdr = plain ? *plain : (uint32_t)ldt_octets(a, ldt_where(a, q, sl.x), a.wtab, 0);
+		const unsigned long long whole = 4ull + (hdr & 0xffffu);
+		complete = bytes == whole;
+		flags = complete ? BTBBX_LE_MSG_COMPLETE : (bytes > whole ? BTBBX_LE_MSG_OVERRUN : 0u);
+	}
+	if (m < a.msg_cap && off + bytes <= a.byte_cap) {
+		flags |= BTBBX_LE_MSG_STORED;
+		a.sinfo[q] = sl.x | LDT_STORED;
+	}
+	a.msgno[q] = m;
+	a.boff[q] = off;
+	if (m < a.msg_cap) {
+		uint2 *o = reinterpret_cast<uint2 *>(a.msgs + m);
+		o[0] = make_uint2((uint32_t)off, (uint32_t)(off >> 32));
+		o[1] = make_uint2(sl.g, i);
+		o[2] = make_uint2(a.mfrag[q], bytes);
+		o[3] = make_uint2(hdr, LDT_ROLE(sl.x) | (flags << 8));
+	}
+	return complete;
+}
+
 // state: w0 = STARTs, w1 | w2 << 32 = their messages' octets
 struct LdtNumber {
 	static constexpr int NW = 3;
@@ -548,34 +622,8 @@ struct LdtNumber {
 			if (ldt_last(a.sg, q, n, g))
 				reinterpret_cast<uint4 *>(a.cnum + (size_t)g * 8)[1] = make_uint4(in.w[0], in.w[1], in.w[2], 0);
 		}
-		if (member && kind == BTBBX_LE_DATA_START && role < 2) {
-			const uint32_t m = ex.w[0], bytes = sl.y, len = sl.x & 0xffu, i = a.slot[q];
-			const unsigned long long off = ((unsigned long long)ex.w[2] << 32) | ex.w[1];
-			uint32_t flags = BTBBX_LE_MSG_RUNT, hdr = 0xffffffffu;
-			if (len >= 4) {
-				const uint2 where = reinterpret_cast<const uint2 *>(a.cands + i)[0];
-				const uint32_t stream = reinterpret_cast<const uint2 *>(a.cands + i)[2].x & 0xffffu;
-				const uint64_t bit = ((((uint64_t)where.y << 32) | where.x) & LT_OFF_MASK) + 56;
-				const unsigned long long raw = stream < a.n_streams ? ldt_read64(a.words + (uint64_t)stream * a.pitch_words, a.n_words, bit) : 0;
-				hdr = (uint32_t)(raw ^ a.wtab[((sl.x >> 24) + 16u) % 127u]);
-				const unsigned long long whole = 4ull + (hdr & 0xffffu);
-				complete = bytes == whole;
-				flags = complete ? BTBBX_LE_MSG_COMPLETE : (bytes > whole ? BTBBX_LE_MSG_OVERRUN : 0u);
-			}
-			if (m < a.msg_cap && off + bytes <= a.byte_cap) {
-				flags |= BTBBX_LE_MSG_STORED;
-				a.sinfo[q] = sl.x | LDT_STORED;
-			}
-			a.msgno[q] = m;
-			a.boff[q] = off;
-			if (m < a.msg_cap) {
-				uint2 *o = reinterpret_cast<uint2 *>(a.msgs + m);
-				o[0] = make_uint2((uint32_t)off, (uint32_t)(off >> 32));
-				o[1] = make_uint2(g, i);
-				o[2] = make_uint2(a.mfrag[q], bytes);
-				o[3] = make_uint2(hdr, role | (flags << 8));
-			}
-		}
+		if (member && kind == BTBBX_LE_DATA_START && role < 2)
+			complete = ldt_start(a, q, sl, ex, nullptr);
 		const uint32_t g0 = __shfl(g, 0, 64);
 		const bool one = __ballot(member && g == g0) == ~0ULL;
 		uint32_t *t = a.tally + (size_t)(member ? g : 0) * 8;
@@ -593,8 +641,8 @@ struct LdtNumber {
 extern "C" __global__ __launch_bounds__(LE_THREADS) void le_data_number_sum_kernel(LdtArgs a) { ldt_tile<LdtNumber, false>(a); }
 extern "C" __global__ __launch_bounds__(LE_THREADS) void le_data_number_kernel(LdtArgs a) { ldt_tile<LdtNumber, true>(a); }
 
-// (the sum of all tiles: the two counts)
-extern "C" __global__ __launch_bounds__(LE_THREADS) void le_data_number_prefix_kernel(LdtArgs a)
+// one workgroup: the prefixes of the tiles' sums; the sum of all is the two counts
+__device__ __forceinline__ void ldt_totals(const LdtArgs &a)
 {
 	const LdtState<3> all = ldt_prefix<LdtNumber>(a);
 	if (threadIdx.x == 0) {
@@ -603,19 +651,18 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_data_number_prefix_k
 	}
 }
 
+extern "C" __global__ __launch_bounds__(LE_THREADS) void le_data_number_prefix_kernel(LdtArgs a) { ldt_totals(a); }
+
 // ---- 7. rule 7: the records ----------------------------------------------------------------------------------------------------------
 
-extern "C" __global__ __launch_bounds__(LE_THREADS) void le_data_pkt_kernel(LdtArgs a)
+// the record of candidate i, which is the member in slot q or no member: its message and its position there, role | kind | bits;
+// a.gdst of a stored message's fragment
+__device__ __forceinline__ void ldt_pkt(const LdtArgs &a, uint32_t i, bool member, uint32_t q)
 {
-	const uint64_t at = (uint64_t)blockIdx.x * LE_THREADS + threadIdx.x;
-	const uint32_t n = a.params[0], k = a.params[1], i = (uint32_t)at;
-	if (at >= n)
-		return;
-	uint32_t g, first, msg = LDT_NONE, pos = 0, tail = 0xffffffffu;
-	uint4 p;
-	if (lf_member(a.cands, a.pkts, a.conns, i, n, k, g, p, first)) {
-		const uint32_t q = first + p.x, x = a.sinfo[q], kind = LDT_KIND(x);
-		if (kind <= BTBBX_LE_DATA_CONTINUATION) {               // a fragment: its message; where the gather puts it
+	uint32_t msg = LDT_NONE, pos = 0, tail = 0xffffffffu;
+	if (member) {
+		const uint32_t x = a.sinfo[q], kind = LDT_KIND(x);
+		if (kind <= BTBBX_LE_DATA_CONTINUATION) {               // a fragment: its message; where its octets go
 			const uint32_t from = kind == BTBBX_LE_DATA_START ? q : a.ps[q];
 			msg = a.msgno[from];
 			pos = a.sx[q] - a.sx[from];
@@ -630,6 +677,18 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_data_pkt_kernel(LdtA
 	o[0] = msg;
 	o[1] = pos;
 	o[2] = tail;
+}
+
+extern "C" __global__ __launch_bounds__(LE_THREADS) void le_data_pkt_kernel(LdtArgs a)
+{
+	const uint64_t at = (uint64_t)blockIdx.x * LE_THREADS + threadIdx.x;
+	const uint32_t n = a.params[0], k = a.params[1], i = (uint32_t)at;
+	if (at >= n)
+		return;
+	uint32_t g, first;
+	uint4 p;
+	const bool member = lf_member(a.cands, a.pkts, a.conns, i, n, k, g, p, first);
+	ldt_pkt(a, i, member, first + p.x);
 }
 
 extern "C" __global__ __launch_bounds__(LE_THREADS) void le_data_conn_kernel(LdtArgs a)
@@ -707,14 +766,13 @@ extern "C" size_t btbbx_le_data_scratch_bytes(uint32_t cand_cap, uint32_t conn_c
 	return le_data_layout(cand_cap, conn_cap).total;
 }
 
-// the 18 launches of one run
-static int le_data_launch(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, const btbbx_le_cand *d_cands,
-			  const uint32_t *d_count, uint32_t cap, const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
-			  const btbbx_le_track_pkt *d_pkts, btbbx_le_data *d_data, btbbx_le_data_pkt *d_data_pkts, btbbx_le_msg *d_msgs,
-			  uint32_t msg_cap, uint32_t *d_msg_count, uint8_t *d_bytes, uint64_t byte_cap, uint64_t *d_byte_count, void *d_scratch,
-			  hipStream_t q)
+// what the kernels are launched with, from a run's parameters and the layout of its scratch
+static LdtArgs le_data_args(const LdtLayout &L, const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			    const btbbx_le_cand *d_cands, const uint32_t *d_count, uint32_t cap, const btbbx_le_conn *d_conns,
+			    const uint32_t *d_conn_count, uint32_t conn_cap, const btbbx_le_track_pkt *d_pkts, btbbx_le_data *d_data,
+			    btbbx_le_data_pkt *d_data_pkts, btbbx_le_msg *d_msgs, uint32_t msg_cap, uint32_t *d_msg_count, uint8_t *d_bytes,
+			    uint64_t byte_cap, uint64_t *d_byte_count, void *d_scratch)
 {
-	const LdtLayout L = le_data_layout(cap, conn_cap);
 	char *s = (char *)d_scratch;
 	LdtArgs a;
 	a.words = d_words;
@@ -755,6 +813,19 @@ static int le_data_launch(const uint64_t *d_words, uint64_t n_words, uint64_t pi
 	a.bytes = d_bytes;
 	a.byte_cap = byte_cap;
 	a.byte_count = (unsigned long long *)d_byte_count;
+	return a;
+}
+
+// the 18 launches of one run
+static int le_data_launch(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, const btbbx_le_cand *d_cands,
+			  const uint32_t *d_count, uint32_t cap, const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
+			  const btbbx_le_track_pkt *d_pkts, btbbx_le_data *d_data, btbbx_le_data_pkt *d_data_pkts, btbbx_le_msg *d_msgs,
+			  uint32_t msg_cap, uint32_t *d_msg_count, uint8_t *d_bytes, uint64_t byte_cap, uint64_t *d_byte_count, void *d_scratch,
+			  hipStream_t q)
+{
+	const LdtLayout L = le_data_layout(cap, conn_cap);
+	const LdtArgs a = le_data_args(L, d_words, n_words, pitch_words, n_streams, d_cands, d_count, cap, d_conns, d_conn_count, conn_cap, d_pkts,
+				       d_data, d_data_pkts, d_msgs, msg_cap, d_msg_count, d_bytes, byte_cap, d_byte_count, d_scratch);
 	const dim3 per_cand((uint32_t)(((uint64_t)cap + LE_THREADS - 1) / LE_THREADS)), per_tile(L.tiles_n), wg(LE_THREADS), one(1);
 	const dim3 per_conn((uint32_t)(((uint64_t)conn_cap + LE_THREADS - 1) / LE_THREADS));
 	const dim3 per_frag((uint32_t)(((uint64_t)cap + LE_THREADS / LDT_FRAG - 1) / (LE_THREADS / LDT_FRAG)));
@@ -791,14 +862,9 @@ extern "C" int btbbx_le_data_device(const uint64_t *d_words, uint64_t n_words, u
 				    void *d_scratch, size_t scratch_bytes, void *hip_stream)
 {
 	const char *who = "btbbx_le_data_device";
-	if (n_streams == 0) {
-		set_error("%s: n_streams must be >= 1", who);
-		return BTBBX_E_ARG;
-	}
-	if (n_words == 0 || (n_streams > 1 && pitch_words < n_words) || n_words > (1ull << 42)) {
-		set_error("%s: n_words must be 1 .. 2^42 and pitch_words >= n_words", who);
-		return BTBBX_E_ARG;
-	}
+	int rc = le_check_streams(who, n_words, pitch_words, n_streams);
+	if (rc)
+		return rc;
 	const LdtLayout L = le_data_layout(cand_cap, conn_cap);
 	if (!d_words || !d_phys_channel || !d_cands || !d_cand_count || !d_conns || !d_conn_count || !d_tracks || !d_pkts || !d_data ||
 	    !d_data_pkts || (!d_msgs && msg_cap) || !d_msg_count || (!d_bytes && byte_cap) || !d_byte_count || !d_scratch ||
@@ -814,7 +880,7 @@ extern "C" int btbbx_le_data_device(const uint64_t *d_words, uint64_t n_words, u
 			  "counters 4; the channels 2)", who);
 		return BTBBX_E_ARG;
 	}
-	const int rc = ctx_require();
+	rc = ctx_require();
 	if (rc)
 		return rc;
 	hipStream_t q = (hipStream_t)hip_stream;

@@ -974,6 +974,20 @@ static int le_follow_launch(const uint64_t *d_words, uint64_t n_words, uint64_t 
 	return BTBBX_OK;
 }
 
+// the shape of the streams every _device entry that reads them refuses: this stage's and those of the span, data and decryption stages
+static int le_check_streams(const char *who, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams)
+{
+	if (n_streams == 0) {
+		set_error("%s: n_streams must be >= 1", who);
+		return BTBBX_E_ARG;
+	}
+	if (n_words == 0 || (n_streams > 1 && pitch_words < n_words) || n_words > (1ull << 42)) {
+		set_error("%s: n_words must be 1 .. 2^42 and pitch_words >= n_words", who);
+		return BTBBX_E_ARG;
+	}
+	return BTBBX_OK;
+}
+
 extern "C" int btbbx_le_epoch_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
 				      const uint16_t *d_phys_channel,
 				      const btbbx_le_cand *d_cands, const uint32_t *d_cand_count, uint32_t cand_cap,
@@ -985,12 +999,10 @@ extern "C" int btbbx_le_epoch_device(const uint64_t *d_words, uint64_t n_words, 
 {
 	const char *who = "btbbx_le_epoch_device";
 	int rc = le_track_check_args(who, n_streams, unit_bits, jitter_bits);
+	if (!rc)
+		rc = le_check_streams(who, n_words, pitch_words, n_streams);
 	if (rc)
 		return rc;
-	if (n_words == 0 || (n_streams > 1 && pitch_words < n_words) || n_words > (1ull << 42)) {
-		set_error("%s: n_words must be 1 .. 2^42 and pitch_words >= n_words", who);
-		return BTBBX_E_ARG;
-	}
 	const LfLayout L = le_follow_layout(cand_cap, conn_cap);
 	if (!d_words || !d_phys_channel || !d_cands || !d_cand_count || !d_conns || !d_conn_count || !d_tracks || !d_pkts || !d_seeds ||
 	    !d_follows || !d_follow_pkts || !d_scratch || scratch_bytes < L.total) {

@@ -380,6 +380,30 @@ static int le_host_messages(btbbx_le_msg *msgs, const btbbx_le_msg *d_msgs, uint
 	return BTBBX_OK;
 }
 
+// the data stage over a tail that le_data_host_layout laid out at `base`; its counts stand at base + T.counts, the octets' first
+static int le_host_data(const LeHostRun &r, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, char *base, const LdtHostTail &T)
+{
+	uint64_t *d_counts = (uint64_t *)(base + T.counts);
+	return le_data_launch(r.d_words, n_words, pitch_words, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count, r.dev_conns,
+			      r.d_pkts, (btbbx_le_data *)(base + T.data), (btbbx_le_data_pkt *)(base + T.dpkts), (btbbx_le_msg *)(base + T.msgs), T.msg_cap,
+			      (uint32_t *)(d_counts + 1), (uint8_t *)(base + T.bytes), T.byte_cap, d_counts, base + T.scratch, r.q);
+}
+
+// behind le_host_finish (ret: what it gave): the two counts as they were read back, the messages and their octets
+static int64_t le_host_message_outs(int64_t ret, const LeHostRun &r, const uint64_t *counts, uint32_t msg_cap, btbbx_le_msg *msgs,
+				    const btbbx_le_msg *d_msgs, uint64_t *n_msgs_out, uint8_t *bytes, const uint8_t *d_bytes, uint64_t *n_bytes_out)
+{
+	if (ret < 0 || !r.nc)
+		return ret;
+	const uint64_t n_msgs = (uint32_t)counts[1];
+	if (n_msgs_out)
+		*n_msgs_out = n_msgs;
+	if (n_bytes_out)
+		*n_bytes_out = counts[0];
+	const int rc = le_host_messages(msgs, d_msgs, std::min<uint64_t>(n_msgs, msg_cap), bytes, d_bytes, r.q);
+	return rc ? rc : ret;
+}
+
 extern "C" int64_t btbbx_le_data_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
 				      uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
 				      btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
@@ -408,24 +432,12 @@ extern "C" int64_t btbbx_le_data_host(const uint64_t *words, uint64_t n_words, u
 	if (r.nc) {
 		if ((rc = le_host_track(a, r)))
 			return rc;
-		rc = le_data_launch(r.d_words, n_words, pitch_words, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count, r.dev_conns,
-				    r.d_pkts, (btbbx_le_data *)(r.own + T.data), (btbbx_le_data_pkt *)(r.own + T.dpkts), d_msgs, T.msg_cap,
-				    (uint32_t *)(d_counts + 1), d_bytes, T.byte_cap, d_counts, r.own + T.scratch, r.q);
-		if (rc)
+		if ((rc = le_host_data(r, n_words, pitch_words, n_streams, r.own, T)))
 			return rc;
 		HIP_TRY(hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, r.q));
 	}
 	const LeHostOut outs[] = {{data, r.own + T.data, sizeof(btbbx_le_data), false}, {data_pkts, r.own + T.dpkts, sizeof(btbbx_le_data_pkt), true}};
-	const int64_t ret = le_host_finish(a, r, 0, outs, 2);
-	if (ret < 0 || !r.nc)
-		return ret;
-	const uint64_t n_msgs = (uint32_t)counts[1];
-	if (n_msgs_out)
-		*n_msgs_out = n_msgs;
-	if (n_bytes_out)
-		*n_bytes_out = counts[0];
-	rc = le_host_messages(msgs, d_msgs, std::min<uint64_t>(n_msgs, T.msg_cap), bytes, d_bytes, r.q);
-	return rc ? rc : ret;
+	return le_host_message_outs(le_host_finish(a, r, 0, outs, 2), r, counts, T.msg_cap, msgs, d_msgs, n_msgs_out, bytes, d_bytes, n_bytes_out);
 }
 
 // ---- decryption -------------------------------------------------------------------------------------------------------------------
@@ -481,15 +493,13 @@ extern "C" int64_t btbbx_le_crypt_host(const uint64_t *words, uint64_t n_words, 
 	const LxHostTail C = le_crypt_host_layout(r.dev_cap, r.dev_conns, n_keys, T);
 	btbbx_le_data_pkt *d_dpkts = (btbbx_le_data_pkt *)(r.own + D.dpkts);
 	btbbx_le_msg *d_msgs = (btbbx_le_msg *)(r.own + C.msgs);
-	uint64_t *d_counts = (uint64_t *)(r.own + C.counts), *d_data_counts = (uint64_t *)(r.own + D.counts), counts[2] = {0, 0};
+	uint64_t *d_counts = (uint64_t *)(r.own + C.counts), counts[2] = {0, 0};
 	uint8_t *d_bytes = (uint8_t *)(r.own + C.bytes), *d_keys = (uint8_t *)(r.own + C.keys);
 	if (r.nc) {
 		HIP_TRY(hipMemcpyAsync(d_keys, keys, 16 * (size_t)n_keys, hipMemcpyHostToDevice, r.q));
 		if ((rc = le_host_track(a, r)))
 			return rc;
-		rc = le_data_launch(r.d_words, n_words, pitch_words, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count, r.dev_conns,
-				    r.d_pkts, (btbbx_le_data *)(r.own + D.data), d_dpkts, (btbbx_le_msg *)(r.own + D.msgs), 0,
-				    (uint32_t *)(d_data_counts + 1), (uint8_t *)(r.own + D.bytes), 0, d_data_counts, r.own + D.scratch, r.q);
+		rc = le_host_data(r, n_words, pitch_words, n_streams, r.own, D);        // (caps 0: its messages and octets are not kept)
 		if (!rc)
 			rc = le_crypt_launch(r.d_words, n_words, pitch_words, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count,
 					     r.dev_conns, r.d_pkts, d_dpkts, d_keys, n_keys, window, (btbbx_le_crypt *)(r.own + C.crypt),
@@ -502,16 +512,7 @@ extern "C" int64_t btbbx_le_crypt_host(const uint64_t *words, uint64_t n_words, 
 	const LeHostOut outs[] = {{data, r.own + D.data, sizeof(btbbx_le_data), false}, {data_pkts, d_dpkts, sizeof(btbbx_le_data_pkt), true},
 				  {crypt, r.own + C.crypt, sizeof(btbbx_le_crypt), false}, {crypt_pkts, r.own + C.cpkts, sizeof(btbbx_le_crypt_pkt), true},
 				  {plain_pkts, r.own + C.ppkts, sizeof(btbbx_le_data_pkt), true}};
-	const int64_t ret = le_host_finish(a, r, 0, outs, 5);
-	if (ret < 0 || !r.nc)
-		return ret;
-	const uint64_t n_msgs = (uint32_t)counts[1];
-	if (n_msgs_out)
-		*n_msgs_out = n_msgs;
-	if (n_bytes_out)
-		*n_bytes_out = counts[0];
-	rc = le_host_messages(msgs, d_msgs, std::min<uint64_t>(n_msgs, T.msg_cap), bytes, d_bytes, r.q);
-	return rc ? rc : ret;
+	return le_host_message_outs(le_host_finish(a, r, 0, outs, 5), r, counts, T.msg_cap, msgs, d_msgs, n_msgs_out, bytes, d_bytes, n_bytes_out);
 }
 
 // ---- following: the follow stage or the span stage behind the seed stage ---------------------------------------------------------
@@ -699,9 +700,7 @@ extern "C" int64_t btbbx_le_pair_host(const uint64_t *words, uint64_t n_words, u
 			btbbx_le_msg *d_msgs = (btbbx_le_msg *)(d_scratch + T.msgs);
 			uint64_t *d_counts = (uint64_t *)(d_scratch + T.counts);
 			uint8_t *d_bytes = (uint8_t *)(d_scratch + T.bytes);
-			int rc2 = le_data_launch(r.d_words, n_words, pitch, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count,
-						 r.dev_conns, r.d_pkts, (btbbx_le_data *)(d_scratch + T.data), (btbbx_le_data_pkt *)(d_scratch + T.dpkts),
-						 d_msgs, T.msg_cap, (uint32_t *)(d_counts + 1), d_bytes, T.byte_cap, d_counts, d_scratch + T.scratch, r.q);
+			int rc2 = le_host_data(r, n_words, pitch, n_streams, d_scratch, T);
 			if (!rc2)
 				rc2 = le_pair_launch(r.d_conn_count, r.dev_conns, d_seeds, d_msgs, (uint32_t *)(d_counts + 1), T.msg_cap, d_bytes,
 						     T.byte_cap, tk_limit, (btbbx_le_pair *)d_out[0], (uint8_t *)d_out[1], key_cap, (uint32_t *)d_out[2],

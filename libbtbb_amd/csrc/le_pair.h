@@ -2,7 +2,8 @@
 // for every connection the SMP exchange among its L2CAP messages, the temporary key (TK) of a legacy pairing by trying every value
 // below tk_limit against the Confirm values, the short-term key (STK) under it, as a key table the decryption stage takes as it is,
 // and the long-term keys the peers distribute.  The contract is in include/btbbx.h (btbbx_le_pair_device), the reasoning in DESIGN
-// 3.8.8.  All arithmetic is integer arithmetic.  AES is le_crypt.h's (lx_te_entry, lx_expand, lx_aes).
+// 3.8.8.  All arithmetic is integer arithmetic.  AES is le_aes.h's (lx_te_entry, lx_expand, lx_aes); of le_crypt.h only LX_MAX_KEYS,
+// the size of the key table the decryption stage takes.
 //
 //   1. le_pair_init_kernel                           the per-connection tables cleared; AES's round table; K and W
 //   2. le_pair_find_kernel                           rules 1, 2 and 8: one lane per message, its class; PREQ and the LTKs by atomicMin
@@ -15,6 +16,7 @@
 //
 // 12 launches, whatever the counts and caps.  Nothing here synchronises or reads back but the host wrapper.
 #pragma once
+#include "le_aes.h"
 #include "le_crypt.h"
 
 #define LP_NONE       0xffffffffu

@@ -628,12 +628,10 @@ extern "C" int btbbx_le_span_device(const uint64_t *d_words, uint64_t n_words, u
 		return BTBBX_E_ARG;
 	}
 	int rc = le_track_check_args(who, n_streams, unit_bits, jitter_bits);
+	if (!rc)
+		rc = le_check_streams(who, n_words, pitch_words, n_streams);
 	if (rc)
 		return rc;
-	if (n_words == 0 || (n_streams > 1 && pitch_words < n_words) || n_words > (1ull << 42)) {
-		set_error("%s: n_words must be 1 .. 2^42 and pitch_words >= n_words", who);
-		return BTBBX_E_ARG;
-	}
 	const LsLayout S = le_span_layout(cand_cap, conn_cap, max_updates);
 	if (!d_words || !d_phys_channel || !d_cands || !d_cand_count || !d_conns || !d_conn_count || !d_tracks || !d_pkts || !d_seeds ||
 	    !d_spans || !d_span_pkts || !d_span_recs || !d_scratch || scratch_bytes < S.total) {

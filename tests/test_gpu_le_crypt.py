@@ -144,6 +144,39 @@ def test_without_an_armed_connection_the_outputs_are_the_data_stages():
         assert not got[0][:-1]["flags"].any() and set(got[1][:-1]["state"].tolist()) <= {cm.CLEAR, 0xFF}
 
 
+def _identity_world(name):
+    """-> (world, msg_cap, byte_cap); caps None: room for every message and octet, as many as the data stage counts."""
+    import _le_data_lattice as dl
+    if name == "product":
+        return dl.product_list(), None, None
+    b = dl.sequence_world()
+    assert len(b.cands) > 2048 and len(b.cands) % 2048 and len(b.conns) % 256
+    if name == "sequence":
+        return b, None, None
+    from test_le_data_lattice_model import sequence_caps
+    return (b,) + sequence_caps(dl.sequence_model())
+
+
+@pytest.mark.parametrize("name", ["sequence", "sequence_under_caps", "product"])
+def test_without_an_armed_connection_across_waves_and_tiles(name):
+    """Rule 8's identity where the messages cross waves, workgroups and a tile of 2048 slots (the sequence worlds of
+    tests/_le_data_lattice.py, with room for everything and under caps that cut the stored prefix short) and over every source residue,
+    destination residue and length of a fragment (the product list): no CONTROL member of these worlds has the length of a procedure
+    PDU, so no connection is ARMED (tests/test_le_crypt_model.py holds that on the model) and every output is the data stage's."""
+    from test_gpu_le_data import _device as data_device
+    b, msg_cap, byte_cap = _identity_world(name)
+    if msg_cap is None:
+        totals = data_device(b, 0, 0)
+        msg_cap, byte_cap = totals[4] + 3, totals[5] + 11
+    data, dpkts, msgs, octets, n_msgs, n_bytes = data_device(b, msg_cap, byte_cap)
+    stored = int((msgs[:min(n_msgs, msg_cap)]["flags"] & dm.STORED != 0).sum())
+    assert n_msgs > 2048 and (0 < stored < msg_cap < n_msgs if name == "sequence_under_caps" else stored == n_msgs)
+    got = _device(b, dpkts[:len(b.cands)], list(cm.WORLD_KEYS), 8, msg_cap, byte_cap)
+    assert (got[5], got[6]) == (n_msgs, n_bytes)
+    assert got[3].tobytes() == msgs.tobytes() and got[4].tobytes() == octets.tobytes() and got[2].tobytes() == dpkts.tobytes()
+    assert not got[0][:-1]["flags"].any() and set(got[1][:-1]["state"].tolist()) <= {cm.CLEAR, 0xFF}
+
+
 # ---- the lattice where the kernel can go wrong ----------------------------------------------------------------------------------------
 LENGTHS = (1, 15, 16, 17, 31, 32, 33, 247, 251)
 MODS = (0, 1, 31, 63)

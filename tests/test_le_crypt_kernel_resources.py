@@ -1,6 +1,7 @@
 """Registers, LDS and scratch of the kernels of LE decryption (le_crypt.h), read from the built library as
-tests/test_le_data_kernel_resources.py does for the data stage: DESIGN 3.8.7 names twenty-four kernels, none of them with scratch
-or a spilled register, and states their VGPR and LDS figures.  The trial kernels keep a key schedule of 44 words in registers and
+tests/test_le_data_kernel_resources.py does for the data stage: DESIGN 3.8.7 names nineteen kernels (the other five of the
+stage's 24 launches are the data stage's kernels, tests/test_le_data_kernel_resources.py), none of them with scratch or a spilled
+register, and states their VGPR and LDS figures.  The trial kernels keep a key schedule of 44 words in registers and
 may use up to 160 VGPRs (three waves per SIMD); every other kernel stays within 64 (eight)."""
 import os
 import re
@@ -13,7 +14,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # kernel -> (VGPRs, bytes of LDS), as DESIGN 3.8.7 lists them
 DOCUMENTED = {
     "le_crypt_init_kernel": (44, 0),
-    "le_crypt_slot_kernel": (10, 0),
     "le_crypt_find_kernel": (20, 0),
     "le_crypt_rsp_kernel": (6, 0),
     "le_crypt_begin_kernel": (6, 0),
@@ -26,10 +26,6 @@ DOCUMENTED = {
     "le_crypt_first_kernel": (109, 2048),
     "le_crypt_retry_kernel": (121, 2048),
     "le_crypt_effect_kernel": (59, 2048),
-    "le_crypt_msg_sum_kernel": (33, 112),
-    "le_crypt_msg_prefix_kernel": (38, 112),
-    "le_crypt_msg_kernel": (46, 112),
-    "le_crypt_close_kernel": (12, 0),
     "le_crypt_number_sum_kernel": (22, 48),
     "le_crypt_number_prefix_kernel": (27, 48),
     "le_crypt_number_kernel": (42, 48),

@@ -99,6 +99,27 @@ def test_without_an_armed_connection_the_messages_are_the_data_stages():
         assert (cut.msgs, cut.payload, cut.n_msgs, cut.n_bytes) == (want.msgs, want.payload, want.n_msgs, want.n_bytes)
 
 
+def _unarmed(name):
+    """(the data model, the decryption model) of a world of tests/_le_data_lattice.py; `sequence_under_caps`: under the caps of the data
+    stage's own test."""
+    import _le_data_lattice as dl
+    from test_le_data_lattice_model import sequence_caps
+    b = dl.product_list() if name == "product" else dl.sequence_world()
+    caps = sequence_caps(dl.sequence_model()) if name == "sequence_under_caps" else (1 << 20, 1 << 30)
+    data = dm.built_model(b, *caps) if name == "product" else dl.sequence_model(None, *caps)
+    return data, cm.crypt(b.conns, b.cands, b.pkts, data.dpkts, b.words, b.n_words, KEYS, 8, *caps)
+
+
+@pytest.mark.parametrize("name", ["sequence", "sequence_under_caps", "product"])
+def test_no_connection_of_the_data_lattices_is_armed(name):
+    """What tests/test_gpu_le_crypt.py's identity over these worlds rests on: their CONTROL members have two octets, no procedure PDU
+    has, so no record carries a flag and the messages are the data stage's."""
+    data, out = _unarmed(name)
+    assert all(r.flags == 0 and r.key == 0xFF for r in out.crypt) and {p.state for p in out.cpkts if p is not None} == {cm.CLEAR}
+    assert (out.n_msgs, out.n_bytes) == (data.n_msgs, data.n_bytes) and out.n_msgs > 2048
+    assert (out.msgs, out.payload, out.ppkts) == (data.msgs, data.payload, data.dpkts)
+
+
 @pytest.mark.parametrize("variant", sorted(cm.VARIANTS))
 def test_every_wrong_model_is_told_from_the_right_one(world, variant):
     b, (data, out) = world
