@@ -560,6 +560,9 @@ static int upload_tables(int max_ac_errors)
 		HIP_TRY(hipMalloc(&fresh.bitmap2, mb.bitmap2.size() * 4));
 		HIP_TRY(hipMemcpy(fresh.bitmap2, mb.bitmap2.data(), mb.bitmap2.size() * 4, hipMemcpyHostToDevice));
 	}
+	// one slot behind the table's end repeats slot 0: a probe that loads slots h and h + 1 in one go (scan_slide_kernel's split
+	// drain) needs no wrap at h = mask
+	mb.slots.push_back(mb.slots[0]);
 	HIP_TRY(hipMalloc(&fresh.tab, total));
 	HIP_TRY(hipMalloc(&fresh.hslots, mb.slots.size() * sizeof(uint64_t)));
 	char *base = (char *)fresh.tab;

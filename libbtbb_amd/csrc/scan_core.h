@@ -175,76 +175,114 @@ __device__ __forceinline__ uint32_t syn3_entry(const ScanTables &t, uint32_t i)
 		return t.tabA[((i - 256u) & 7u) << 8] ^ t.tabB[(i - 256u) >> 3] ^ t.tabB[0];   // 42 .. 44 (tabA) and 45 .. 49 (tabB, linear part)
 	return t.tabB[(i - 512u) << 5];                                            // 50 .. 56, with tabB's constant
 }
+// The two-error form in pieces, for a caller that sends the pattern look-up and reads its answer later (scan_slide_kernel's
+// split drain); verify_lap_any<.., TWO> is these pieces in a row.  lap_syndrome2 = the syndrome of the window, and the window
+// with its barker bits corrected; hslot_of = the first slot of a syndrome's probe sequence; slot_errors2 = a matching slot's
+// error positions taken out of the window, their count returned.
+__device__ __forceinline__ uint64_t lap_syndrome2(const ScanArgs &a, uint64_t w, uint64_t &sw, uint32_t syn3_off)
+{
+	const uint32_t win = (uint32_t)(w >> 57);
+	const uint32_t cls = __popc(win ^ BARKER1) <= 1 ? 1u : 0u;
+	sw = (w & LOW57) | ((uint64_t)(cls ? BARKER1 : BARKER0) << 57);
+	const uint64_t low = w & LOW57;
+	const uint32_t hi = (uint32_t)(low >> 32);                                 // window bits 32 .. 56; a table index as a byte offset
+	const uint32_t s_lo = (uint32_t)low ^ lds_ld(syn3_off + (hi & 0x3fcu)) ^ lds_ld(syn3_off + 1024u + ((hi >> 8) & 0x3fcu))
+			      ^ lds_ld(syn3_off + 2048u + ((hi >> 16) & 0x1fcu)) ^ (cls ? a.t.kdiff : 0u);
+	const uint32_t l0 = (uint32_t)low, l1 = (uint32_t)(low >> 32);
+	const uint32_t f0 = (l0 & (uint32_t)a.t.hi_mask[0]) ^ (l1 & (uint32_t)(a.t.hi_mask[0] >> 32));
+	const uint32_t f1 = (l0 & (uint32_t)a.t.hi_mask[1]) ^ (l1 & (uint32_t)(a.t.hi_mask[1] >> 32));
+	const uint32_t s_hi = ((uint32_t)(a.t.kclass[cls] >> 32) ^ (__popc(f0) & 1) ^ ((__popc(f1) & 1) << 1)) & 3;
+	return ((uint64_t)s_hi << 32) | s_lo;
+}
+__device__ __forceinline__ uint64_t hslot_of(const ScanTables &t, uint64_t syn)
+{
+	return ((((uint32_t)syn ^ (uint32_t)(syn >> 32)) * 0x9E3779B1u) >> (32 - __popcll(t.hmask))) & t.hmask;
+}
+__device__ __forceinline__ bool hslot_matches(uint64_t slot, uint64_t syn)
+{
+	return (slot & 0x3ffffffffULL) == syn;
+}
+__device__ __forceinline__ uint32_t slot_errors2(uint64_t slot, uint64_t &sw)
+{
+	// a stored pattern has a first position (0 .. 57) and a second one or 63; bit 63 of the window is a barker bit
+	// that the LAP does not read, so "no second error" needs no select, only the count does
+	const uint32_t p0 = (uint32_t)(slot >> 34) & 63, p1 = (uint32_t)(slot >> 40) & 63;
+	sw ^= (1ULL << p0) | (1ULL << p1);
+	return p1 != 63 ? 2u : 1u;
+}
+__device__ __forceinline__ uint32_t lap_of(uint64_t sw)
+{
+	return (uint32_t)(sw >> 34) & 0xffffff;
+}
 template <bool LDS_TABLES = true, bool TWO = false>
 __device__ __forceinline__ bool verify_lap_any(const ScanArgs &a, uint64_t w, uint32_t &lap, uint32_t &nerr_out, uint32_t syn3_off = 0)
 {
-	uint32_t win = (uint32_t)(w >> 57);
-	uint32_t cls = __popc(win ^ BARKER1) <= 1 ? 1u : 0u;
-	uint64_t sw = (w & LOW57) | ((uint64_t)(cls ? BARKER1 : BARKER0) << 57);
-	// syndrome of (sw ^ pn): linear in the low 57 window bits plus a class constant.  The low 32
-	// bits come from the LDS tables exactly as in the probe; bits 32 and 33 are two parities.  (The
-	// byte tables in global memory cost eight divergent loads per candidate, which is what bounded
-	// the scan for tables built for three or more errors.)
-	const uint64_t low = w & LOW57;
-	const uint32_t ia = (uint32_t)(low >> TABA_FIRST) & ((1u << TABA_BITS) - 1), ib = (uint32_t)(low >> (TABA_FIRST + TABA_BITS));
-	uint32_t s_lo;
 	if constexpr (TWO) {
-		const uint32_t hi = (uint32_t)(low >> 32);                                 // window bits 32 .. 56; a table index as a byte offset
-		s_lo = (uint32_t)low ^ lds_ld(syn3_off + (hi & 0x3fcu)) ^ lds_ld(syn3_off + 1024u + ((hi >> 8) & 0x3fcu))
-		       ^ lds_ld(syn3_off + 2048u + ((hi >> 16) & 0x1fcu)) ^ (cls ? a.t.kdiff : 0u);
-	} else {
-		s_lo = (uint32_t)low ^ (LDS_TABLES ? lds_ld(LDS_OFF_TABA + (ia << 2)) : a.t.tabA[ia])
-		       ^ (LDS_TABLES ? lds_ld(LDS_OFF_TABB + (ib << 2)) : a.t.tabB[ib]) ^ (cls ? a.t.kdiff : 0u);
-	}
-	uint32_t s_hi;
-	if constexpr (TWO) {
-		const uint32_t l0 = (uint32_t)low, l1 = (uint32_t)(low >> 32);
-		const uint32_t f0 = (l0 & (uint32_t)a.t.hi_mask[0]) ^ (l1 & (uint32_t)(a.t.hi_mask[0] >> 32));
-		const uint32_t f1 = (l0 & (uint32_t)a.t.hi_mask[1]) ^ (l1 & (uint32_t)(a.t.hi_mask[1] >> 32));
-		s_hi = ((uint32_t)(a.t.kclass[cls] >> 32) ^ (__popc(f0) & 1) ^ ((__popc(f1) & 1) << 1)) & 3;
-	} else {
-		s_hi = ((uint32_t)(a.t.kclass[cls] >> 32) ^ (__popcll(low & a.t.hi_mask[0]) & 1)
-			^ ((__popcll(low & a.t.hi_mask[1]) & 1) << 1)) & 3;
-	}
-	const uint64_t syn = ((uint64_t)s_hi << 32) | s_lo;
-	if (!TWO && a.t.bitmap2) {
-		const uint32_t i2 = (s_lo * 0x9E3779B1u) >> a.t.bitmap2_shift;
-		if (!((a.t.bitmap2[i2 >> 5] >> (i2 & 31)) & 1))
-			return false;
-	}
-	uint32_t nerr = 0;
-	if (syn) {
-		uint64_t h = ((((uint32_t)syn ^ (uint32_t)(syn >> 32)) * 0x9E3779B1u) >> (32 - __popcll(a.t.hmask))) & a.t.hmask;
-		for (;;) {
-			uint64_t slot = a.t.hslots[h];
-			if (slot == HSLOT_EMPTY)
-				return false;                         // no pattern -> ac_errors = 0xff -> reject
-			if ((slot & 0x3ffffffffULL) == syn) {
-				if constexpr (TWO) {
-					// a stored pattern has a first position (0 .. 57) and a second one or 63; bit 63 of the window is a barker bit
-					// that the LAP below does not read, so "no second error" needs no select, only the count does
-					const uint32_t p0 = (uint32_t)(slot >> 34) & 63, p1 = (uint32_t)(slot >> 40) & 63;
-					sw ^= (1ULL << p0) | (1ULL << p1);
-					nerr = p1 != 63 ? 2u : 1u;
+		uint64_t sw;
+		const uint64_t syn = lap_syndrome2(a, w, sw, syn3_off);
+		uint32_t nerr = 0;
+		if (syn) {
+			uint64_t h = hslot_of(a.t, syn);
+			for (;;) {
+				const uint64_t slot = a.t.hslots[h];
+				if (slot == HSLOT_EMPTY)
+					return false;                         // no pattern -> ac_errors = 0xff -> reject
+				if (hslot_matches(slot, syn)) {
+					nerr = slot_errors2(slot, sw);
 					break;
 				}
-				uint64_t err = 0;
-#pragma unroll
-				for (int i = 0; i < 5; i++) {
-					uint32_t pos = (uint32_t)(slot >> (34 + 6 * i)) & 63;
-					if (pos != 63)
-						err |= 1ULL << pos;
-				}
-				sw ^= err;
-				nerr = __popcll(err);
-				break;
+				h = (h + 1) & a.t.hmask;
 			}
-			h = (h + 1) & a.t.hmask;
 		}
+		lap = lap_of(sw);
+		nerr_out = nerr;
+		return (int)nerr <= a.max_err;
+	} else {
+		uint32_t win = (uint32_t)(w >> 57);
+		uint32_t cls = __popc(win ^ BARKER1) <= 1 ? 1u : 0u;
+		uint64_t sw = (w & LOW57) | ((uint64_t)(cls ? BARKER1 : BARKER0) << 57);
+		// syndrome of (sw ^ pn): linear in the low 57 window bits plus a class constant.  The low 32
+		// bits come from the LDS tables exactly as in the probe; bits 32 and 33 are two parities.  (The
+		// byte tables in global memory cost eight divergent loads per candidate, which is what bounded
+		// the scan for tables built for three or more errors.)
+		const uint64_t low = w & LOW57;
+		const uint32_t ia = (uint32_t)(low >> TABA_FIRST) & ((1u << TABA_BITS) - 1), ib = (uint32_t)(low >> (TABA_FIRST + TABA_BITS));
+		const uint32_t s_lo = (uint32_t)low ^ (LDS_TABLES ? lds_ld(LDS_OFF_TABA + (ia << 2)) : a.t.tabA[ia])
+				      ^ (LDS_TABLES ? lds_ld(LDS_OFF_TABB + (ib << 2)) : a.t.tabB[ib]) ^ (cls ? a.t.kdiff : 0u);
+		const uint32_t s_hi = ((uint32_t)(a.t.kclass[cls] >> 32) ^ (__popcll(low & a.t.hi_mask[0]) & 1)
+				       ^ ((__popcll(low & a.t.hi_mask[1]) & 1) << 1)) & 3;
+		const uint64_t syn = ((uint64_t)s_hi << 32) | s_lo;
+		if (a.t.bitmap2) {
+			const uint32_t i2 = (s_lo * 0x9E3779B1u) >> a.t.bitmap2_shift;
+			if (!((a.t.bitmap2[i2 >> 5] >> (i2 & 31)) & 1))
+				return false;
+		}
+		uint32_t nerr = 0;
+		if (syn) {
+			uint64_t h = ((((uint32_t)syn ^ (uint32_t)(syn >> 32)) * 0x9E3779B1u) >> (32 - __popcll(a.t.hmask))) & a.t.hmask;
+			for (;;) {
+				uint64_t slot = a.t.hslots[h];
+				if (slot == HSLOT_EMPTY)
+					return false;                         // no pattern -> ac_errors = 0xff -> reject
+				if ((slot & 0x3ffffffffULL) == syn) {
+					uint64_t err = 0;
+#pragma unroll
+					for (int i = 0; i < 5; i++) {
+						uint32_t pos = (uint32_t)(slot >> (34 + 6 * i)) & 63;
+						if (pos != 63)
+							err |= 1ULL << pos;
+					}
+					sw ^= err;
+					nerr = __popcll(err);
+					break;
+				}
+				h = (h + 1) & a.t.hmask;
+			}
+		}
+		lap = (uint32_t)(sw >> 34) & 0xffffff;
+		nerr_out = nerr;
+		return (int)nerr <= a.max_err;
 	}
-	lap = (uint32_t)(sw >> 34) & 0xffffff;
-	nerr_out = nerr;
-	return (int)nerr <= a.max_err;
 }
 
 // ---- LAP_ANY ----------------------------------------------------------------------------

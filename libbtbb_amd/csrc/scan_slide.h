@@ -1,6 +1,7 @@
 // scan_slide.h -- scan_slide_kernel, the headline kernel (LAP_ANY with tables for <= 4 errors), its tuning constants and its two
 // cuts.  A piece of scan.hip.
 #pragma once
+#include <type_traits>
 #include "scan_core.h"
 
 // ---- LAP_ANY, sliding checks (tables for <= 4 errors; two cuts of one kernel: SlideStd / Slide4 below) ----
@@ -10,7 +11,7 @@
 // halves of the lane's words, then the lock-step survivor loop -- eight vector instructions and ONE read of the
 // 2^SLIDE_BITS-bit candidate set in LDS per survivor (chains as shift registers, round 5).  A candidate goes straight to
 // the wave's ring in LDS (the membership compare's lane mask + mbcnt, no atomics; the one-level form notes it in a register and appends a trip's notes at once, round 7); the exact reference rule (verify_lap_any, syndrome tables read
-// through L2; the one-level form's syndrome tables in LDS, round 8) runs on ring batches of up to 64.  The ring and those 2.5 KiB are the only LDS besides the set, so TWO workgroups
+// through L2; the one-level form's syndrome tables in LDS, round 8; its pattern look-up sent at a trip's end and read in the next trip, round 9) runs on ring batches of up to 64.  The ring and those 2.5 KiB are the only LDS besides the set, so TWO workgroups
 // fit a CU: 2 x 768 threads = 6 waves per SIMD at <= 80 VGPRs (78.5 KiB of LDS each; a wave owns 63 words of a tile of 756).  Measured on one box,
 // 4 GiB, ms per launch (profiles/r03_ab/): one 1024-thread workgroup per CU (4 waves per SIMD) 4.12, 2 x 1024
 // (8 waves, 64 VGPRs, spills outside the loop) 3.82-3.90, 2 x 768 3.59, 2 x 896 / 832 / 704 / 640 (waves that do
@@ -27,6 +28,13 @@
 #define SLIDE_DRAIN_AT 60u                 // 64-entry ring: entries at which a trip end drains it (32 / 48 / 56 / 60: 3.56 / 3.48 / 3.46 / 3.455 ms; round 6 on
                                            // the 63-word kernel: 32 +1.5 %, 40 and 48 nothing -- profiles/r06_scan/ab_b3_drain_threshold.txt)
 #define SLIDE_DRAIN_AT_ORD 40u             // ... of the ordered form (see its drain)
+// The split drain (round 9, profiles/r16_split_drain).  Five rotations of seven builds on one box, ms per launch, parent 2.6152 (its runs 0.5 % apart):
+#ifndef SLIDE_SPLIT_AT
+#define SLIDE_SPLIT_AT 0                   // where the trip BEHIND a drain_issue finishes the batch: 0 = at its head, in front of the filter; 1 = between filter
+#endif                                     // and passes; 2 = at its end, in front of its append.  One slot sent: 2.6026 / 2.6016 / 2.6090; two: 2.5890 / 2.6053 / 2.6055
+#ifndef SLIDE_SPLIT_SLOTS
+#define SLIDE_SPLIT_SLOTS 2                // slots a drain_issue sends per lane: h alone, or h and h + 1 in one 16-byte load (see the figures above)
+#endif
 // Round 6 measured three more forms of this kernel and dropped them (profiles/r06_scan; the source with the switches is kept there as text):
 //   * the fixed passes without compare, scalar OR and branch -- the sign of (set word << index) shifted into a hit register per chain, one look
 //     at the registers behind the last pass, the candidate's record carrying its survivor's ordinal for the drain to turn into an offset:
@@ -58,6 +66,17 @@
 //   measured, the count says <= 0.8 %), the hit queue (0.55 % is its whole cost), the append ranked once per two trips (the first
 //   trip's raw dwords would have to live through the second).  Probing two slots per round trip, and pattern tables of a quarter
 //   to sixteen times the slots, changed nothing: the look-up's 2.5 % is one dependent round trip to the L2 per drain and the loop around it.
+// Round 9 (profiles/r16_split_drain): the drain in two.  Priced first, on the parent: the probe's slot read from LDS instead of the
+//   pattern table in L2 (timing only) -1.9 % (2.6270 -> 2.5762 ms, the parent's three runs 0.27 % apart) and 230 M fewer wave cycles of
+//   SQ_WAIT_ANY per launch = 710 per drain: a drain waits for about two round trips to the L2, not one -- sixty lanes probe at once, two
+//   thirds of them false candidates that read on until an empty slot, and at a load of 0.05 one of them meets a taken slot in nine batches of ten.
+//   Built: a trip end that drains only SENDS the look-up (drain_issue) and the next trip's tile loads leave behind it; the trip behind
+//   it reads the answer (drain, second half).  With one slot sent the gain was 0.4 to 0.6 % wherever the second half ran (head / behind the
+//   filter / end of the trip: the second probe still waited); with slots h and h + 1 sent in one 16-byte load and the second half at
+//   the trip's head -1.0 % in the rotation of all seven forms and, as the tree, 2.6151 -> 2.5762 ms (-1.5 %, every one of six pairs:
+//   -1.1 to -1.9 %; the parent's six runs were 0.9 % apart in that job, so the gain is 1.6 spreads, not the three the round asked for),
+//   SQ_WAIT_ANY 3 075 -> 2 862 M, wave cycles 7 763 -> 7 592 M (-2.2 %, what the LDS switch reached), vector instructions 1 497.96 ->
+//   1 493.17 M (no exec mask around the syndrome and the look-up: lanes without a record send one too).  73 VGPRs for 65 (71 with one slot sent), six waves per SIMD as before.
 // The kernel's two cuts.
 // SlideStd: tables for <= 2 errors (0.3 % of the survivors are members of the set).  Two workgroups per CU around a 2^19-bit set; six
 //   passes run blind, a candidate the ring has no room for is checked in place.
@@ -175,19 +194,87 @@ void scan_slide_kernel(ScanArgs a)
 	CODE_WORD_CLOSURE(TILE_WORDS, LANE_WORDS, code_tile = t);
 	// hits: up to 64 pending records per wave in registers, written 1 KiB at a time behind one counter atomic (scan_core.h)
 	HIT_QUEUE_CLOSURES();
-	auto drain = [&](uint32_t n) {               // the n <= 64 oldest ring entries through the exact rule
+	// One-level form (round 9): the drain in two.  drain_issue, at the trip end: records, windows, syndromes, and the pattern
+	// look-up SENT -- every lane's, also a lane without a record (rec = 0 gives a slot inside the table like any other, and no
+	// exec mask is formed); the ring is free again at once.  drain(p_n, the second half), a trip later (SLIDE_SPLIT_AT): the
+	// slot's answer, the error decode, the LAP and the hits.  Carried per lane: code, the corrected window's high dword (the LAP
+	// is its bits 2 .. 25), the syndrome and the slot in flight; wave-uniform: p_n, the batch's size, 0 = no batch pending (a
+	// batch has an entry).  The two-level form and (placement E) the ordered form drain in one go: drain(n, whole).
+	static_assert(SLIDE_SPLIT_AT >= 0 && SLIDE_SPLIT_AT <= 2, "head, behind the filter, or end of the trip");
+	constexpr bool SPLIT = !CFG::DENSE && !(ORD && SLIDE_SPLIT_AT == 2);     // (E: the ordered form's ranking borrows the ring, which the passes have written to by then)
+	static_assert(!SPLIT || CFG::TWO_ERRORS, "the split drain has no test of a second-level bitmap");
+	uint32_t p_n = 0;
+	uint32_t p_code = 0, p_swhi = 0, p_synlo = 0, p_synhi = 0;
+	uint64_t p_slot = 0, p_slot2 = 0;
+	auto drain_issue = [&](uint32_t n) {
+		u32x4 rec = {0u, 0u, 0u, 0u};
+		if (lane < n)
+			rec = lds_ld4(ring_off + CAND_BYTES * ((q_head + lane) & (RING - 1)));
+		p_code = rec.x;
+		const uint64_t w = ((uint64_t)alignbit(rec.w, rec.z, p_code) << 32) | alignbit(rec.z, rec.y, p_code);   // (shift = the low five bits)
+		uint64_t sw;
+		const uint64_t syn = lap_syndrome2(a, w, sw, SYN3_OFF);
+#if SLIDE_SPLIT_SLOTS == 2
+		{	// slots h and h + 1 in one 16-byte load (the table has one slot behind its end that repeats slot 0: context.cpp)
+			typedef uint64_t slot_pair_t __attribute__((ext_vector_type(2), aligned(8)));
+			const slot_pair_t two = *reinterpret_cast<const slot_pair_t *>(a.t.hslots + hslot_of(a.t, syn));
+			p_slot = two.x;
+			p_slot2 = two.y;
+		}
+#else
+		p_slot = a.t.hslots[hslot_of(a.t, syn)];
+#endif
+		p_swhi = (uint32_t)(sw >> 32);
+		p_synlo = (uint32_t)syn;
+		p_synhi = (uint32_t)(syn >> 32);
+		p_n = n;
+		q_head += n;
+	};
+	const std::false_type whole;
+	const std::true_type second_half;
+	auto drain = [&](uint32_t n, auto half) {    // the n <= 64 oldest ring entries through the exact rule, or the batch drain_issue sent through the rest of it
+		constexpr bool SECOND = decltype(half)::value;
 		bool hit = false;
 		uint32_t stream = 0, lap = 0, nerr = 0;
 		uint64_t offset = 0;
 		u32x4 rec = {0u, 0u, 0u, 0u};
-		if (lane < n)
+		if constexpr (SECOND)
+			rec.x = p_code;
+		else if (lane < n)
 			rec = lds_ld4(ring_off + CAND_BYTES * ((q_head + lane) & (RING - 1)));
 		const uint32_t code = rec.x;
 		const uint64_t word = code_word(code, stream);
 		if (lane < n) {
-			const uint64_t w = ((uint64_t)alignbit(rec.w, rec.z, code) << 32) | alignbit(rec.z, rec.y, code);   // (shift = the low five bits)
-			offset = word * 64 + (code & 63);
-			hit = verify_lap_any<false, CFG::TWO_ERRORS>(a, w, lap, nerr, SYN3_OFF);
+			if constexpr (SECOND) {
+				offset = word * 64 + (code & 63);
+				const uint64_t syn = ((uint64_t)p_synhi << 32) | p_synlo;
+				uint64_t sw = (uint64_t)p_swhi << 32;
+				bool found = true;
+				if (syn) {
+					uint64_t slot = p_slot;
+#if SLIDE_SPLIT_SLOTS == 2
+					if (slot != HSLOT_EMPTY && !hslot_matches(slot, syn))
+						slot = p_slot2;
+#endif
+					if (slot != HSLOT_EMPTY && !hslot_matches(slot, syn)) {      // a displaced pattern (16 slots per pattern: rare): the probe goes on, waiting
+						uint64_t h = hslot_of(a.t, syn) + (SLIDE_SPLIT_SLOTS - 1);
+						do {
+							h = (h + 1) & a.t.hmask;
+							slot = a.t.hslots[h];
+						} while (slot != HSLOT_EMPTY && !hslot_matches(slot, syn));
+					}
+					if (slot == HSLOT_EMPTY)
+						found = false;                    // no pattern -> ac_errors = 0xff -> reject
+					else
+						nerr = slot_errors2(slot, sw);
+				}
+				lap = lap_of(sw);
+				hit = found && (int)nerr <= a.max_err;
+			} else {
+				const uint64_t w = ((uint64_t)alignbit(rec.w, rec.z, code) << 32) | alignbit(rec.z, rec.y, code);   // (shift = the low five bits)
+				offset = word * 64 + (code & 63);
+				hit = verify_lap_any<false, CFG::TWO_ERRORS>(a, w, lap, nerr, SYN3_OFF);
+			}
 		}
 		if constexpr (ORD) {
 			// A drain takes whole trips, so every hit of a segment (tile iteration code >> 12 of this wave) is in this batch: its
@@ -268,7 +355,10 @@ void scan_slide_kernel(ScanArgs a)
 		} else {
 			push_hits(hit, stream, offset, lap, nerr);
 		}
-		q_head += n;
+		if constexpr (SECOND)
+			p_n = 0;
+		else
+			q_head += n;
 	};
 
 	// The tile cursor carries its tile's address along (one 64-bit scalar add per tile; the products stream x pitch and tile x
@@ -341,6 +431,10 @@ void scan_slide_kernel(ScanArgs a)
 	}
 
 	for (uint32_t it = 0; tc[0].stream < a.n_streams; it += TILES) {
+		if constexpr (SPLIT && SLIDE_SPLIT_AT == 0) {
+			if (p_n)
+				drain(p_n, second_half);                      // (still at PRIO_CAND from the trip end)
+		}
 		__builtin_amdgcn_s_setprio(PRIO_FILTER);
 		uint32_t d[TILES][4], m[TILES][2], c[TILES][3];
 		uint32_t c2[TILES][CFG::LEVEL2 ? 3 : 1];                 // (two-level form) the second check stream, positions as c
@@ -674,6 +768,12 @@ void scan_slide_kernel(ScanArgs a)
 		PROF_MARK(0);
 		uint32_t pass_no = 1;
 		if constexpr (!CFG::DENSE) {
+			if constexpr (SPLIT && SLIDE_SPLIT_AT == 1) {
+				if (p_n) {
+					__builtin_amdgcn_s_setprio(PRIO_CAND);
+					drain(p_n, second_half);
+				}
+			}
 			__builtin_amdgcn_s_setprio(PRIO_LOOP);
 #pragma unroll 1
 			for (int k = 0; k < SLIDE_FIXED; k++) { // practically every trip needs these (TILES * 128 chains of ~4 survivors)
@@ -682,14 +782,24 @@ void scan_slide_kernel(ScanArgs a)
 				pass_no++;
 			}
 			sparse_tail();
+			if constexpr (SPLIT && SLIDE_SPLIT_AT == 2) {
+				if (p_n) {
+					__builtin_amdgcn_s_setprio(PRIO_CAND);
+					drain(p_n, second_half);
+				}
+			}
 			append_noted();
 			PROF_MARK(pass_no < 13 ? pass_no : 13);
 			__builtin_amdgcn_s_setprio(PRIO_CAND);
 			PROF_MARK(16);
 			// (ORD: drained at 40, which costs nothing measurable -- profiles/r06_scan -- and leaves every trip room for 24 candidates
 			// where it has 4.5: a hit verified in place, outside the drains, then only happens to streams made of sync words)
-			if (q_tail - q_head >= (RING == 64 ? (ORD ? SLIDE_DRAIN_AT_ORD : SLIDE_DRAIN_AT) : 64u))
-				drain(q_tail - q_head > 64 ? 64 : q_tail - q_head);
+			if (q_tail - q_head >= (RING == 64 ? (ORD ? SLIDE_DRAIN_AT_ORD : SLIDE_DRAIN_AT) : 64u)) {
+				if constexpr (SPLIT)
+					drain_issue(q_tail - q_head > 64 ? 64 : q_tail - q_head);       // (the batch before it was finished in this trip)
+				else
+					drain(q_tail - q_head > 64 ? 64 : q_tail - q_head, whole);
+			}
 		} else {
 			// The pass loop is left when the ring gets short of room (a.ring_margin entries: what a pass may add), drained at
 			// the one site behind it and re-entered; candidates that still find no room are checked in place.  (With the
@@ -711,7 +821,7 @@ void scan_slide_kernel(ScanArgs a)
 				__builtin_amdgcn_s_setprio(PRIO_CAND);
 				PROF_MARK(16);
 				if (more || q_tail - q_head >= 32u)
-					drain(q_tail - q_head > 64 ? 64 : q_tail - q_head);
+					drain(q_tail - q_head > 64 ? 64 : q_tail - q_head, whole);
 				if (!more)
 					break;
 			}
@@ -729,8 +839,18 @@ void scan_slide_kernel(ScanArgs a)
 		}
 		PROF_MARK(19);
 	}
-	while (q_tail != q_head)
-		drain(q_tail - q_head > 64 ? 64 : q_tail - q_head);
+	if constexpr (SPLIT) {
+		for (;;) {                                   // the batch the last trip sent, then what is left in the ring
+			if (p_n)
+				drain(p_n, second_half);
+			if (q_tail == q_head)
+				break;
+			drain_issue(q_tail - q_head > 64 ? 64 : q_tail - q_head);
+		}
+	} else {
+		while (q_tail != q_head)
+			drain(q_tail - q_head > 64 ? 64 : q_tail - q_head, whole);
+	}
 	flush_hits();
 #ifdef SCAN_PROFILE
 	if (lane < 32)
