@@ -745,12 +745,14 @@ int btbbx_le_seed_device(const btbbx_le_pkt *d_adv, const uint32_t *d_adv_count,
  *      MAP_UPDATE / PARAM_UPDATE only for a VALID update that is not ignored; any other update stays CONTROL.
  * LIMITS: the interval after a parameter update is not followed by this stage (btbbx_le_span_device below finds the new window's anchor and goes on);
  * LL_PAUSE_ENC is not tracked; a first event seen only through a packet longer than unit_bits - jitter_bits - 230 bits behind
- * its missed anchor may get c_f one too large; a request whose connection never shows seeds nothing. */
+ * its missed anchor may get c_f one too large; a request whose connection never shows seeds nothing; an update behind
+ * LL_START_ENC_REQ is OPAQUE here and read only by btbbx_le_keyed_epoch_device below, behind the decryption stage. */
 #define BTBBX_LE_FOLLOW_SEEDED     1u   /* btbbx_le_follow.flags */
 #define BTBBX_LE_FOLLOW_COUNTED    2u   /* some event is not BEFORE */
 #define BTBBX_LE_FOLLOW_STOPPED    4u   /* stop is finite */
 #define BTBBX_LE_FOLLOW_TERMINATED 8u
 #define BTBBX_LE_FOLLOW_ENCRYPTED  16u
+#define BTBBX_LE_FOLLOW_DECRYPTED  128u /* the keyed entries alone: a control PDU behind LL_START_ENC_REQ was read as plaintext */
 #define BTBBX_LE_STATE_COUNTED 0u       /* btbbx_le_follow_pkt.state */
 #define BTBBX_LE_STATE_BEFORE  1u
 #define BTBBX_LE_STATE_BEYOND  2u
@@ -863,8 +865,9 @@ int64_t btbbx_le_epoch_host(const uint64_t *words, uint64_t n_words, uint64_t pi
  * max_updates, an event of span 0 that the follow stage leaves COUNTED carries the same values.
  * LIMITS: the first counter of a later span is exact while WinSize' * unit_bits + 4 * jitter_bits < P_(s+1) and the events
  * deviate by at most jitter_bits; it also inherits A_L's deviation, and any drift over I_s - c_L intervals when the events just
- * before the instant are missed.  An update whose PDU is seen only behind LL_START_ENC_REQ is never read; LL_PAUSE_ENC is not
- * tracked; more than 16 updates are not followed. */
+ * before the instant are missed.  An update whose PDU is seen only behind LL_START_ENC_REQ is never read (but by
+ * btbbx_le_keyed_span_device below, behind the decryption stage); LL_PAUSE_ENC is not tracked; more than 16 updates are not
+ * followed. */
 #define BTBBX_LE_SPAN_CAPPED   32u      /* btbbx_le_span.flags, beside the BTBBX_LE_FOLLOW_* values */
 #define BTBBX_LE_SPAN_REFUSED  64u
 #define BTBBX_LE_STATE_GAP     3u       /* btbbx_le_span_pkt.state, beside COUNTED / BEFORE / BEYOND */
@@ -1092,7 +1095,8 @@ int64_t btbbx_le_data_host(const uint64_t *words, uint64_t n_words, uint64_t pit
  *      other member these are 0.  opcode = plaintext octet 0 of a VERIFIED member with llid == 3, else 0xff.
  * LIMITS: a connection whose LL_ENC_REQ / LL_ENC_RSP are not in the capture stays unarmed; LL_PAUSE_ENC and a second encryption
  * start are not tracked; a lost packet shows as skew and is found only within window; the roles' limits are the data stage's; an
- * update PDU decrypted here is not fed back to the follow or span stage. */
+ * update PDU decrypted here is not fed back to the follow or span stage (btbbx_le_keyed_epoch_device and
+ * btbbx_le_keyed_span_device below read it from this stage's records). */
 #define BTBBX_LE_CRYPT_CLEAR    0u   /* btbbx_le_crypt_pkt.state */
 #define BTBBX_LE_CRYPT_VERIFIED 1u
 #define BTBBX_LE_CRYPT_FAILED   2u
@@ -1155,6 +1159,80 @@ int64_t btbbx_le_crypt_host(const uint64_t *words, uint64_t n_words, uint64_t pi
 			    const uint8_t *keys, uint32_t n_keys, uint32_t window, btbbx_le_crypt *crypt, btbbx_le_crypt_pkt *crypt_pkts,
 			    btbbx_le_data_pkt *plain_pkts, btbbx_le_msg *msgs, uint64_t msg_cap, uint64_t *n_msgs_out, uint8_t *bytes,
 			    uint64_t byte_cap, uint64_t *n_bytes_out);
+
+/* ---- Keyed LE following: map and parameter updates sent encrypted ---------------------------
+ * The follow stage and the span stage stop reading control PDUs at the first LL_START_ENC_REQ: every CONTROL member behind it is
+ * OPAQUE, and a paired connection sends nearly all its LL_CHANNEL_MAP_IND and LL_CONNECTION_UPDATE_IND PDUs there.  The KEYED form
+ * of either stage has the same rules and the same output records, with the control PDUs the decryption stage VERIFIED read as
+ * plaintext.  It changes nothing of its input.
+ *
+ * The input is btbbx_le_epoch_device's / btbbx_le_span_device's plus three arrays: d_data_pkts, the data stage's, read for role;
+ * d_crypt, the decryption stage's, read for session_key, iv and flags; d_crypt_pkts, read for state, counter and counter_hi.
+ * d_data_pkts and d_crypt_pkts are parallel to the sorted candidate list, d_crypt to conns.  Members, ranks, events, slots and
+ * ENC_START -- the first CONTROL member in time order that reads in the clear as opcode 5 and length 1 -- are the follow stage's.
+ *   1. READABLE.  Member i of connection g with header length L is READABLE iff d_crypt[g].flags has KEYED,
+ *      d_crypt_pkts[i].state == BTBBX_LE_CRYPT_VERIFIED, (header0 & 3) == 3 and L >= 5, d_data_pkts[i].role is CENTRAL or
+ *      PERIPHERAL, and g has an ENC_START and i's rank is above its rank.  (The decryption stage gives VERIFIED to no other kind of
+ *      control member; the other conditions guard a list from elsewhere.)  A member that fails one of them is treated as in the
+ *      unkeyed stage.
+ *   2. PLAINTEXT.  The nonce is the decryption stage's rule 5's with c = counter | (uint64_t)counter_hi << 32, dir = 1 for
+ *      CENTRAL and 0 for PERIPHERAL, iv = d_crypt[g].iv.  S_1 = AES-128(session_key, 0x01 | nonce | 00 01).  L' = L - 4.  Plain
+ *      octet j = (payload octet j as follow rule 3 reads it: dewhitening continued behind the header, zeros beyond the stream's
+ *      end) ^ S_1[j] for j < min(L', 12).  The MIC's octets are never read as payload, and the MIC is not checked again.
+ *   3. PARSING.  A READABLE member is CONTROL with length L' and those octets; follow rule 3 and span rule 3 parse it with L' in
+ *      the length's place (map update: opcode 1 and L' 8; parameter update: opcode 0 and L' 12; TERMINATE: opcode 2 and L' 2).  It
+ *      is never ENC_START, whatever its opcode.  A CONTROL member above ENC_START that is not READABLE stays OPAQUE with opcode
+ *      0xff: FAILED, SKIPPED and SHORT members, the CLEAR members of a connection that is not ARMED, retransmissions.
+ *   4. REST.  Everything else is follow rules 1-7 and span rules 1-7: n_control, stop, instants, epochs, spans, gaps, tallies,
+ *      the algorithm.  BTBBX_LE_FOLLOW_DECRYPTED (128, the free bit of btbbx_le_follow.flags and btbbx_le_span.flags beside CAPPED
+ *      and REFUSED) is set iff the connection is SEEDED and has a READABLE member.  The records are btbbx_le_follow, _follow_pkt,
+ *      _span, _span_pkt and _span_rec; every byte of them is written, nothing behind them.
+ *   5. EQUALITIES.  (a) If no member is READABLE, every output byte equals the unkeyed entry's on the same input.  (b) The keyed
+ *      span stage with max_updates == 0 relates to the keyed follow stage as the unkeyed ones relate.
+ * LIMITS: LL_PAUSE_ENC and a second encryption start are not tracked; a PDU the decryption stage did not VERIFY is not read -- a
+ * lost packet beyond window, a role UNKNOWN in a split event's tail, a key that is not in the table.
+ *
+ * Each _device entry takes the unkeyed entry's arguments with d_data_pkts, d_crypt, d_crypt_pkts behind d_seeds, and makes its
+ * promises.  d_scratch: the unkeyed stage's bytes, 16 per candidate and 2 bits per candidate.  The count of launches equals the
+ * unkeyed entry's: the kernels that read a payload or say a PDU's kind are replaced by keyed ones and none is added, so the count
+ * depends on conn_cap and max_updates as there and never on the data.  BTBBX_E_ARG, before any launch: the unkeyed entry's
+ * conditions, a new pointer that is null or misaligned (d_crypt 8 bytes, d_crypt_pkts 16, d_data_pkts 4).  cand_cap == 0 or
+ * conn_cap == 0 succeeds and writes nothing.  Asynchronous on hip_stream; nothing is read back. */
+size_t btbbx_le_keyed_epoch_scratch_bytes(uint32_t cand_cap, uint32_t conn_cap);
+int btbbx_le_keyed_epoch_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				const uint16_t *d_phys_channel,
+				const btbbx_le_cand *d_cands, const uint32_t *d_cand_count, uint32_t cand_cap,
+				const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
+				const btbbx_le_track *d_tracks, const btbbx_le_track_pkt *d_pkts, const btbbx_le_seed *d_seeds,
+				const btbbx_le_data_pkt *d_data_pkts, const btbbx_le_crypt *d_crypt, const btbbx_le_crypt_pkt *d_crypt_pkts,
+				uint32_t unit_bits, uint32_t jitter_bits,
+				btbbx_le_follow *d_follows, btbbx_le_follow_pkt *d_follow_pkts,
+				void *d_scratch, size_t scratch_bytes, void *hip_stream);
+size_t btbbx_le_keyed_span_scratch_bytes(uint32_t cand_cap, uint32_t conn_cap, uint32_t max_updates);
+int btbbx_le_keyed_span_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			       const uint16_t *d_phys_channel,
+			       const btbbx_le_cand *d_cands, const uint32_t *d_cand_count, uint32_t cand_cap,
+			       const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
+			       const btbbx_le_track *d_tracks, const btbbx_le_track_pkt *d_pkts, const btbbx_le_seed *d_seeds,
+			       const btbbx_le_data_pkt *d_data_pkts, const btbbx_le_crypt *d_crypt, const btbbx_le_crypt_pkt *d_crypt_pkts,
+			       uint32_t unit_bits, uint32_t jitter_bits, uint32_t max_updates,
+			       btbbx_le_span *d_spans, btbbx_le_span_pkt *d_span_pkts, btbbx_le_span_rec *d_span_recs,
+			       void *d_scratch, size_t scratch_bytes, void *hip_stream);
+
+/* Host wrapper: btbbx_le_epoch_host's chain -- the advertising scan, discovery, tracking and seed -- then the data stage, the
+ * decryption stage under keys / n_keys / window (as btbbx_le_crypt_host takes them) and the keyed span stage, all on one stream.
+ * btbbx_le_span_host's arguments and return value, with keys, n_keys, window, crypt and crypt_pkts behind seeds; crypt: conn_cap
+ * records; crypt_pkts and span_pkts (either may be NULL): cand_cap records.  The data stage's and the decryption stage's messages
+ * and octets are not kept.  BTBBX_E_ARG: the span wrapper's conditions and the decryption wrapper's: keys NULL, crypt NULL with
+ * conn_cap != 0, n_keys outside 1..64, window outside 1..32. */
+int64_t btbbx_le_keyed_span_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				 uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+				 btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+				 uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+				 int adv_errors, btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_seed *seeds,
+				 const uint8_t *keys, uint32_t n_keys, uint32_t window, btbbx_le_crypt *crypt,
+				 btbbx_le_crypt_pkt *crypt_pkts, uint32_t max_updates, btbbx_le_span *spans,
+				 btbbx_le_span_pkt *span_pkts, btbbx_le_span_rec *span_recs);
 
 /* ---- LE legacy pairing key recovery: SMP exchange, TK search, STK --------------------------
  * Behind the data stage or the decryption stage, on the device: for every connection the Security Manager exchange among its

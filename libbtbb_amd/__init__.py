@@ -131,6 +131,7 @@ assert LE_SEED_DTYPE.itemsize == 56 and LE_FOLLOW_DTYPE.itemsize == 48 and LE_FO
 # LE following through connection parameter updates (include/btbbx.h btbbx_le_span / btbbx_le_span_pkt / btbbx_le_span_rec; le_span.h
 # checks the C layout with static_asserts); the flags and states stand beside the LE_FOLLOW_* / LE_STATE_* values
 LE_SPAN_CAPPED, LE_SPAN_REFUSED = 32, 64
+LE_FOLLOW_DECRYPTED = 128       # btbbx_le_follow.flags and btbbx_le_span.flags, set by the keyed entries alone
 LE_STATE_GAP = 3
 LE_SPAN_DTYPE = np.dtype([("map", "<u8"), ("counter_first", "<u4"), ("stop", "<u4"), ("n_before", "<u4"), ("n_on", "<u4"),
                           ("n_off", "<u4"), ("n_beyond", "<u4"), ("n_gap", "<u4"), ("n_control", "<u4"), ("n_map_updates", "<u4"),
@@ -292,6 +293,14 @@ SIGNATURES = {
                                         _vp, _vp, _vp, _u32, _vp, _vp, _u64, _vp, _vp, C.c_size_t, _vp]),
     "btbbx_le_crypt_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
                                         _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "btbbx_le_keyed_epoch_scratch_bytes": (C.c_size_t, [_u32, _u32]),
+    "btbbx_le_keyed_epoch_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u32,
+                                               _u32, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "btbbx_le_keyed_span_scratch_bytes": (C.c_size_t, [_u32, _u32, _u32]),
+    "btbbx_le_keyed_span_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u32,
+                                              _u32, _u32, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "btbbx_le_keyed_span_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
+                                             C.c_int, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
     "btbbx_le_pair_scratch_bytes": (C.c_size_t, [_u32]),
     "btbbx_le_pair_device": (C.c_int, [_vp, _u32, _vp, _vp, _vp, _u32, _vp, _u64, _u32, _vp, _vp, _u32, _vp, _vp, C.c_size_t, _vp]),
     "btbbx_le_pair_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
@@ -790,6 +799,65 @@ def le_crack(words, search_bits, phys_channels, tk_limit=LE_PAIR_MAX_TK, key_cap
     if not found:
         return pair, None
     return pair, le_decrypt(words, search_bits, phys_channels, pair[6][:found], window=window, **kw)
+
+
+def le_span_keyed(words, search_bits, phys_channels, keys, window=8, max_updates=4, max_len=27, min_count=2, n_streams=1,
+                  pitch_words=None, n_words=None, unit_bits=1250, ifs_bits=200, jitter_bits=50, flags=LE_TRACK_REMAP, adv_errors=0,
+                  conn_cap=1 << 12, cand_cap=1 << 20, truncate=False):
+    """le_span's chain with the data stage, the decryption stage under `keys` and `window` (le_decrypt's) and the KEYED span stage
+    behind the seeds (include/btbbx.h btbbx_le_keyed_span_device): the channel map and connection parameter updates a connection
+    sends encrypted are read as plaintext and put in force.  le_span's other parameters.  max_len is not raised: an encrypted PDU is
+    4 octets longer than its plaintext, so pass max_len >= 31 for a connection with 27-octet PDUs (an encrypted parameter update
+    itself is 16 octets long) and 255 with data length extension.
+    Returns (conns, cands, tracks, pkts, seeds, crypt, crypt_pkts, spans, span_pkts, span_recs): le_span's arrays with the
+    LE_CRYPT_DTYPE records parallel to conns and the LE_CRYPT_PKT_DTYPE records parallel to cands behind the seeds."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if pitch_words is None:
+        pitch_words = len(words) // n_streams
+    if n_words is None:
+        n_words = pitch_words
+    assert n_words <= pitch_words and (n_streams - 1) * pitch_words + n_words <= len(words)
+    phys = np.ascontiguousarray(np.broadcast_to(np.asarray(phys_channels, dtype=np.uint16), (n_streams,)))
+    if not isinstance(keys, np.ndarray):
+        keys = np.frombuffer(b"".join(bytes(k) for k in keys), np.uint8)
+    keys = np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1, 16)
+    per = min(int(max_updates), 16) + 1
+    conns = np.empty(max(conn_cap, 1), dtype=LE_CONN_DTYPE)
+    tracks = np.empty(max(conn_cap, 1), dtype=LE_TRACK_DTYPE)
+    seeds = np.empty(max(conn_cap, 1), dtype=LE_SEED_DTYPE)
+    crypt = np.empty(max(conn_cap, 1), dtype=LE_CRYPT_DTYPE)
+    spans = np.empty(max(conn_cap, 1), dtype=LE_SPAN_DTYPE)
+    span_recs = np.empty((max(conn_cap, 1), per), dtype=LE_SPAN_REC_DTYPE)
+    cands = np.empty(max(cand_cap, 1), dtype=LE_CAND_DTYPE)
+    pkts = np.empty(max(cand_cap, 1), dtype=LE_TRACK_PKT_DTYPE)
+    crypt_pkts = np.empty(max(cand_cap, 1), dtype=LE_CRYPT_PKT_DTYPE)
+    span_pkts = np.empty(max(cand_cap, 1), dtype=LE_SPAN_PKT_DTYPE)
+    n_cands = C.c_uint64(0)
+    n = check(lib().btbbx_le_keyed_span_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, _ptr(phys), max_len, min_count,
+                                             _ptr(conns), conn_cap, _ptr(cands), cand_cap, C.byref(n_cands), unit_bits, ifs_bits,
+                                             jitter_bits, flags, adv_errors, _ptr(tracks), _ptr(pkts), _ptr(seeds), _ptr(keys), len(keys),
+                                             window, _ptr(crypt), _ptr(crypt_pkts), max_updates, _ptr(spans), _ptr(span_pkts),
+                                             _ptr(span_recs)), "btbbx_le_keyed_span_host")
+    if (n > conn_cap or n_cands.value > cand_cap) and not truncate:
+        raise BtbbError("buffers too small: %d connections > %d or %d candidates > %d" % (n, conn_cap, n_cands.value, cand_cap))
+    nc, nk = min(n, conn_cap), min(n_cands.value, cand_cap)
+    return (conns[:nc].copy(), cands[:nk].copy(), tracks[:nc].copy(), pkts[:nk].copy(), seeds[:nc].copy(), crypt[:nc].copy(),
+            crypt_pkts[:nk].copy(), spans[:nc].copy(), span_pkts[:nk].copy(), span_recs[:nc].copy())
+
+
+def le_crack_span(words, search_bits, phys_channels, tk_limit=LE_PAIR_MAX_TK, key_cap=LE_PAIR_MAX_KEYS, window=8, max_updates=4,
+                  adv_errors=0, **kw):
+    """le_pair, then le_span_keyed under the short-term keys it recovered, as le_crack composes pairing and decryption: capture in,
+    every connection followed through the updates it sends encrypted, no key given.  kw: what both take (max_len, min_count,
+    n_streams, pitch_words, n_words, the timing, flags, conn_cap, cand_cap, truncate); msg_cap and byte_cap go to le_pair alone.
+    Returns (pair, keyed): le_pair's tuple and le_span_keyed's.  When no key was found nothing is raised and keyed is None."""
+    pair = le_pair(words, search_bits, phys_channels, tk_limit=tk_limit, key_cap=key_cap, adv_errors=adv_errors, **kw)
+    found = min(pair[7], key_cap)
+    if not found:
+        return pair, None
+    kw = {k: v for k, v in kw.items() if k not in ("msg_cap", "byte_cap")}
+    return pair, le_span_keyed(words, search_bits, phys_channels, pair[6][:found], window=window, max_updates=max_updates,
+                               adv_errors=adv_errors, **kw)
 
 
 class DeviceBuffer:

@@ -304,6 +304,7 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_epoch_init_kernel(co
 
 // ---- 2. slots and control PDUs ----------------------------------------------------------------------------------------------
 
+// (le_keyed.h has this kernel's keyed form, le_keyed_slot_kernel, and this payload reader as lk_octets: a change here is made there too)
 extern "C" __global__ __launch_bounds__(LE_THREADS) void le_epoch_slot_kernel(const uint64_t *words, uint64_t n_words, uint64_t pitch_words,
 									      uint32_t n_streams, const btbbx_le_cand *cands,
 									      const btbbx_le_track_pkt *pkts, const btbbx_le_conn *conns,
@@ -359,6 +360,7 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_epoch_slot_kernel(co
 // ---- 3. events --------------------------------------------------------------------------------------------------------------
 
 // the member in front of which its connection's time order changes the event stores anchor | channel << 56 and the connection
+// (le_keyed.h has this kernel's keyed form, le_keyed_open_kernel: a change here is made there too)
 extern "C" __global__ __launch_bounds__(LE_THREADS) void le_epoch_open_kernel(const btbbx_le_cand *cands, const btbbx_le_track_pkt *pkts,
 									      const btbbx_le_conn *conns, const uint32_t *params,
 									      const uint32_t *slot, uint64_t *anchor, uint32_t *econn)
@@ -846,6 +848,7 @@ __device__ __forceinline__ void lf_pkt_event(uint4 ev, const uint8_t *algorithm,
 	}
 }
 
+// (le_keyed.h has this kernel's keyed form, le_keyed_pkt_epoch_kernel: a change here is made there too)
 extern "C" __global__ __launch_bounds__(LE_THREADS) void le_epoch_pkt_kernel(const btbbx_le_cand *cands, const btbbx_le_track_pkt *pkts,
 									     const btbbx_le_conn *conns, const btbbx_le_seed *seeds,
 									     const uint32_t *params, const uint4 *ctl, const uint4 *evres,
@@ -917,18 +920,36 @@ static LfBufs le_follow_bufs(void *d_scratch, uint32_t cap, uint32_t conn_cap)
 	return B;
 }
 
+// How a run reads its control PDUs: the kernels that read a payload or say a PDU's kind.  This one reads them in the clear, with
+// the kernels above.  le_keyed.h has the one that reads behind LL_START_ENC_REQ: the same number of launches, other kernels
+struct LfReadClear {
+	void tables(const LfBufs &B, const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, const btbbx_le_cand *d_cands,
+		    const btbbx_le_track_pkt *d_pkts, const btbbx_le_conn *d_conns, dim3 per_cand, hipStream_t q) const
+	{
+		const dim3 wg(LE_THREADS);
+		hipLaunchKernelGGL(le_epoch_slot_kernel, per_cand, wg, 0, q, d_words, n_words, pitch_words, n_streams, d_cands, d_pkts, d_conns, B.params,
+				   B.slot, B.ctl, B.work);
+		hipLaunchKernelGGL(le_epoch_open_kernel, per_cand, wg, 0, q, d_cands, d_pkts, d_conns, B.params, B.slot, B.anchor, B.econn);
+	}
+	void follow_pkts(const LfBufs &B, const btbbx_le_cand *d_cands, const btbbx_le_track_pkt *d_pkts, const btbbx_le_conn *d_conns,
+			 const btbbx_le_seed *d_seeds, btbbx_le_follow *d_follows, btbbx_le_follow_pkt *d_fpkts, dim3 per_cand, hipStream_t q) const
+	{
+		hipLaunchKernelGGL(le_epoch_pkt_kernel, per_cand, dim3(LE_THREADS), 0, q, d_cands, d_pkts, d_conns, d_seeds, B.params, B.ctl, B.evres,
+				   B.work, d_follows, d_fpkts);
+	}
+};
+
 // kernels 1-3: the tables every later pass of this stage and of the span stage reads
+template <class Read>
 static void le_follow_open(const LfBufs &B, const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
 			   const btbbx_le_cand *d_cands, const uint32_t *d_count, uint32_t cap, const btbbx_le_conn *d_conns,
-			   const uint32_t *d_conn_count, uint32_t conn_cap, const btbbx_le_track_pkt *d_pkts, hipStream_t q)
+			   const uint32_t *d_conn_count, uint32_t conn_cap, const btbbx_le_track_pkt *d_pkts, hipStream_t q, const Read &read)
 {
 	const dim3 per_cand((cap + LE_THREADS - 1) / LE_THREADS), wg(LE_THREADS);
 	const uint32_t init_grid = (uint32_t)(((uint64_t)std::max(cap, conn_cap) + LE_THREADS - 1) / LE_THREADS);
 	hipLaunchKernelGGL(le_epoch_init_kernel, dim3(init_grid), wg, 0, q, d_count, cap, d_conn_count, conn_cap, B.params, B.uparams, B.slot, B.econn,
 			   B.work);
-	hipLaunchKernelGGL(le_epoch_slot_kernel, per_cand, wg, 0, q, d_words, n_words, pitch_words, n_streams, d_cands, d_pkts, d_conns, B.params,
-			   B.slot, B.ctl, B.work);
-	hipLaunchKernelGGL(le_epoch_open_kernel, per_cand, wg, 0, q, d_cands, d_pkts, d_conns, B.params, B.slot, B.anchor, B.econn);
+	read.tables(B, d_words, n_words, pitch_words, n_streams, d_cands, d_pkts, d_conns, per_cand, q);
 }
 
 // the update list a list kernel left in side 0 of the sort's buffers, sorted stably by I -- least significant first: the 48 bits an
@@ -944,14 +965,16 @@ static const uint64_t *le_follow_sort_updates(const LfBufs &B, uint32_t cap, uin
 }
 
 // the launches of one run: 12 of this stage's kernels, 3 of the tracking's scans, and 3 per radix pass (6 over I, 1 to 4 over conn_cap)
+// (`read` chooses three of them: the slot, open and packet kernels, or le_keyed.h's in their places)
+template <class Read = LfReadClear>
 static int le_follow_launch(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, const btbbx_le_cand *d_cands,
 			    const uint32_t *d_count, uint32_t cap, const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
 			    const btbbx_le_track_pkt *d_pkts, const btbbx_le_seed *d_seeds, uint32_t unit_bits, uint32_t jitter_bits,
-			    btbbx_le_follow *d_follows, btbbx_le_follow_pkt *d_fpkts, void *d_scratch, hipStream_t q)
+			    btbbx_le_follow *d_follows, btbbx_le_follow_pkt *d_fpkts, void *d_scratch, hipStream_t q, const Read &read = Read())
 {
 	const LfBufs B = le_follow_bufs(d_scratch, cap, conn_cap);
 	const dim3 per_cand((cap + LE_THREADS - 1) / LE_THREADS), per_tile(B.tiles_n), wg(LE_THREADS);
-	le_follow_open(B, d_words, n_words, pitch_words, n_streams, d_cands, d_count, cap, d_conns, d_conn_count, conn_cap, d_pkts, q);
+	le_follow_open(B, d_words, n_words, pitch_words, n_streams, d_cands, d_count, cap, d_conns, d_conn_count, conn_cap, d_pkts, q, read);
 	hipLaunchKernelGGL(le_epoch_step_kernel, per_tile, wg, 0, q, B.anchor, B.econn, d_conns, d_seeds, B.params, unit_bits, jitter_bits, B.step,
 			   B.tiles64);
 	hipLaunchKernelGGL(le_track_prefix64_kernel, dim3(1), wg, 0, q, B.tiles64, B.tiles_n);
@@ -968,8 +991,7 @@ static int le_follow_launch(const uint64_t *d_words, uint64_t n_words, uint64_t 
 			   B.s_map, jitter_bits, B.evres, B.work);
 	hipLaunchKernelGGL(le_epoch_verdict_kernel, dim3((conn_cap + LE_THREADS - 1) / LE_THREADS), wg, 0, q, d_conns, d_seeds, B.params, B.uparams,
 			   B.step, s_conn, B.s_map, B.evres, B.work, d_follows);
-	hipLaunchKernelGGL(le_epoch_pkt_kernel, per_cand, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, B.params, B.ctl, B.evres, B.work, d_follows,
-			   d_fpkts);
+	read.follow_pkts(B, d_cands, d_pkts, d_conns, d_seeds, d_follows, d_fpkts, per_cand, q);
 	HIP_TRY(hipGetLastError());
 	return BTBBX_OK;
 }

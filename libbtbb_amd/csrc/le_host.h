@@ -447,14 +447,15 @@ struct LxHostTail {
 	size_t scratch, crypt, cpkts, ppkts, msgs, counts, bytes, keys, total;
 };
 
-static LxHostTail le_crypt_host_layout(uint32_t dev_cap, uint32_t dev_conns, uint32_t n_keys, const LdtHostTail &T)
+// (records: with the stage's own records crypt and cpkts; a wrapper that keeps them among its outputs lays none out here)
+static LxHostTail le_crypt_host_layout(uint32_t dev_cap, uint32_t dev_conns, uint32_t n_keys, const LdtHostTail &T, bool records = true)
 {
 	LxHostTail C;
 	size_t at = le_data_host_layout(dev_cap, dev_conns, 0, 0).total;
 	auto take = [&](size_t bytes) { const size_t here = at; at += ld_up(bytes); return here; };
 	C.scratch = take(le_crypt_layout(dev_cap, dev_conns, n_keys).total);
-	C.crypt = take((size_t)dev_conns * sizeof(btbbx_le_crypt));
-	C.cpkts = take((size_t)dev_cap * sizeof(btbbx_le_crypt_pkt));
+	C.crypt = take(records ? (size_t)dev_conns * sizeof(btbbx_le_crypt) : 0);
+	C.cpkts = take(records ? (size_t)dev_cap * sizeof(btbbx_le_crypt_pkt) : 0);
 	C.ppkts = take((size_t)dev_cap * sizeof(btbbx_le_data_pkt));
 	C.msgs = take((size_t)T.msg_cap * sizeof(btbbx_le_msg));
 	C.counts = take(256);
@@ -572,7 +573,7 @@ static int le_follow_host_adv(const LeHostArgs &a, const LeHostRun &r, uint64_t 
 
 // The chain of btbbx_le_epoch_host and btbbx_le_span_host: the advertising scan, the tracking, the seed stage and the wrapper's
 // last stage -- last(r, pitch_words, d_seeds, d_scratch, d_out): its launches --, whose scratch takes last_scratch(dev_cap, dev_conns)
-// bytes.  outs: the last stage's outputs (at most three; src is not read): their device records stand behind the scratch in this
+// bytes.  outs: the last stage's outputs (at most five; src is not read): their device records stand behind the scratch in this
 // order, dev_conns or dev_cap of them each (or `fixed` of them), and d_out[o] is where those of outs[o] begin.
 // A failed launch does not end the call at once: the stream is synchronised and a spilled advertising block freed first
 template <class Scratch, class Last>
@@ -606,8 +607,8 @@ static int64_t le_follow_host_chain(const LeHostArgs &a, int adv_errors, btbbx_l
 	}
 	void *spill = nullptr;                                  // a second advertising block, when the first was too small
 	btbbx_le_seed *d_seeds = (btbbx_le_seed *)r.own;
-	LeHostOut all[4] = {{seeds, d_seeds, sizeof(btbbx_le_seed), false}};
-	char *d_out[3] = {nullptr, nullptr, nullptr};
+	LeHostOut all[6] = {{seeds, d_seeds, sizeof(btbbx_le_seed), false}};
+	char *d_out[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 	for (int o = 0; o < n_outs; o++) {
 		d_out[o] = r.own + records(r.dev_cap, r.dev_conns, o);
 		all[o + 1] = {outs[o].dst, d_out[o], outs[o].size, outs[o].per_cand, outs[o].fixed};
@@ -670,6 +671,59 @@ extern "C" int64_t btbbx_le_span_host(const uint64_t *words, uint64_t n_words, u
 			return le_span_launch(r.d_words, n_words, pitch, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count,
 					      r.dev_conns, r.d_pkts, d_seeds, unit_bits, jitter_bits, max_updates, (btbbx_le_span *)d_out[0],
 					      (btbbx_le_span_pkt *)d_out[1], (btbbx_le_span_rec *)d_out[2], d_scratch, r.q);
+		});
+}
+
+// the data stage, the decryption stage and the keyed span stage behind the seed stage
+extern "C" int64_t btbbx_le_keyed_span_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+					    uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+					    btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+					    uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+					    int adv_errors, btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_seed *seeds,
+					    const uint8_t *keys, uint32_t n_keys, uint32_t window, btbbx_le_crypt *crypt,
+					    btbbx_le_crypt_pkt *crypt_pkts, uint32_t max_updates, btbbx_le_span *spans,
+					    btbbx_le_span_pkt *span_pkts, btbbx_le_span_rec *span_recs)
+{
+	const LeHostArgs a = LE_HOST_ARGS("btbbx_le_keyed_span_host");
+	if (max_updates > LS_MAX_UPDATES) {
+		set_error("%s: max_updates must be 0..%u", a.who, LS_MAX_UPDATES);
+		return BTBBX_E_ARG;
+	}
+	const int rc = le_crypt_check_keys(a.who, n_keys, window);
+	if (rc)
+		return rc;
+	// the data stage's and the decryption stage's parts as btbbx_le_crypt_host lays them out (no message, no octet is kept; the
+	// decryption stage's records are outputs here and stand with them), then the keyed span stage's scratch
+	const auto crypt_tail = [&](uint32_t cap, uint32_t k) {
+		return le_crypt_host_layout(cap, k, n_keys, le_data_host_layout(cap, k, 0, 0), false);
+	};
+	const LeHostOut outs[] = {{crypt, nullptr, sizeof(btbbx_le_crypt), false}, {crypt_pkts, nullptr, sizeof(btbbx_le_crypt_pkt), true},
+				  {spans, nullptr, sizeof(btbbx_le_span), false}, {span_pkts, nullptr, sizeof(btbbx_le_span_pkt), true},
+				  {span_recs, nullptr, (max_updates + 1) * sizeof(btbbx_le_span_rec), false}};
+	return le_follow_host_chain(
+		a, adv_errors, seeds, ((!spans || !span_recs || !crypt) && conn_cap) || !keys,
+		[&](uint32_t cap, uint32_t k) { return ld_up(crypt_tail(cap, k).total) + btbbx_le_keyed_span_scratch_bytes(cap, k, max_updates); }, outs, 5,
+		[&](const LeHostRun &r, uint64_t pitch, const btbbx_le_seed *d_seeds, char *d_scratch, char *const *d_out) {
+			const LdtHostTail D = le_data_host_layout(r.dev_cap, r.dev_conns, 0, 0);
+			const LxHostTail C = crypt_tail(r.dev_cap, r.dev_conns);
+			const btbbx_le_data_pkt *d_dpkts = (const btbbx_le_data_pkt *)(d_scratch + D.dpkts);
+			uint64_t *d_counts = (uint64_t *)(d_scratch + C.counts);
+			uint8_t *d_keys = (uint8_t *)(d_scratch + C.keys);
+			HIP_TRY(hipMemcpyAsync(d_keys, keys, 16 * (size_t)n_keys, hipMemcpyHostToDevice, r.q));
+			int rc2 = le_host_data(r, n_words, pitch, n_streams, d_scratch, D);
+			if (!rc2)
+				rc2 = le_crypt_launch(r.d_words, n_words, pitch, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count,
+						      r.dev_conns, r.d_pkts, d_dpkts, d_keys, n_keys, window, (btbbx_le_crypt *)d_out[0],
+						      (btbbx_le_crypt_pkt *)d_out[1], (btbbx_le_data_pkt *)(d_scratch + C.ppkts),
+						      (btbbx_le_msg *)(d_scratch + C.msgs), 0, (uint32_t *)(d_counts + 1), (uint8_t *)(d_scratch + C.bytes), 0,
+						      d_counts, d_scratch + C.scratch, r.q);
+			if (!rc2)
+				rc2 = le_keyed_launch_span(r.d_words, n_words, pitch, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count,
+							   r.dev_conns, r.d_pkts, d_seeds, d_dpkts, (const btbbx_le_crypt *)d_out[0],
+							   (const btbbx_le_crypt_pkt *)d_out[1], unit_bits, jitter_bits, max_updates,
+							   (btbbx_le_span *)d_out[2], (btbbx_le_span_pkt *)d_out[3], (btbbx_le_span_rec *)d_out[4],
+							   d_scratch + ld_up(C.total), r.q);
+			return rc2;
 		});
 }
 

@@ -80,6 +80,7 @@ static LsLayout le_span_layout(uint32_t cand_cap, uint32_t conn_cap, uint32_t ma
 // ---- a. the parameter updates' fields ---------------------------------------------------------------------------------------
 
 // prm[i] = WinSize | WinOffset << 16, Interval | Latency << 16; the timeout goes to ctl[i].z, which an opcode-0 PDU leaves free
+// (le_keyed.h has this kernel's keyed form, le_keyed_param_kernel: a change here is made there too)
 extern "C" __global__ __launch_bounds__(LE_THREADS) void le_span_param_kernel(const uint64_t *words, uint64_t n_words, uint64_t pitch_words,
 									      uint32_t n_streams, const btbbx_le_cand *cands,
 									      const btbbx_le_track_pkt *pkts, const btbbx_le_conn *conns,
@@ -534,6 +535,7 @@ extern "C" __global__ __launch_bounds__(LE_THREADS) void le_span_verdict_kernel(
 	out[6] = make_uint2(sc[g].s + 1, (sc[g].interval & 0xffffu) | (v.algorithm << 16) | (flags << 24));
 }
 
+// (le_keyed.h has this kernel's keyed form, le_keyed_pkt_span_kernel: a change here is made there too)
 extern "C" __global__ __launch_bounds__(LE_THREADS) void le_span_pkt_kernel(const btbbx_le_cand *cands, const btbbx_le_track_pkt *pkts,
 									    const btbbx_le_conn *conns, const btbbx_le_seed *seeds,
 									    const uint32_t *params, const uint4 *ctl, const uint4 *evres,
@@ -565,13 +567,32 @@ extern "C" size_t btbbx_le_span_scratch_bytes(uint32_t cand_cap, uint32_t conn_c
 	return le_span_layout(cand_cap, conn_cap, max_updates > LS_MAX_UPDATES ? LS_MAX_UPDATES : max_updates).total;
 }
 
+// the clear reading of a run's control PDUs (le_follow.h), with the kernel that reads a parameter update's fields and this stage's
+// packet kernel
+struct LsReadClear : LfReadClear {
+	void param(const LfBufs &B, const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, const btbbx_le_cand *d_cands,
+		   const btbbx_le_track_pkt *d_pkts, const btbbx_le_conn *d_conns, const btbbx_le_seed *d_seeds, uint2 *prm, dim3 per_cand,
+		   hipStream_t q) const
+	{
+		hipLaunchKernelGGL(le_span_param_kernel, per_cand, dim3(LE_THREADS), 0, q, d_words, n_words, pitch_words, n_streams, d_cands, d_pkts,
+				   d_conns, d_seeds, B.params, B.ctl, prm, B.work);
+	}
+	void span_pkts(const LfBufs &B, const btbbx_le_cand *d_cands, const btbbx_le_track_pkt *d_pkts, const btbbx_le_conn *d_conns,
+		       const btbbx_le_seed *d_seeds, btbbx_le_span *d_spans, btbbx_le_span_pkt *d_spkts, dim3 per_cand, hipStream_t q) const
+	{
+		hipLaunchKernelGGL(le_span_pkt_kernel, per_cand, dim3(LE_THREADS), 0, q, d_cands, d_pkts, d_conns, d_seeds, B.params, B.ctl, B.evres,
+				   B.work, d_spans, d_spkts);
+	}
+};
+
 // the launches of one run: 13 kernels -- 5 of them the follow stage's, 1 the tracking's --, 6 per round, 3 per radix pass (6 over I, 1 to 4
-// over conn_cap)
+// over conn_cap); `read` chooses four of them: the slot, open, parameter and packet kernels, or le_keyed.h's in their places
+template <class Read = LsReadClear>
 static int le_span_launch(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams, const btbbx_le_cand *d_cands,
 			  const uint32_t *d_count, uint32_t cap, const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
 			  const btbbx_le_track_pkt *d_pkts, const btbbx_le_seed *d_seeds, uint32_t unit_bits, uint32_t jitter_bits,
 			  uint32_t max_updates, btbbx_le_span *d_spans, btbbx_le_span_pkt *d_spkts, btbbx_le_span_rec *d_recs, void *d_scratch,
-			  hipStream_t q)
+			  hipStream_t q, const Read &read = Read())
 {
 	const LfBufs B = le_follow_bufs(d_scratch, cap, conn_cap);
 	const LsLayout S = le_span_layout(cap, conn_cap, max_updates);
@@ -581,9 +602,8 @@ static int le_span_launch(const uint64_t *d_words, uint64_t n_words, uint64_t pi
 	uint2 *prm = (uint2 *)(s + S.prm);
 	LsConn *sc = (LsConn *)(s + S.sc);
 	const dim3 per_cand((cap + LE_THREADS - 1) / LE_THREADS), per_tile(B.tiles_n), per_conn((conn_cap + LE_THREADS - 1) / LE_THREADS), wg(LE_THREADS);
-	le_follow_open(B, d_words, n_words, pitch_words, n_streams, d_cands, d_count, cap, d_conns, d_conn_count, conn_cap, d_pkts, q);
-	hipLaunchKernelGGL(le_span_param_kernel, per_cand, wg, 0, q, d_words, n_words, pitch_words, n_streams, d_cands, d_pkts, d_conns, d_seeds,
-			   B.params, B.ctl, prm, B.work);
+	le_follow_open(B, d_words, n_words, pitch_words, n_streams, d_cands, d_count, cap, d_conns, d_conn_count, conn_cap, d_pkts, q, read);
+	read.param(B, d_words, n_words, pitch_words, n_streams, d_cands, d_pkts, d_conns, d_seeds, prm, per_cand, q);
 	hipLaunchKernelGGL(le_span_begin_kernel, per_conn, wg, 0, q, d_conns, d_seeds, B.params, B.econn, B.anchor, jitter_bits, max_updates, sc,
 			   sstart, d_recs);
 	for (uint32_t round = 0; round <= max_updates; round++) {
@@ -607,8 +627,7 @@ static int le_span_launch(const uint64_t *d_words, uint64_t n_words, uint64_t pi
 			   B.s_map, sstart, d_recs, max_updates, B.evres, B.work, sc);
 	hipLaunchKernelGGL(le_span_verdict_kernel, per_conn, wg, 0, q, d_conns, d_seeds, B.params, B.uparams, B.step, s_conn, B.s_map, B.evres, B.work,
 			   sc, d_spans);
-	hipLaunchKernelGGL(le_span_pkt_kernel, per_cand, wg, 0, q, d_cands, d_pkts, d_conns, d_seeds, B.params, B.ctl, B.evres, B.work, d_spans,
-			   d_spkts);
+	read.span_pkts(B, d_cands, d_pkts, d_conns, d_seeds, d_spans, d_spkts, per_cand, q);
 	HIP_TRY(hipGetLastError());
 	return BTBBX_OK;
 }

@@ -57,7 +57,8 @@ def put(words, row, bit, value, nbits):
         nbits -= take
 
 
-def build(n_conns, n_events, map_instants, param_instants, seed):
+def build(n_conns, n_events, map_instants, param_instants, seed, intervals=(8, 6)):
+    """intervals: what the two parameter updates change the 6 units to."""
     rng = np.random.default_rng(seed)
     per = 2 * n_events
     cands = np.zeros(n_conns * per, bt.LE_CAND_DTYPE)
@@ -82,7 +83,7 @@ def build(n_conns, n_events, map_instants, param_instants, seed):
         # the forward walk: 6 units, then 8 from the first instant, 6 from the second; each new window WinOffset units + pos behind
         gap = np.full(n_events, 6 * UNIT, np.int64)
         gap[0] = 0
-        ups = [(param_instants[0], 8, int(rng.integers(0, 4)), 1), (param_instants[1], 6, int(rng.integers(0, 4)), 2)]
+        ups = [(param_instants[0], intervals[0], int(rng.integers(0, 4)), 1), (param_instants[1], intervals[1], int(rng.integers(0, 4)), 2)]
         iv = 6
         for i, new, wo, ws in ups:
             gap[i] = iv * UNIT + wo * UNIT + int(rng.integers(0, ws * UNIT - 200))
