@@ -1343,6 +1343,142 @@ int64_t btbbx_le_pair_host(const uint64_t *words, uint64_t n_words, uint64_t pit
 			   uint64_t msg_cap, uint64_t byte_cap, uint32_t tk_limit, btbbx_le_pair *pairs, uint8_t *keys,
 			   uint32_t key_cap, uint32_t *n_keys_out);
 
+/* ---- LE address resolution: IRKs from SMP, RPAs resolved, identities ------------------------
+ * Behind the advertising scan and -- for the keys the peers distribute -- behind the decryption stage, on the device: the distinct
+ * device addresses of the advertising records, a table of identity resolving keys (IRKs: the caller's, then those the SMP
+ * messages carry), every resolvable private address (RPA) tried against every key of the table, and per connection which
+ * address and which key its two ends have.  It changes nothing of its input.
+ *
+ * The input is the decoded advertising records (d_adv, d_adv_count, adv_cap, as btbbx_le_seed_device takes them; A = the smaller
+ * of count and cap), the message outputs of the data stage or the decryption stage exactly as btbbx_le_pair_device takes them
+ * (d_msgs may be NULL with msg_cap 0: nothing is harvested then; the same three skip guards apply: conn >= K, octets outside
+ * byte_cap, bytes < 4 + l2cap_len; an SMP message is what that stage's rule 1 says, sent by role CENTRAL or PERIPHERAL), the
+ * connections (d_conn_count, conn_cap, d_seeds; K = the smaller of count and cap; conn_cap 0 is allowed: no peers, no harvest)
+ * and the caller's keys (d_given, n_given keys of 16 octets in AES key order, most significant octet first: the byte order
+ * btbbx_le_crypt_device takes).  All arithmetic is integer arithmetic.  An address is six octets a[0..5] as they lie in the PDU
+ * (least significant first), like seed.init_a, with its random bit t.
+ *   1. KIND.  PUBLIC 0 iff t == 0.  Otherwise by a[5] >> 6: 0 NONRESOLVABLE 1, 1 RESOLVABLE 2, 2 RESERVED 3, 3 STATIC 4.
+ *   2. SLOTS.  Record i < A has the address slots 2i and 2i + 1.  A record with crc_ok == 0, is_data != 0 or channel_idx < 37
+ *      has none.  Otherwise, with bytes[6..11] the first and bytes[12..17] the second address of the PDU, by adv_type:
+ *        0, 2, 4, 6  ADV_IND, ADV_NONCONN_IND, SCAN_RSP, ADV_SCAN_IND   length >= 6: slot 0 = the first address, t = adv_tx_add,
+ *                    role ADVERTISER 1; no slot 1
+ *        1           ADV_DIRECT_IND   length >= 12: slot 0 ADVERTISER 1 (adv_tx_add), slot 1 TARGET 8 (adv_rx_add)
+ *        3           SCAN_REQ         length >= 12: slot 0 SCANNER 2 (adv_tx_add), slot 1 ADVERTISER 1 (adv_rx_add)
+ *        5           CONNECT_IND      length >= 12: slot 0 INITIATOR 4 (adv_tx_add), slot 1 ADVERTISER 1 (adv_rx_add)
+ *      Every other type has none: extended advertising is not read.
+ *   3. DISTINCT LIST.  key = t << 48 | a[5] << 40 | ... | a[0].  The distinct keys in ascending order are the address list;
+ *      *d_addr_count = their number N: the stage WRITES it, it does not add to it.  d_slot_addr[s] (2 * adv_cap entries, every
+ *      one written) = the rank of slot s's key in that list, 0xffffffff for a slot that holds no address.  The first
+ *      min(N, addr_cap) records are written to d_addrs, every byte of them and nothing behind them.
+ *   4. IRK TABLE.  Slots 0 .. n_given - 1 are the caller's keys, flag GIVEN 1, conn = 0xffffffff, role 0.  Behind them the
+ *      harvested keys by ascending (connection, role), CENTRAL before PERIPHERAL, flag HARVESTED 2, conn and role set.  A
+ *      (connection, role) has a key iff it has an SMP message with code 0x08 and l2cap_len 17; the first such counts:
+ *      key[j] = v[16 - j], the byte order of the pairing stage's rule 8.  If it also has one with code 0x09 and l2cap_len 8, the
+ *      first counts: id_random = v[1] & 1, id_addr[j] = v[2 + j], flag HAS_ADDR 4.  A slot whose sixteen octets are all zero
+ *      gets flag NULLKEY 8 and is never tried (the specification's "no IRK" is one such).  *d_irk_count = n_given + the number
+ *      of harvested keys, written, not added to; it may exceed irk_cap: the keys beyond the cap are neither stored nor tried.
+ *      Duplicates are kept as they come.  Every byte of d_irks[0 .. irk_cap) is written, behind the count as zeros with
+ *      conn = 0xffffffff.  irk_cap is 0..BTBBX_LE_RESOLVE_MAX_IRKS, n_given <= irk_cap.
+ *   5. RESOLVE.  Over all N distinct addresses, whatever addr_cap is, and the min(*d_irk_count, irk_cap) slots without NULLKEY:
+ *      only RESOLVABLE addresses are tried.  block[0..12] = 0, block[13] = a[5], block[14] = a[4], block[15] = a[3]; address
+ *      and slot MATCH iff o = AES(key, block) has o[13] == a[2], o[14] == a[1], o[15] == a[0] (ah of Core Vol 3 Part H 2.2.2:
+ *      prand = a[5..3], hash = a[2..0]).  The address's irk is the smallest matching slot, 0xffff if none.  A wrong key matches
+ *      with probability 2^-24 per trial: against 4096 keys one unrelated RPA in 4096 resolves by accident, 256 of 2^20.
+ *   6. ADDRESS RECORDS.  first_offset / last_offset: the smallest and the largest offset of a record that holds the address in a
+ *      slot; n_slots: how many slots hold it; first_rec: the smallest such record index; addr, random (t), kind (rule 1), irk
+ *      (rule 5), roles: the OR of the slot roles; channels: bit channel_idx - 37 of every such record.
+ *   7. IRK RECORDS.  key, id_addr, id_random, flags, conn, role (rule 4); n_addrs: the distinct addresses whose irk is this
+ *      slot; n_slots: the slots they fill.  All N addresses count, not only the stored ones.
+ *   8. PEERS.  Parallel to the connections, every byte of d_peers[0 .. K) written, nothing behind it.  For a SEEDED connection
+ *      whose seed.request < A: init_addr = d_slot_addr[2 * request], adv_addr = d_slot_addr[2 * request + 1], init_irk /
+ *      adv_irk = those addresses' irk; otherwise 0xffffffff / 0xffff.  irk[role] = the table slot of the key harvested from
+ *      that (connection, role), 0xffff if there is none or it lies beyond irk_cap.  The stage reads flags and request of a seed,
+ *      nothing else.
+ * LIMITS: extended advertising (type 7 and what AuxPtr points to) and addresses inside AdvData are not read; CSRK and
+ * EDIV / Rand are not extracted; a second pairing's keys do not replace the first's; the Identity messages of an LE Secure
+ * Connections pairing are read like any others once a key decrypts them. */
+#define BTBBX_LE_RESOLVE_MAX_IRKS 4096u
+#define BTBBX_LE_ADDR_PUBLIC        0u   /* btbbx_le_addr.kind */
+#define BTBBX_LE_ADDR_NONRESOLVABLE 1u
+#define BTBBX_LE_ADDR_RESOLVABLE    2u
+#define BTBBX_LE_ADDR_RESERVED      3u
+#define BTBBX_LE_ADDR_STATIC        4u
+#define BTBBX_LE_ADDR_ADVERTISER    1u   /* btbbx_le_addr.roles */
+#define BTBBX_LE_ADDR_SCANNER       2u
+#define BTBBX_LE_ADDR_INITIATOR     4u
+#define BTBBX_LE_ADDR_TARGET        8u
+#define BTBBX_LE_IRK_GIVEN          1u   /* btbbx_le_irk.flags */
+#define BTBBX_LE_IRK_HARVESTED      2u
+#define BTBBX_LE_IRK_HAS_ADDR       4u
+#define BTBBX_LE_IRK_NULLKEY        8u
+
+typedef struct btbbx_le_addr {       /* 40 bytes, one per distinct address, ascending by key */
+	uint64_t first_offset, last_offset;
+	uint32_t n_slots, first_rec;
+	uint8_t  addr[6], random, kind;
+	uint16_t irk;                /* table slot, 0xffff if none */
+	uint8_t  roles;              /* ADVERTISER 1, SCANNER 2, INITIATOR 4, TARGET 8 */
+	uint8_t  channels;           /* bit channel_idx - 37 */
+	uint8_t  reserved[4];        /* written as 0 */
+} btbbx_le_addr;
+typedef struct btbbx_le_irk {        /* 40 bytes, one per table slot */
+	uint8_t  key[16], id_addr[6], id_random, flags;
+	uint32_t conn;               /* 0xffffffff unless HARVESTED */
+	uint32_t n_addrs, n_slots;
+	uint8_t  role, reserved[3];  /* reserved: written as 0 */
+} btbbx_le_irk;
+typedef struct btbbx_le_peer {       /* 16 bytes, parallel to conns */
+	uint32_t init_addr, adv_addr; /* ranks in the address list, 0xffffffff if none */
+	uint16_t init_irk, adv_irk, irk[2];
+} btbbx_le_peer;
+
+/* Nothing is read back and the call is asynchronous on hip_stream.  d_scratch: btbbx_le_resolve_scratch_bytes(adv_cap, conn_cap,
+ * irk_cap) bytes, 16-byte aligned: the keys and vals of both sides of the sort, its histogram, the per-address words, 44 words of
+ * schedule per table slot, the round table and the counts, about 120 bytes per advertising record.  The count of launches, 32,
+ * depends on no count and no cap.
+ * BTBBX_E_ARG, before any launch: a null pointer (d_adv and d_slot_addr may be null with adv_cap 0, d_msgs with msg_cap 0, d_bytes
+ * with byte_cap 0, d_given with n_given 0, d_addrs with addr_cap 0, d_irks with irk_cap 0, d_conn_count, d_seeds and d_peers with
+ * conn_cap 0), irk_cap > 4096, n_given > irk_cap, adv_cap >= 2^31, a record pointer that is not 8-byte aligned (the slot map and
+ * the counters: 4), a scratch that is too small or not 16-byte aligned. */
+size_t btbbx_le_resolve_scratch_bytes(uint32_t adv_cap, uint32_t conn_cap, uint32_t irk_cap);
+int btbbx_le_resolve_device(const btbbx_le_pkt *d_adv, const uint32_t *d_adv_count, uint32_t adv_cap,
+			    const uint32_t *d_conn_count, uint32_t conn_cap, const btbbx_le_seed *d_seeds,
+			    const btbbx_le_msg *d_msgs, const uint32_t *d_msg_count, uint32_t msg_cap,
+			    const uint8_t *d_bytes, uint64_t byte_cap, const uint8_t *d_given, uint32_t n_given,
+			    uint32_t *d_slot_addr, btbbx_le_addr *d_addrs, uint32_t addr_cap, uint32_t *d_addr_count,
+			    btbbx_le_irk *d_irks, uint32_t irk_cap, uint32_t *d_irk_count, btbbx_le_peer *d_peers,
+			    void *d_scratch, size_t scratch_bytes, void *hip_stream);
+
+/* Host wrapper over the advertising channels alone: capture in, advertising scan (BTBBX_LE_ADV_AA, adv_errors), order, decode,
+ * then this stage with the caller's keys and no connection; it works on a capture without any data channel.  adv: adv_cap
+ * decoded records in (stream, offset) order; slot_addr: 2 * adv_cap entries; addrs: addr_cap records; irks: irk_cap records.  Returns the
+ * number of advertising records found; when it, *n_addrs_out or *n_irks_out exceeds its cap the prefix is returned and the count
+ * says so (slot_addr then names ranks beyond addr_cap too).  The n_*_out pointers may be NULL.
+ * BTBBX_E_ARG: btbbx_le_scan_host's conditions, a null array with a cap != 0, keys NULL with n_given != 0, irk_cap > 4096,
+ * n_given > irk_cap, adv_cap >= 2^31. */
+int64_t btbbx_le_resolve_adv_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				  uint64_t search_bits, const uint16_t *phys_channel, int adv_errors,
+				  const uint8_t *given, uint32_t n_given, btbbx_le_pkt *adv, uint64_t adv_cap,
+				  uint32_t *slot_addr, btbbx_le_addr *addrs, uint32_t addr_cap, uint32_t *n_addrs_out,
+				  btbbx_le_irk *irks, uint32_t irk_cap, uint32_t *n_irks_out);
+
+/* Host wrapper: btbbx_le_keyed_span_host's chain up to and including the decryption stage (keys, n_keys >= 1, window; msg_cap and
+ * byte_cap: the device-side room for the decrypted messages, which are not copied out), then this stage over the decrypted
+ * messages, the chain's own advertising records and the caller's keys (given, n_given, which may be 0).  btbbx_le_epoch_host's
+ * arguments up to and including seeds and its return value; peers: conn_cap records parallel to conns; irks: irk_cap records;
+ * addrs: addr_cap records; *n_irks_out and *n_addrs_out (may be NULL): the counts, which may exceed the caps.  A capture without
+ * a candidate or without a stored connection gives zeroed tables and the counts 0.
+ * BTBBX_E_ARG: btbbx_le_keyed_span_host's conditions on what it shares, peers NULL with conn_cap != 0, irks NULL with irk_cap
+ * != 0, addrs NULL with addr_cap != 0, given NULL with n_given != 0, irk_cap > 4096, n_given > irk_cap. */
+int64_t btbbx_le_resolve_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			      uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+			      btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+			      uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+			      int adv_errors, btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_seed *seeds,
+			      const uint8_t *keys, uint32_t n_keys, uint32_t window, uint64_t msg_cap, uint64_t byte_cap,
+			      const uint8_t *given, uint32_t n_given, btbbx_le_peer *peers, btbbx_le_irk *irks, uint32_t irk_cap,
+			      uint32_t *n_irks_out, btbbx_le_addr *addrs, uint32_t addr_cap, uint32_t *n_addrs_out);
+
 /* ---- hop selection and CLK1-27 reversal ------------------------- */
 #define BTBBX_SEQUENCE_LENGTH 134217728u   /* values of CLK1-27, bluetooth_piconet.h:102 */
 

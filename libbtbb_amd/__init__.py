@@ -176,6 +176,19 @@ LE_PAIR_DTYPE = np.dtype([("stk", "u1", (16,)), ("ltk", "u1", (2, 16)), ("preq",
                           ("sconf", "<u4"), ("mrand", "<u4"), ("srand", "<u4"), ("tk", "<u4"), ("method", "u1"), ("flags", "u1"),
                           ("keys", "u1"), ("key_size", "u1"), ("key", "u1"), ("reserved", "u1", (7,))])
 assert LE_PAIR_DTYPE.itemsize == 88
+# LE address resolution (include/btbbx.h btbbx_le_addr / btbbx_le_irk / btbbx_le_peer; le_resolve.h checks the C layout with
+# static_asserts): an address's kind, the roles it was seen in, a table slot's flags
+LE_ADDR_PUBLIC, LE_ADDR_NONRESOLVABLE, LE_ADDR_RESOLVABLE, LE_ADDR_RESERVED, LE_ADDR_STATIC = range(5)
+LE_ADDR_ADVERTISER, LE_ADDR_SCANNER, LE_ADDR_INITIATOR, LE_ADDR_TARGET = 1, 2, 4, 8
+LE_IRK_GIVEN, LE_IRK_HARVESTED, LE_IRK_HAS_ADDR, LE_IRK_NULLKEY = 1, 2, 4, 8
+LE_RESOLVE_MAX_IRKS = 4096
+LE_NO_ADDR, LE_NO_IRK = 0xFFFFFFFF, 0xFFFF
+LE_ADDR_DTYPE = np.dtype([("first_offset", "<u8"), ("last_offset", "<u8"), ("n_slots", "<u4"), ("first_rec", "<u4"), ("addr", "u1", (6,)),
+                          ("random", "u1"), ("kind", "u1"), ("irk", "<u2"), ("roles", "u1"), ("channels", "u1"), ("reserved", "u1", (4,))])
+LE_IRK_DTYPE = np.dtype([("key", "u1", (16,)), ("id_addr", "u1", (6,)), ("id_random", "u1"), ("flags", "u1"), ("conn", "<u4"),
+                         ("n_addrs", "<u4"), ("n_slots", "<u4"), ("role", "u1"), ("reserved", "u1", (3,))])
+LE_PEER_DTYPE = np.dtype([("init_addr", "<u4"), ("adv_addr", "<u4"), ("init_irk", "<u2"), ("adv_irk", "<u2"), ("irk", "<u2", (2,))])
+assert LE_ADDR_DTYPE.itemsize == 40 and LE_IRK_DTYPE.itemsize == 40 and LE_PEER_DTYPE.itemsize == 16
 
 # one surveyed piconet (include/btbbx.h btbbx_survey_rec; survey.hip checks the C layout with static_asserts)
 SURVEY_DTYPE = np.dtype([("lap", "<u4"), ("flags", "<u4"), ("uap", "u1"), ("clk_offset", "u1"), ("used_channels", "u1"),
@@ -305,6 +318,13 @@ SIGNATURES = {
     "btbbx_le_pair_device": (C.c_int, [_vp, _u32, _vp, _vp, _vp, _u32, _vp, _u64, _u32, _vp, _vp, _u32, _vp, _vp, C.c_size_t, _vp]),
     "btbbx_le_pair_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
                                        C.c_int, _vp, _vp, _vp, _u64, _u64, _u32, _vp, _vp, _u32, _vp]),
+    "btbbx_le_resolve_scratch_bytes": (C.c_size_t, [_u32, _u32, _u32]),
+    "btbbx_le_resolve_device": (C.c_int, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32,
+                                          _vp, _vp, _vp, C.c_size_t, _vp]),
+    "btbbx_le_resolve_adv_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, C.c_int, _vp, _u32, _vp, _u64, _vp, _vp, _u32, _vp, _vp, _u32,
+                                              _vp]),
+    "btbbx_le_resolve_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
+                                          C.c_int, _vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp]),
     "btbbx_survey_scratch_bytes": (C.c_size_t, [_u32]),
     "btbbx_survey_hits_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp,
                                            _vp, C.c_size_t, _vp]),
@@ -858,6 +878,101 @@ def le_crack_span(words, search_bits, phys_channels, tk_limit=LE_PAIR_MAX_TK, ke
     kw = {k: v for k, v in kw.items() if k not in ("msg_cap", "byte_cap")}
     return pair, le_span_keyed(words, search_bits, phys_channels, pair[6][:found], window=window, max_updates=max_updates,
                                adv_errors=adv_errors, **kw)
+
+
+def _key_rows(keys):
+    """Keys as a (n, 16) uint8 array: an array, or a sequence of 16-octet values."""
+    if keys is None:
+        return np.zeros((0, 16), np.uint8)
+    if not isinstance(keys, np.ndarray):
+        keys = np.frombuffer(b"".join(bytes(k) for k in keys), np.uint8)
+    return np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1, 16)
+
+
+def le_resolve(words, search_bits, phys_channels, irks, adv_errors=0, n_streams=1, pitch_words=None, n_words=None, adv_cap=1 << 20,
+               addr_cap=1 << 20, irk_cap=None, truncate=False):
+    """LE address resolution over the advertising channels alone (include/btbbx.h btbbx_le_resolve_device): the advertising scan
+    (le_scan's, with adv_errors), then every distinct device address of the advertising PDUs and every resolvable private address
+    among them tried against `irks` (16-octet keys in AES key order, most significant octet first, at most 4096).  irk_cap: the
+    table's slots, len(irks) by default.  The capture needs no data channel.
+    Returns (adv, slot_addr, addrs, table): the LE_PKT_DTYPE records in (stream, offset) order, a (len(adv), 2) uint32 array with the rank of each
+    record's two address slots in addrs (LE_NO_ADDR: the slot holds none), the LE_ADDR_DTYPE records ascending by (random bit,
+    address) -- irk names the smallest matching slot of the table, LE_NO_IRK if none -- and the LE_IRK_DTYPE records of the table."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if pitch_words is None:
+        pitch_words = len(words) // n_streams
+    if n_words is None:
+        n_words = pitch_words
+    assert n_words <= pitch_words and (n_streams - 1) * pitch_words + n_words <= len(words)
+    phys = np.ascontiguousarray(np.broadcast_to(np.asarray(phys_channels, dtype=np.uint16), (n_streams,)))
+    given = _key_rows(irks)
+    irk_cap = len(given) if irk_cap is None else irk_cap
+    adv = np.empty(max(adv_cap, 1), dtype=LE_PKT_DTYPE)
+    slot_addr = np.empty((max(adv_cap, 1), 2), dtype=np.uint32)
+    addrs = np.empty(max(addr_cap, 1), dtype=LE_ADDR_DTYPE)
+    table = np.empty(max(irk_cap, 1), dtype=LE_IRK_DTYPE)
+    n_addrs, n_irks = C.c_uint32(0), C.c_uint32(0)
+    n = check(lib().btbbx_le_resolve_adv_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, _ptr(phys), adv_errors, _ptr(given),
+                                              len(given), _ptr(adv), adv_cap, _ptr(slot_addr), _ptr(addrs), addr_cap, C.byref(n_addrs),
+                                              _ptr(table), irk_cap, C.byref(n_irks)), "btbbx_le_resolve_adv_host")
+    if (n > adv_cap or n_addrs.value > addr_cap) and not truncate:
+        raise BtbbError("buffers too small: %d advertising records > %d or %d addresses > %d" % (n, adv_cap, n_addrs.value, addr_cap))
+    na = min(n, adv_cap)
+    return adv[:na].copy(), slot_addr[:na].copy(), addrs[:min(n_addrs.value, addr_cap)].copy(), table[:irk_cap].copy()
+
+
+def le_identify(words, search_bits, phys_channels, keys, irks=None, window=8, max_len=27, min_count=2, n_streams=1, pitch_words=None,
+                n_words=None, unit_bits=1250, ifs_bits=200, jitter_bits=50, flags=LE_TRACK_REMAP, adv_errors=0, conn_cap=1 << 12,
+                cand_cap=1 << 20, truncate=False, msg_cap=1 << 16, byte_cap=1 << 22, irk_cap=LE_RESOLVE_MAX_IRKS, addr_cap=1 << 16):
+    """le_span_keyed's chain up to and including the decryption stage under `keys` and `window` (le_decrypt's), then LE address
+    resolution (include/btbbx.h btbbx_le_resolve_device) over the decrypted messages, the chain's own advertising records and the
+    caller's `irks` (may be None): the identity resolving keys the peers distribute are read out of the plaintext, and every
+    resolvable private address of the advertising channels is tried against them and the caller's.  msg_cap and byte_cap: the
+    device-side room for the decrypted messages, which are not returned.  le_follow's other parameters; max_len as le_span_keyed.
+    Returns (conns, cands, tracks, pkts, seeds, peers, table, addrs, n_irks, n_addrs): le_follow's arrays up to seeds, LE_PEER_DTYPE
+    records parallel to conns, the LE_IRK_DTYPE table (irk_cap records: the caller's keys, then the harvested ones), the first
+    addr_cap LE_ADDR_DTYPE records and the two counts, which may exceed their caps."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if pitch_words is None:
+        pitch_words = len(words) // n_streams
+    if n_words is None:
+        n_words = pitch_words
+    assert n_words <= pitch_words and (n_streams - 1) * pitch_words + n_words <= len(words)
+    phys = np.ascontiguousarray(np.broadcast_to(np.asarray(phys_channels, dtype=np.uint16), (n_streams,)))
+    keys, given = _key_rows(keys), _key_rows(irks)
+    conns = np.empty(max(conn_cap, 1), dtype=LE_CONN_DTYPE)
+    tracks = np.empty(max(conn_cap, 1), dtype=LE_TRACK_DTYPE)
+    seeds = np.empty(max(conn_cap, 1), dtype=LE_SEED_DTYPE)
+    peers = np.empty(max(conn_cap, 1), dtype=LE_PEER_DTYPE)
+    cands = np.empty(max(cand_cap, 1), dtype=LE_CAND_DTYPE)
+    pkts = np.empty(max(cand_cap, 1), dtype=LE_TRACK_PKT_DTYPE)
+    table = np.zeros(max(irk_cap, 1), dtype=LE_IRK_DTYPE)
+    addrs = np.zeros(max(addr_cap, 1), dtype=LE_ADDR_DTYPE)
+    n_cands, n_irks, n_addrs = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0)
+    n = check(lib().btbbx_le_resolve_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, _ptr(phys), max_len, min_count,
+                                          _ptr(conns), conn_cap, _ptr(cands), cand_cap, C.byref(n_cands), unit_bits, ifs_bits, jitter_bits,
+                                          flags, adv_errors, _ptr(tracks), _ptr(pkts), _ptr(seeds), _ptr(keys), len(keys), window, msg_cap,
+                                          byte_cap, _ptr(given), len(given), _ptr(peers), _ptr(table), irk_cap, C.byref(n_irks), _ptr(addrs),
+                                          addr_cap, C.byref(n_addrs)), "btbbx_le_resolve_host")
+    if (n > conn_cap or n_cands.value > cand_cap) and not truncate:
+        raise BtbbError("buffers too small: %d connections > %d or %d candidates > %d" % (n, conn_cap, n_cands.value, cand_cap))
+    nc, nk = min(n, conn_cap), min(n_cands.value, cand_cap)
+    return (conns[:nc].copy(), cands[:nk].copy(), tracks[:nc].copy(), pkts[:nk].copy(), seeds[:nc].copy(), peers[:nc].copy(),
+            table[:irk_cap].copy(), addrs[:min(n_addrs.value, addr_cap)].copy(), int(n_irks.value), int(n_addrs.value))
+
+
+def le_crack_identify(words, search_bits, phys_channels, irks=None, tk_limit=LE_PAIR_MAX_TK, key_cap=LE_PAIR_MAX_KEYS, window=8,
+                      adv_errors=0, irk_cap=LE_RESOLVE_MAX_IRKS, addr_cap=1 << 16, **kw):
+    """le_pair, then le_identify under the short-term keys it recovered, as le_crack composes pairing and decryption: capture in,
+    identities out, no key given.  kw: what both take (max_len, min_count, n_streams, pitch_words, n_words, the timing, flags,
+    conn_cap, cand_cap, msg_cap, byte_cap, truncate).
+    Returns (pair, identities): le_pair's tuple and le_identify's.  When no key was found nothing is raised and identities is None."""
+    pair = le_pair(words, search_bits, phys_channels, tk_limit=tk_limit, key_cap=key_cap, adv_errors=adv_errors, **kw)
+    found = min(pair[7], key_cap)
+    if not found:
+        return pair, None
+    return pair, le_identify(words, search_bits, phys_channels, pair[6][:found], irks=irks, window=window, adv_errors=adv_errors,
+                             irk_cap=irk_cap, addr_cap=addr_cap, **kw)
 
 
 class DeviceBuffer:

@@ -545,4 +545,5 @@ extern "C" int64_t btbbx_le_scan_host(const uint64_t *words, uint64_t n_words, u
 #include "le_crypt.h"
 #include "le_keyed.h"
 #include "le_pair.h"
+#include "le_resolve.h"
 #include "le_host.h"

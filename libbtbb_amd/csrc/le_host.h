@@ -1,4 +1,4 @@
-// le_host.h -- the host wrappers of the LE stages (included by le.hip, behind le_pair.h).  Every wrapper runs one chain: the
+// le_host.h -- the host wrappers of the LE stages (included by le.hip, behind le_resolve.h).  Every wrapper runs one chain: the
 // capture goes to the device, the discovery scans and groups it, the tracking works on what the discovery stored, the wrapper's own
 // stages follow on the same stream and the records are copied out.  The chain is written here once:
 //
@@ -11,7 +11,7 @@
 // A wrapper calls these in this order, launches its own stages between le_host_track and le_host_finish, and names its own
 // outputs (LeHostOut).  Nothing of one call outlives it: what a tail's size depends on is captured by the callable that computes it.
 #pragma once
-#include "le_pair.h"
+#include "le_resolve.h"
 
 // What the discovery leaves on the device, inside the caller's CallScope: the counters, the sorted candidates, the connection
 // records and, behind them, `tail` (tail_bytes(dev_cap, dev_conns) bytes for what a caller runs next on the same stream).
@@ -142,6 +142,10 @@ struct LeHostRun : LeDiscHostRun {
 	btbbx_le_track *d_tracks;
 	btbbx_le_track_pkt *d_pkts;
 	char *own;                                     // the wrapper's own part of the tail, behind the tracking's
+	// le_follow_host_chain's advertising block, for its last stage: the decoded records, their count, what the block holds
+	const btbbx_le_pkt *d_adv = nullptr;
+	const uint32_t *d_adv_count = nullptr;
+	uint32_t adv_cap = 0;
 };
 
 // an output of a wrapper beyond conns / tracks / pkts / cands: one record of `size` bytes per connection, or per candidate; a
@@ -571,8 +575,16 @@ static int le_follow_host_adv(const LeHostArgs &a, const LeHostRun &r, uint64_t 
 					   BTBBX_LE_ADV_CRC_INIT, *d_adv, r.q);
 }
 
+// the advertising hits le_follow_host_chain makes room for at first (a 40-bit pattern with up to four errors matches noise at one
+// offset in ten million)
+static uint32_t le_follow_adv_guess(const LeHostArgs &a)
+{
+	const uint64_t guess = a.search_bits / 16384 * a.n_streams + 4096;
+	return guess > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)guess;
+}
+
 // The chain of btbbx_le_epoch_host and btbbx_le_span_host: the advertising scan, the tracking, the seed stage and the wrapper's
-// last stage -- last(r, pitch_words, d_seeds, d_scratch, d_out): its launches --, whose scratch takes last_scratch(dev_cap, dev_conns)
+// last stage -- last(r, pitch_words, d_seeds, d_scratch, d_out): its launches; r names the advertising block too --, whose scratch takes last_scratch(dev_cap, dev_conns)
 // bytes.  outs: the last stage's outputs (at most five; src is not read): their device records stand behind the scratch in this
 // order, dev_conns or dev_cap of them each (or `fixed` of them), and d_out[o] is where those of outs[o] begin.
 // A failed launch does not end the call at once: the stream is synchronised and a spilled advertising block freed first
@@ -585,9 +597,7 @@ static int64_t le_follow_host_chain(const LeHostArgs &a, int adv_errors, btbbx_l
 		return rc;
 	const uint64_t pitch_words = a.n_streams == 1 ? a.n_words : a.pitch_words;
 	CallScope scope;
-	// (a 40-bit pattern with up to four errors matches noise at one offset in ten million)
-	const uint64_t guess = a.search_bits / 16384 * a.n_streams + 4096;
-	uint32_t adv_cap = guess > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)guess;
+	uint32_t adv_cap = le_follow_adv_guess(a);
 	// behind the tracking's part: the seeds, the last stage's scratch and records, the advertising scan's block
 	const auto records = [&](uint32_t cap, uint32_t conns, int upto) {
 		size_t at = ld_up((size_t)conns * sizeof(btbbx_le_seed)) + ld_up(last_scratch(cap, conns));
@@ -622,6 +632,9 @@ static int64_t le_follow_host_chain(const LeHostArgs &a, int adv_errors, btbbx_l
 		if (!rc)
 			rc = btbbx_le_seed_device(d_adv, (uint32_t *)ablock, adv_cap, r.d_conns, r.d_conn_count, r.dev_conns, r.d_tracks, a.unit_bits,
 						  d_seeds, r.q);
+		r.d_adv = d_adv;
+		r.d_adv_count = (const uint32_t *)ablock;
+		r.adv_cap = adv_cap;
 		if (!rc)
 			rc = last(r, pitch_words, d_seeds, r.own + ld_up((size_t)r.dev_conns * sizeof(btbbx_le_seed)), d_out);
 	}
@@ -763,5 +776,193 @@ extern "C" int64_t btbbx_le_pair_host(const uint64_t *words, uint64_t n_words, u
 		});
 	if (ret >= 0 && n_keys_out)
 		*n_keys_out = n_keys;
+	return ret;
+}
+
+// ---- address resolution -----------------------------------------------------------------------------------------------------------
+
+// the advertising channels alone: btbbx_le_scan_host's chain for the advertising AA, then the resolve stage under the caller's keys
+extern "C" int64_t btbbx_le_resolve_adv_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+					     uint64_t search_bits, const uint16_t *phys_channel, int adv_errors, const uint8_t *given,
+					     uint32_t n_given, btbbx_le_pkt *adv, uint64_t adv_cap, uint32_t *slot_addr, btbbx_le_addr *addrs,
+					     uint32_t addr_cap, uint32_t *n_addrs_out, btbbx_le_irk *irks, uint32_t irk_cap, uint32_t *n_irks_out)
+{
+	const char *who = "btbbx_le_resolve_adv_host";
+	int rc = le_check_args(who, n_words, pitch_words, n_streams, search_bits, adv_errors);
+	if (!rc)
+		rc = le_resolve_check_limits(who, adv_cap, n_given, irk_cap);
+	if (rc)
+		return rc;
+	if (!words || !phys_channel || ((!adv || !slot_addr) && adv_cap) || (!addrs && addr_cap) || (!irks && irk_cap) || (!given && n_given)) {
+		set_error("%s: null pointer", who);
+		return BTBBX_E_ARG;
+	}
+	rc = ctx_require();
+	if (rc)
+		return rc;
+	if (n_addrs_out)
+		*n_addrs_out = 0;
+	if (n_irks_out)
+		*n_irks_out = 0;
+	if (n_streams == 1)
+		pitch_words = n_words;
+	CallScope scope;
+	hipStream_t q = scope_stream();
+	const uint64_t cap_words = (uint64_t)(n_streams - 1) * pitch_words + n_words;
+	const size_t words_bytes = ((size_t)(cap_words + 1) * 8 + 255) & ~(size_t)255;
+	char *dblock = (char *)scope_device(words_bytes + 2 * (size_t)n_streams);
+	if (!dblock)
+		return BTBBX_E_NOMEM;
+	const uint64_t *d_words = (const uint64_t *)dblock;
+	uint16_t *d_phys = (uint16_t *)(dblock + words_bytes);
+	HIP_TRY(hipMemcpyAsync(dblock, words, (size_t)cap_words * 8, hipMemcpyHostToDevice, q));
+	HIP_TRY(hipMemcpyAsync(d_phys, phys_channel, 2 * (size_t)n_streams, hipMemcpyHostToDevice, q));
+	// the scan as btbbx_le_scan_host runs it: a first guess, repeated with room for every match so that the prefix is the true one
+	uint64_t guess = std::min<uint64_t>(search_bits / 1024 * n_streams + 4096, adv_cap);
+	uint32_t dev_cap = (uint32_t)guess, count = 0, n = 0;
+	char *block = nullptr;
+	size_t at = 0;
+	auto take = [&](size_t bytes) { const size_t here = at; at += ld_up(bytes); return here; };
+	size_t hits = 0, order = 0, order_bytes = 0, pkts = 0, keys = 0, slots = 0, arecs = 0, irecs = 0, counts = 0, scratch = 0;
+	for (int pass = 0; pass < 2; pass++) {
+		n = (uint32_t)std::min<uint64_t>(dev_cap, adv_cap);     // the records that are decoded and resolved
+		at = 256;
+		hits = take((size_t)dev_cap * sizeof(btbbx_hit));
+		order_bytes = dev_cap >= 2 ? btbbx_order_hits_scratch_bytes(dev_cap) : 0;
+		order = take(order_bytes);
+		pkts = take((size_t)n * sizeof(btbbx_le_pkt));
+		keys = take(16 * (size_t)n_given);
+		slots = take(8 * (size_t)n);
+		arecs = take((size_t)addr_cap * sizeof(btbbx_le_addr));
+		irecs = take((size_t)irk_cap * sizeof(btbbx_le_irk));
+		counts = take(256);
+		scratch = take(le_resolve_layout(n, 0, irk_cap).total);
+		block = (char *)scope_hits(at);
+		if (!block)
+			return BTBBX_E_NOMEM;
+		HIP_TRY(hipMemsetAsync(block, 0, sizeof(uint32_t), q));
+		rc = le_launch_scan(d_words, n_words, pitch_words, n_streams, search_bits, BTBBX_LE_ADV_AA, adv_errors, (btbbx_hit *)(block + hits),
+				    dev_cap, (uint32_t *)block, q);
+		if (rc)
+			return rc;
+		HIP_TRY(hipMemcpyAsync(&count, block, sizeof(count), hipMemcpyDeviceToHost, q));
+		HIP_TRY(hipStreamSynchronize(q));
+		if (count <= dev_cap || adv_cap == 0)
+			break;
+		dev_cap = count;
+	}
+	uint32_t *d_count = (uint32_t *)block, *d_counts = (uint32_t *)(block + counts);
+	btbbx_le_pkt *d_adv = (btbbx_le_pkt *)(block + pkts);
+	if (std::min(count, dev_cap) >= 2) {
+		rc = btbbx_order_hits_device((btbbx_hit *)(block + hits), d_count, dev_cap, block + order, ld_up(order_bytes), q);
+		if (rc)
+			return rc;
+	}
+	if (n) {
+		rc = btbbx_le_decode_hits_device(d_words, n_words, pitch_words, (btbbx_hit *)(block + hits), d_count, n, d_phys, BTBBX_LE_ADV_CRC_INIT,
+						 d_adv, q);
+		if (rc)
+			return rc;
+	}
+	if (n_given)
+		HIP_TRY(hipMemcpyAsync(block + keys, given, 16 * (size_t)n_given, hipMemcpyHostToDevice, q));
+	rc = le_resolve_launch(n ? d_adv : nullptr, d_count, n, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, (const uint8_t *)(block + keys),
+			       n_given, (uint32_t *)(block + slots), (btbbx_le_addr *)(block + arecs), addr_cap, d_counts, (btbbx_le_irk *)(block + irecs),
+			       irk_cap, d_counts + 1, nullptr, block + scratch, q);
+	if (rc)
+		return rc;
+	uint32_t got[2] = {0, 0};
+	HIP_TRY(hipMemcpyAsync(got, d_counts, sizeof(got), hipMemcpyDeviceToHost, q));
+	HIP_TRY(hipStreamSynchronize(q));
+	const uint32_t have = std::min(count, n), have_addrs = std::min(got[0], addr_cap);
+	if (have) {
+		HIP_TRY(hipMemcpyAsync(adv, d_adv, (size_t)have * sizeof(btbbx_le_pkt), hipMemcpyDeviceToHost, q));
+		HIP_TRY(hipMemcpyAsync(slot_addr, block + slots, 8 * (size_t)have, hipMemcpyDeviceToHost, q));
+	}
+	if (have_addrs)
+		HIP_TRY(hipMemcpyAsync(addrs, block + arecs, (size_t)have_addrs * sizeof(btbbx_le_addr), hipMemcpyDeviceToHost, q));
+	if (irk_cap)
+		HIP_TRY(hipMemcpyAsync(irks, block + irecs, (size_t)irk_cap * sizeof(btbbx_le_irk), hipMemcpyDeviceToHost, q));
+	HIP_TRY(hipStreamSynchronize(q));
+	if (n_addrs_out)
+		*n_addrs_out = got[0];
+	if (n_irks_out)
+		*n_irks_out = got[1];
+	return (int64_t)count;
+}
+
+// the data stage, the decryption stage and the resolve stage behind the seed stage
+extern "C" int64_t btbbx_le_resolve_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+					 uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, uint32_t min_count,
+					 btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+					 uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+					 int adv_errors, btbbx_le_track *tracks, btbbx_le_track_pkt *pkts, btbbx_le_seed *seeds,
+					 const uint8_t *keys, uint32_t n_keys, uint32_t window, uint64_t msg_cap, uint64_t byte_cap,
+					 const uint8_t *given, uint32_t n_given, btbbx_le_peer *peers, btbbx_le_irk *irks, uint32_t irk_cap,
+					 uint32_t *n_irks_out, btbbx_le_addr *addrs, uint32_t addr_cap, uint32_t *n_addrs_out)
+{
+	const LeHostArgs a = LE_HOST_ARGS("btbbx_le_resolve_host");
+	int rc = le_resolve_check_limits(a.who, 0, n_given, irk_cap);
+	if (!rc)
+		rc = le_crypt_check_keys(a.who, n_keys, window);
+	if (rc)
+		return rc;
+	uint32_t n_irks = 0, n_addrs = 0;
+	void *extra = nullptr;                                  // this stage's own blocks, when the advertising block had to grow
+	const uint32_t guess = std::min(le_follow_adv_guess(a), 0x7fffffffu);
+	// the data stage's and the decryption stage's parts as btbbx_le_crypt_host lays them out, then the caller's keys, the slot map and
+	// this stage's scratch, the last two for `guess` advertising records
+	const auto caps = [&](uint32_t cap, uint32_t k) { return le_data_host_layout(cap, k, msg_cap, byte_cap); };
+	const auto crypt_tail = [&](uint32_t cap, uint32_t k) { return le_crypt_host_layout(cap, k, n_keys, caps(cap, k)); };
+	const auto own_given = [&](uint32_t cap, uint32_t k) { return ld_up(crypt_tail(cap, k).total); };
+	const auto own_slots = [&](uint32_t cap, uint32_t k) { return own_given(cap, k) + ld_up(16 * (size_t)n_given); };
+	const auto own_scratch = [&](uint32_t cap, uint32_t k) { return own_slots(cap, k) + ld_up(8 * (size_t)guess); };
+	const LeHostOut outs[] = {{peers, nullptr, sizeof(btbbx_le_peer), false}, {irks, nullptr, sizeof(btbbx_le_irk), false, (int64_t)irk_cap},
+				  {addrs, nullptr, sizeof(btbbx_le_addr), false, (int64_t)addr_cap}, {&n_irks, nullptr, sizeof(uint32_t), false, 1},
+				  {&n_addrs, nullptr, sizeof(uint32_t), false, 1}};
+	const int64_t ret = le_follow_host_chain(
+		a, adv_errors, seeds, (!peers && conn_cap) || (!irks && irk_cap) || (!addrs && addr_cap) || (!given && n_given) || !keys,
+		[&](uint32_t cap, uint32_t k) { return own_scratch(cap, k) + le_resolve_layout(guess, k, irk_cap).total; }, outs, 5,
+		[&](const LeHostRun &r, uint64_t pitch, const btbbx_le_seed *d_seeds, char *d_scratch, char *const *d_out) {
+			const LdtHostTail D = le_data_host_layout(r.dev_cap, r.dev_conns, 0, 0), T = caps(r.dev_cap, r.dev_conns);
+			const LxHostTail C = crypt_tail(r.dev_cap, r.dev_conns);
+			const btbbx_le_data_pkt *d_dpkts = (const btbbx_le_data_pkt *)(d_scratch + D.dpkts);
+			btbbx_le_msg *d_msgs = (btbbx_le_msg *)(d_scratch + C.msgs);
+			uint64_t *d_counts = (uint64_t *)(d_scratch + C.counts);
+			uint8_t *d_bytes = (uint8_t *)(d_scratch + C.bytes), *d_keys = (uint8_t *)(d_scratch + C.keys);
+			uint8_t *d_given = (uint8_t *)(d_scratch + own_given(r.dev_cap, r.dev_conns));
+			const uint32_t adv_cap = std::min(r.adv_cap, 0x7fffffffu);
+			char *d_slots = d_scratch + own_slots(r.dev_cap, r.dev_conns), *d_own = d_scratch + own_scratch(r.dev_cap, r.dev_conns);
+			if (adv_cap > guess) {
+				const size_t slot_bytes = ld_up(8 * (size_t)adv_cap);
+				if (hipMalloc(&extra, slot_bytes + le_resolve_layout(adv_cap, r.dev_conns, irk_cap).total) != hipSuccess) {
+					set_error("%s: block for %u advertising records failed", a.who, adv_cap);
+					return (int)BTBBX_E_NOMEM;
+				}
+				d_slots = (char *)extra;
+				d_own = d_slots + slot_bytes;
+			}
+			HIP_TRY(hipMemcpyAsync(d_keys, keys, 16 * (size_t)n_keys, hipMemcpyHostToDevice, r.q));
+			if (n_given)
+				HIP_TRY(hipMemcpyAsync(d_given, given, 16 * (size_t)n_given, hipMemcpyHostToDevice, r.q));
+			int rc2 = le_host_data(r, n_words, pitch, n_streams, d_scratch, D);
+			if (!rc2)
+				rc2 = le_crypt_launch(r.d_words, n_words, pitch, n_streams, r.d_cands, r.d_count, r.dev_cap, r.d_conns, r.d_conn_count,
+						      r.dev_conns, r.d_pkts, d_dpkts, d_keys, n_keys, window, (btbbx_le_crypt *)(d_scratch + C.crypt),
+						      (btbbx_le_crypt_pkt *)(d_scratch + C.cpkts), (btbbx_le_data_pkt *)(d_scratch + C.ppkts), d_msgs,
+						      T.msg_cap, (uint32_t *)(d_counts + 1), d_bytes, T.byte_cap, d_counts, d_scratch + C.scratch, r.q);
+			if (!rc2)
+				rc2 = le_resolve_launch(r.d_adv, r.d_adv_count, adv_cap, r.d_conn_count, r.dev_conns, d_seeds, d_msgs,
+							(const uint32_t *)(d_counts + 1), T.msg_cap, d_bytes, T.byte_cap, d_given, n_given,
+							(uint32_t *)d_slots, (btbbx_le_addr *)d_out[2], addr_cap, (uint32_t *)d_out[4],
+							(btbbx_le_irk *)d_out[1], irk_cap, (uint32_t *)d_out[3], (btbbx_le_peer *)d_out[0], d_own, r.q);
+			return rc2;
+		});
+	if (extra)
+		(void)hipFree(extra);
+	if (ret >= 0 && n_irks_out)
+		*n_irks_out = n_irks;
+	if (ret >= 0 && n_addrs_out)
+		*n_addrs_out = n_addrs;
 	return ret;
 }
