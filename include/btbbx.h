@@ -1479,6 +1479,83 @@ int64_t btbbx_le_resolve_host(const uint64_t *words, uint64_t n_words, uint64_t 
 			      const uint8_t *given, uint32_t n_given, btbbx_le_peer *peers, btbbx_le_irk *irks, uint32_t irk_cap,
 			      uint32_t *n_irks_out, btbbx_le_addr *addrs, uint32_t addr_cap, uint32_t *n_addrs_out);
 
+/* ---- LE Coded PHY scan: coded access address search, Viterbi decode ------------------------
+ * The LE Coded PHY (Core v5.x Vol 6 Part B 2.2, 3.1, 3.2, 3.3) runs at the 1 Msym/s of the streams above.  AIR FORMAT, from the
+ * first preamble symbol: 80 uncoded preamble symbols, ten times 0 0 1 1 1 1 0 0; FEC block 1 = access address (32 bits, LSB
+ * first), CI (2 bits, LSB first), TERM1 (3 zero bits), always at S = 8 symbols per bit: 296 symbols; FEC block 2 = PDU (2 + L
+ * octets), CRC-24, TERM2 (3 zero bits): N = 8 * (L + 5) + 3 bits at S = 8 (CI 0) or S = 2 (CI 1); CI 2 and 3 are RFU.  CRC,
+ * then whitening, then FEC, then the pattern mapper; CRC and whitening are the 1M ones and cover PDU (whitening: and CRC) only.
+ * The encoder is rate 1/2, K = 4, starts each block in state 0, a0 = b ^ b1 ^ b2 ^ b3, a1 = b ^ b2 ^ b3, a0 sent first; at S = 8 a
+ * coded 0 is sent as 0 0 1 1 and a coded 1 as 1 1 0 0, at S = 2 coded bits are sent as they are.  A packet is 376 + S * N
+ * symbols, 17040 at most.  Hard decisions only.
+ *
+ *  1. MATCH.  Offset o < search_bits of a stream matches iff the 336 symbols from o differ from preamble + mapped, coded AA
+ *     (encoder from state 0, no CI) in at most max_errors places, max_errors 0 .. BTBBX_LE_CODED_MAX_ERRORS.  The record is a
+ *     btbbx_hit: offset = first preamble symbol, lap = the AA SEARCHED FOR, ac_errors = the mismatch count, stream.  Every matching
+ *     offset is reported, nothing is suppressed; an AA whose pattern is periodic (all zeros is one) matches at shifts too.  63 keeps
+ *     the count in a uint8_t and below the side lobes of a true packet (smallest count at a wrong offset within +-400 symbols:
+ *     104 for the advertising AA, 84 over 200 random AAs).  The records leave in no order; btbbx_order_hits_device orders them.
+ *  2. TRELLIS.  State s = b1 | b2 << 1 | b3 << 2, next state (s << 1 | b) & 7.  A step reads S symbols; its branch metric is the
+ *     Hamming distance between them and the mapped (a0, a1) of the transition.  Symbols past the stream's end read as 0.  State
+ *     s' has the predecessors (s' >> 1) | x << 2, x = 0 or 1; the one with the smaller sum survives, x = 0 on equal sums.  A block
+ *     starts with state 0 at metric 0, the other states unreachable.
+ *  3. BLOCK 1.  37 steps of 8 symbols from o + 80, traced back from state 0.  Bits 0..31 = access_address (the DECODED one, which
+ *     may differ from the one searched for), bits 32..33 = ci, metric1 = the path's metric.
+ *  4. S.  ci 0: 8.  ci 1: 2.  ci 2 or 3: s = 0, there is no block 2: pdu_bytes = 0, crc_ok = 0, truncated = 0, symbols = 376,
+ *     metric2 = 0, header_moved = 0, crc_rx = crc_calc = 0, bytes = the four AA octets and zeros, and the fields derived from the
+ *     header are those of a zero header.
+ *  5. LENGTH.  Block 2 starts at o + 376 and is ONE forward pass.  After step 16 + BTBBX_LE_CODED_LAG = 40 the path is traced back
+ *     from the state with the smallest metric (smallest state index on ties); its first 16 bits, dewhitened, are the provisional
+ *     header, L its octet 1 (all 8 bits), N = 8 * (L + 5) + 3 (>= 43 > 40: the lag step always exists).
+ *  6. BODY.  The forward pass goes on to step N; the path is traced back from state 0.  Its first N - 3 bits are header, payload
+ *     and CRC as sent, metric2 its metric; header_moved = 1 iff its 16 header bits differ from rule 5's.  L is not revised.
+ *  7. RECORD.  The bits of rule 6 are dewhitened with the channel's register, the CRC-24 runs under crc_init over 2 + L octets;
+ *     crc_rx, crc_calc, pdu_bytes, crc_ok, bytes[64] (decoded AA, then the dewhitened octets, zero past the end) and every lell
+ *     field are formed exactly as btbbx_le_decode_hits_device forms them from its octets (one device function serves both).
+ *     truncated = 1 and crc_ok = 0 iff o + symbols > 64 * n_words.  aa_errors = the hit's ac_errors; offset and stream the hit's.
+ *  8. WRITES.  Records [0, min(*d_count, cap)) of both arrays are written whole, the reserved bytes as 0; nothing else is
+ *     written; the count stays on the device.
+ * LIMITS: not in here are the promiscuous discovery of coded connections (unknown AA), reading ADV_EXT_IND / AuxPtr (extended
+ * advertising), feeding coded records to the seed, follow or resolve stages, the 2M PHY, soft decisions, and bytes beyond 64
+ * octets.  The lell_* entries still abort. */
+#define BTBBX_LE_CODED_PATTERN    336   /* preamble 80 + coded AA 256 symbols */
+#define BTBBX_LE_CODED_MAX_ERRORS 63
+#define BTBBX_LE_CODED_LAG        24
+
+typedef struct btbbx_le_coded_info {   /* 16 bytes, parallel to the btbbx_le_pkt of the same hit */
+	uint32_t symbols;      /* 376 + S * N, from the first preamble symbol; 376 when s == 0 */
+	uint32_t metric2;      /* symbol mismatches along block 2's chosen path */
+	uint16_t metric1;      /* the same for block 1 (296 symbols) */
+	uint8_t  ci, s;        /* CI as decoded; 8, 2, or 0 for an RFU CI */
+	uint8_t  header_moved; /* the final path's 16 header bits differ from the lag decision's (rule 5) */
+	uint8_t  reserved[3];
+} btbbx_le_coded_info;
+
+/* Stage 1 (rule 1).  Arguments as btbbx_le_scan_device; BTBBX_E_ARG: max_errors outside 0..63, search_bits + 335 > 64 * n_words,
+ * n_streams outside 1..65535, pitch_words < n_words, a null pointer, d_words not 8-, d_hits not 16-, d_hit_count not 4-byte
+ * aligned.  The counter is added to, not cleared. */
+int btbbx_le_coded_scan_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			       uint64_t search_bits, uint32_t aa, int max_errors,
+			       btbbx_hit *d_hits, uint32_t hit_cap, uint32_t *d_hit_count, void *hip_stream);
+
+/* Stage 2 (rules 2..8) for the first min(*d_count, cap) hits.  The decoder keeps its survivor decisions in LDS (2112 bytes per
+ * hit) and needs NO caller scratch: btbbx_le_coded_scratch_bytes returns 0 for every cap, d_scratch may be NULL and is never
+ * touched, so no scratch is too short.  BTBBX_E_ARG: a null pointer with cap != 0, d_words, d_hits or d_out not 8-, d_count or
+ * d_info not 4-, d_phys_channel not 2-byte aligned, n_words > 2^40. */
+size_t btbbx_le_coded_scratch_bytes(uint32_t cap);
+int btbbx_le_coded_decode_hits_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words,
+				      const btbbx_hit *d_hits, const uint32_t *d_count, uint32_t cap,
+				      const uint16_t *d_phys_channel, uint32_t crc_init,
+				      btbbx_le_pkt *d_out, btbbx_le_coded_info *d_info,
+				      void *d_scratch, size_t scratch_bytes, void *hip_stream);
+
+/* Host wrapper, btbbx_le_scan_host's chain: copy in, scan, scan again with room for every hit when the first guess was short,
+ * order by (stream, offset), decode, copy out.  Returns the number of matches or a negative BTBBX_E_*; when it exceeds cap the
+ * cap SMALLEST (stream, offset) records are returned.  Safe to call from several host threads at once. */
+int64_t btbbx_le_coded_scan_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				 uint64_t search_bits, const uint16_t *phys_channel, uint32_t aa, uint32_t crc_init,
+				 int max_errors, btbbx_le_pkt *pkts, btbbx_le_coded_info *info, uint64_t cap);
+
 /* ---- hop selection and CLK1-27 reversal ------------------------- */
 #define BTBBX_SEQUENCE_LENGTH 134217728u   /* values of CLK1-27, bluetooth_piconet.h:102 */
 

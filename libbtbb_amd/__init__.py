@@ -89,6 +89,14 @@ LE_PKT_DTYPE = np.dtype([("offset", "<u8"), ("stream", "<u2"), ("aa_errors", "u1
                          ("pad", "u1", (4,))])
 assert LE_PKT_DTYPE.itemsize == 104 and LE_PKT_DTYPE.fields["bytes"][1] == 36
 
+# LE Coded PHY (include/btbbx.h btbbx_le_coded_*; le_coded.h checks the C layout with a static_assert)
+LE_CODED_PATTERN = 336
+LE_CODED_MAX_ERRORS = 63
+LE_CODED_LAG = 24
+LE_CODED_INFO_DTYPE = np.dtype([("symbols", "<u4"), ("metric2", "<u4"), ("metric1", "<u2"), ("ci", "u1"), ("s", "u1"),
+                                ("header_moved", "u1"), ("reserved", "u1", (3,))])
+assert LE_CODED_INFO_DTYPE.itemsize == 16
+
 # LE connection discovery (include/btbbx.h btbbx_le_cand / btbbx_le_conn; le_discover.h checks the C layout with static_asserts)
 LE_CAND_DTYPE = np.dtype([("offset", "<u8"), ("access_address", "<u4"), ("crc_init", "<u4"), ("stream", "<u2"),
                           ("header0", "u1"), ("length", "u1"), ("conn", "<u4")])
@@ -273,6 +281,10 @@ SIGNATURES = {
     "btbbx_le_scan_device": (C.c_int, [_vp, _u64, _u64, _u32, _u64, _u32, C.c_int, _vp, _u32, _vp, _vp]),
     "btbbx_le_decode_hits_device": (C.c_int, [_vp, _u64, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp]),
     "btbbx_le_scan_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, C.c_int, _vp, _u64]),
+    "btbbx_le_coded_scan_device": (C.c_int, [_vp, _u64, _u64, _u32, _u64, _u32, C.c_int, _vp, _u32, _vp, _vp]),
+    "btbbx_le_coded_scratch_bytes": (C.c_size_t, [_u32]),
+    "btbbx_le_coded_decode_hits_device": (C.c_int, [_vp, _u64, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "btbbx_le_coded_scan_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, C.c_int, _vp, _vp, _u64]),
     "btbbx_le_discover_scan_device": (C.c_int, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _vp, _u32, _vp, _vp]),
     "btbbx_le_discover_scratch_bytes": (C.c_size_t, [_u32]),
     "btbbx_le_discover_group_device": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _vp, C.c_size_t, _vp]),
@@ -526,6 +538,28 @@ def le_scan(words, search_bits, phys_channels, aa=LE_ADV_AA, crc_init=LE_ADV_CRC
     if n > cap and not truncate:
         raise BtbbError("packet buffer too small: %d > %d" % (n, cap))
     return pkts[:min(n, cap)]
+
+
+def le_coded_scan(words, search_bits, phys_channels, aa=LE_ADV_AA, crc_init=LE_ADV_CRC_INIT, max_errors=16, n_streams=1,
+                  pitch_words=None, n_words=None, cap=1 << 20, truncate=False):
+    """Bluetooth LE Coded PHY packets (include/btbbx.h, LE Coded PHY scan: the 336 symbols preamble + coded access address within
+    max_errors <= 63 mismatches, both FEC blocks Viterbi-decoded, dewhitened, CRC checked) in n_streams packed streams held in host
+    memory; words, phys_channels, n_words and pitch_words as le_scan.  Returns (pkts, info): LE_PKT_DTYPE and LE_CODED_INFO_DTYPE
+    records of the same hits in (stream, offset) order.  With truncate=True the `cap` smallest are returned when more were found."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if pitch_words is None:
+        pitch_words = len(words) // n_streams
+    if n_words is None:
+        n_words = pitch_words
+    assert n_words <= pitch_words and (n_streams - 1) * pitch_words + n_words <= len(words)
+    phys = np.ascontiguousarray(np.broadcast_to(np.asarray(phys_channels, dtype=np.uint16), (n_streams,)))
+    pkts = np.zeros(max(cap, 1), dtype=LE_PKT_DTYPE)
+    info = np.zeros(max(cap, 1), dtype=LE_CODED_INFO_DTYPE)
+    n = check(lib().btbbx_le_coded_scan_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, _ptr(phys), aa, crc_init,
+                                             max_errors, _ptr(pkts), _ptr(info), cap), "btbbx_le_coded_scan_host")
+    if n > cap and not truncate:
+        raise BtbbError("packet buffer too small: %d > %d" % (n, cap))
+    return pkts[:min(n, cap)], info[:min(n, cap)]
 
 
 def le_discover(words, search_bits, phys_channels, max_len=27, min_count=2, n_streams=1, pitch_words=None, n_words=None,

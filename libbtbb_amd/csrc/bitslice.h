@@ -258,3 +258,92 @@ BITSLICE_FN uint32_t le_filter16(const uint32_t *r, const uint32_t *flip)
 	const uint32_t le2 = (~b_any & ~bitop3<0x80>(a0, a1, a2)) | (b_one & ~bitop3<0xfe>(a0, a1, a2));
 	return le1 | (le2 & ~ones);
 }
+
+// ---- LE Coded PHY (le_coded.h): bit-sliced counters wider than a handful of planes ----
+// bs_add<N>: o[0 .. N] = a[0 .. N-1] + b[0 .. N-1], planes LSB first (a ripple of full adders: two instructions per plane).
+// o must not alias a or b.
+template <int N>
+BITSLICE_FN void bs_add(const uint32_t *a, const uint32_t *b, uint32_t *o)
+{
+	uint32_t c = a[0] & b[0];
+	o[0] = a[0] ^ b[0];
+#pragma unroll
+	for (int k = 1; k < N; k++) {
+		o[k] = FA_SUM(a[k], b[k], c);
+		c = FA_CARRY(a[k], b[k], c);
+	}
+	o[N] = c;
+}
+
+// bs_shift_add<N>: o = lo + (the N-plane stream hi:lo moved down by sh positions, 0 < sh < 32): the count at offset p plus the
+// count at offset p + sh
+template <int N>
+BITSLICE_FN void bs_shift_add(const uint32_t *lo, const uint32_t *hi, uint32_t sh, uint32_t *o)
+{
+	uint32_t s[N];
+#pragma unroll
+	for (int k = 0; k < N; k++)
+		s[k] = alignbit(hi[k], lo[k], sh);
+	bs_add<N>(lo, s, o);
+}
+
+// bs_le<N>: the offsets whose N-plane count is <= limit (a run-time value below 2^N)
+template <int N>
+BITSLICE_FN uint32_t bs_le(const uint32_t *p, uint32_t limit)
+{
+	uint32_t gt = 0, eq = 0xffffffffu;
+#pragma unroll
+	for (int b = N - 1; b >= 0; b--) {
+		const uint32_t lim_bit = ((limit >> b) & 1) ? 0xffffffffu : 0u;
+		gt |= eq & p[b] & ~lim_bit;
+		eq &= ~(p[b] ^ lim_bit);
+	}
+	return ~gt;
+}
+
+// The coded scan's necessary condition.  Preamble and mapped access address are 84 groups of four symbols, each 0011 or 1100,
+// whatever the address: symbols k and k + 2 of the pattern differ for k mod 4 in {0, 1}.  These 168 pairs are disjoint, so a
+// window with e mismatches has at most e pairs of EQUAL symbols, and "equal pairs among the first 160 (groups 0 .. 79, window
+// symbols 0 .. 319) <= limit" can never reject a match.  Per dword d of the stream: V = pairs that are equal, A = V + V >> 1 (a
+// group's two pairs), then + >> 4, + >> 8, + >> 16: B[d] = the equal pairs of the eight groups from each of its 32 offsets;
+// chain c (the 32 offsets from dword c) sums B[c .. c + 9] as (c, c+1) + (c+2, c+3) + ... pairwise, every partial sum shared with the
+// neighbouring chains.  D[0 .. 15]: the sixteen dwords from the first chain's; m[0 .. 3]: the surviving offsets of four chains.
+// About 900 instructions for 128 offsets.  On a random stream the count is binomial(160, 1/2).
+#define LE_CODED_FILTER_PAIRS 160
+BITSLICE_FN void le_coded_filter(const uint32_t *D, uint32_t limit, uint32_t *m)
+{
+	uint32_t V[15], A[15][2], A4[15][3], A8[15][4], B[13][5], C[12][6], E[8][7], G[4][8];
+#pragma unroll
+	for (int d = 0; d < 15; d++)
+		V[d] = ~(D[d] ^ alignbit(D[d + 1], D[d], 2));
+#pragma unroll
+	for (int d = 0; d < 14; d++)
+		bs_shift_add<1>(&V[d], &V[d + 1], 1, A[d]);
+	A[14][0] = A[14][1] = 0;                            // (dword 14 of A, A4 and A8 only feeds bits of dword 13 that nothing reads)
+#pragma unroll
+	for (int d = 0; d < 14; d++)
+		bs_shift_add<2>(A[d], A[d + 1], 4, A4[d]);
+	A4[14][0] = A4[14][1] = A4[14][2] = 0;
+#pragma unroll
+	for (int d = 0; d < 14; d++)
+		bs_shift_add<3>(A4[d], A4[d + 1], 8, A8[d]);
+#pragma unroll
+	for (int d = 0; d < 13; d++)
+		bs_shift_add<4>(A8[d], A8[d + 1], 16, B[d]);
+#pragma unroll
+	for (int d = 0; d < 12; d++)
+		bs_add<5>(B[d], B[d + 1], C[d]);
+#pragma unroll
+	for (int d = 0; d < 8; d++)
+		bs_add<6>(C[d], C[d + 2], E[d]);
+#pragma unroll
+	for (int c = 0; c < 4; c++) {
+		bs_add<7>(E[c], E[c + 4], G[c]);
+		uint32_t last[8], sum[9];
+#pragma unroll
+		for (int k = 0; k < 8; k++)
+			last[k] = k < 6 ? C[c + 8][k] : 0u;
+		bs_add<8>(G[c], last, sum);                     // (at most 160: sum[8] is never set)
+		m[c] = bs_le<8>(sum, limit);
+	}
+}

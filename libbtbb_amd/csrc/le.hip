@@ -9,6 +9,7 @@
 // register position 23 down to 0.  Both registers run here in their reflected software form: whitening state bit j
 // = position 6 - j, CRC state bit j = position 23 - j; tests/_le.py shifts the spec's positions literally.
 #include "tile_scan.h"
+#include "le_record.h"
 #include <algorithm>
 #include <stddef.h>
 
@@ -171,77 +172,8 @@ __global__ __launch_bounds__(LE_THREADS) void le_scan_kernel(LeScanArgs a)
 
 // ---- stage 2: dewhitening, CRC-24, the lell fields ----------------------------------------------------------------
 
-// le_channel_index of the reference (bluetooth_le_packet.c:266-280), its integer arithmetic included: an odd or
-// out-of-range MHz value gives what the reference's unsigned-char conversion gives
-__host__ __device__ inline uint8_t le_channel_index(uint16_t mhz)
-{
-	const int f = mhz;
-	if (f == 2402)
-		return 37;
-	if (f < 2426)
-		return (uint8_t)((f - 2404) / 2);
-	if (f == 2426)
-		return 38;
-	if (f < 2480)
-		return (uint8_t)(11 + (f - 2428) / 2);
-	return 39;
-}
-
-// a 12-bit window of the AA with a run of seven or more equal bits, as the reference's enumeration counts such windows
-// (bluetooth_le_packet.c:184-238): its case list leaves out 38 of the 224 windows that hold such a run -- seven ones at
-// bits 0..6 or 5..11 unless the rest of the window is zero, seven ones at 4..10 with bit 2 clear, nine zeros at 0..8
-// unless bits 9..11 are all ones, and 0x401 -- and the offense count follows the reference, not the rule
-__host__ __device__ inline bool le_run_window(uint32_t v)
-{
-	uint32_t ones = v, zeros = ~v & 0xfffu;
-	for (int k = 0; k < 6; k++) {                       // x & x >> 1 ... six times: bit i survives iff bits i..i+6 are all set
-		ones &= ones >> 1;
-		zeros &= zeros >> 1;
-	}
-	if (!(ones | zeros))
-		return false;
-	if ((v & 0xffu) == 0x7fu && (v >> 8) != 0)
-		return false;
-	if ((v & 0xff0u) == 0xfe0u && (v & 0xfu) != 0)
-		return false;
-	if ((v & 0xffcu) == 0x7f0u)
-		return false;
-	if ((v & 0x3ffu) == 0x200u && (v >> 10) != 3)
-		return false;
-	return v != 0x401u;
-}
-
-// aa_data_channel_offenses (bluetooth_le_packet.c:100-242), restated: transitions beyond 24, fewer than two transitions
-// in the six most significant bits, four equal octets, the advertising AA or one of its one-bit neighbours, and one
-// per nibble-aligned 12-bit window with a long run (le_run_window)
-__host__ __device__ inline uint32_t le_data_offenses(uint32_t aa)
-{
-	uint32_t n = 0;
-	const uint32_t transitions = (uint32_t)__builtin_popcount((aa ^ (aa >> 1)) & 0x7fffffffu);
-	if (transitions > 24)
-		n += transitions - 24;
-	const uint32_t top6 = aa >> 26;
-	if (__builtin_popcount((top6 ^ (top6 >> 1)) & 0x1fu) < 2)
-		n++;
-	const uint32_t b0 = aa & 0xff;
-	if (b0 == ((aa >> 8) & 0xff) && b0 == ((aa >> 16) & 0xff) && b0 == (aa >> 24))
-		n++;
-	if (aa == BTBBX_LE_ADV_AA)
-		n++;
-	if (__builtin_popcount(aa ^ BTBBX_LE_ADV_AA) == 1)
-		n++;
-	for (int shift = 0; shift <= 20; shift += 4)
-		n += le_run_window((aa >> shift) & 0xfffu) ? 1u : 0u;
-	return n;
-}
-
-__host__ __device__ inline uint32_t le_reverse24(uint32_t x)
-{
-	uint32_t r = 0;
-	for (int i = 0; i < 24; i++)
-		r |= ((x >> i) & 1u) << (23 - i);
-	return r;
-}
+// (le_record.h, included above: the channel mapping, the access-address rules, the two tables' entries and le_record, which the
+// coded-PHY decoder of le_coded.h calls as well)
 
 // one thread per hit (hits are rare next to the offsets scanned).  LDS: the byte-wise CRC table of the reflected register
 // (state >>= 8 ^ T[(state ^ octet) & 0xff]) and the whitening register advanced eight bits at a time (127-state LFSR:
@@ -253,22 +185,9 @@ __global__ __launch_bounds__(256) void le_decode_kernel(const uint64_t *words, u
 	__shared__ uint32_t crc_tab[256];
 	__shared__ uint16_t wh_tab[128];                    // low byte: eight whitening bits; high byte: the next state
 	const uint32_t tid = threadIdx.x;
-	{
-		uint32_t s = tid;
-		for (int k = 0; k < 8; k++)
-			s = (s >> 1) ^ ((s & 1u) ? 0xda6000u : 0u);   // x^24 + x^10 + x^9 + x^6 + x^4 + x^3 + x + 1, reflected
-		crc_tab[tid] = s;
-		if (tid < 128) {
-			uint32_t w = tid, o = 0;
-			for (int k = 0; k < 8; k++) {
-				o |= (w & 1u) << k;
-				if (w & 1u)
-					w ^= 0x88u;
-				w >>= 1;
-			}
-			wh_tab[tid] = (uint16_t)(o | (w << 8));
-		}
-	}
+	crc_tab[tid] = le_crc_tab_entry(tid);
+	if (tid < 128)
+		wh_tab[tid] = le_wh_tab_entry(tid);
 	__syncthreads();
 	const uint32_t n = min(*d_count, cap);
 	const uint32_t i = blockIdx.x * 256u + tid;
@@ -283,78 +202,10 @@ __global__ __launch_bounds__(256) void le_decode_kernel(const uint64_t *words, u
 		const uint64_t hi = sh > 56 && wi + 1 < n_words ? w[wi + 1] : 0;
 		return (uint32_t)(((lo >> sh) | (sh ? hi << (64 - sh) : 0)) & 0xffu);
 	};
-	const uint16_t mhz = phys[h.stream];
-	const uint8_t ch_idx = le_channel_index(mhz);
-	const uint8_t ch_k = (uint8_t)(((int)mhz - 2402) / 2);
-	uint32_t ws = (ch_idx & 0x3fu) | 0x40u;            // whitening register: position 0 = 1, positions 1..6 = channel index
-	uint32_t crc = crc_init_reflected;
 	const uint64_t pdu_bit = h.offset + 40;
-	uint32_t *ob = reinterpret_cast<uint32_t *>(out[i].bytes);
-	ob[0] = h.lap;
-	// header
-	uint32_t wt = wh_tab[ws];
-	const uint32_t h0 = octet(pdu_bit) ^ (wt & 0xffu);
-	ws = wt >> 8;
-	wt = wh_tab[ws];
-	const uint32_t h1 = octet(pdu_bit + 8) ^ (wt & 0xffu);
-	ws = wt >> 8;
-	const uint32_t pdu = 2 + h1;
-	crc = (crc >> 8) ^ crc_tab[(crc ^ h0) & 0xffu];
-	crc = (crc >> 8) ^ crc_tab[(crc ^ h1) & 0xffu];
-	uint32_t acc = h0 | (h1 << 8), crc_rx = 0;
-	uint32_t dw = 1;                                    // next dword of `bytes` to store
-	for (uint32_t k = 2; k < pdu + 3; k++) {
-		wt = wh_tab[ws];
-		const uint32_t d = octet(pdu_bit + 8ull * k) ^ (wt & 0xffu);
-		ws = wt >> 8;
-		if (k < pdu)
-			crc = (crc >> 8) ^ crc_tab[(crc ^ d) & 0xffu];
-		else
-			crc_rx |= d << (8 * (k - pdu));
-		if (dw < 16) {
-			acc |= d << (8 * (k & 3));
-			if ((k & 3) == 3) {
-				ob[dw++] = acc;
-				acc = 0;
-			}
-		}
-	}
-	if (dw < 16 && ((pdu + 3) & 3))
-		ob[dw++] = acc;
-	while (dw < 16)
-		ob[dw++] = 0;
-	ob[16] = 0;                                         // (the record's tail padding: records are compared as bytes)
-	const uint64_t end_bit = pdu_bit + 8ull * (pdu + 3);
-	const bool truncated = end_bit > n_words * 64;
-	btbbx_le_pkt &o = out[i];
-	o.offset = h.offset;
-	o.stream = h.stream;
-	o.aa_errors = h.ac_errors;
-	o.crc_rx = crc_rx;
-	o.crc_calc = crc;
-	o.crc_ok = (!truncated && crc == crc_rx) ? 1 : 0;
-	o.pdu_bytes = (uint16_t)pdu;
-	o.truncated = truncated ? 1 : 0;
-	o.channel_idx = ch_idx;
-	o.channel_k = ch_k;
-	const bool data = ch_idx < 37;
-	o.is_data = data ? 1 : 0;
-	o.access_address = h.lap;
-	if (data) {
-		o.length = (uint8_t)(h1 & 0x1f);
-		o.adv_type = o.adv_tx_add = o.adv_rx_add = 0;
-		const uint32_t off = le_data_offenses(h.lap);
-		o.access_address_offenses = (uint8_t)off;
-		o.access_address_ok = off ? 0 : 1;
-	} else {
-		o.length = (uint8_t)(h1 & 0x3f);
-		o.adv_type = (uint8_t)(h0 & 0xf);
-		o.adv_tx_add = (h0 & 0x40) ? 1 : 0;
-		o.adv_rx_add = (h0 & 0x80) ? 1 : 0;
-		const bool ok = h.lap == BTBBX_LE_ADV_AA;
-		o.access_address_ok = ok ? 1 : 0;
-		o.access_address_offenses = ok ? 0 : (__builtin_popcount(h.lap ^ BTBBX_LE_ADV_AA) == 1 ? 1 : 32);
-	}
+	le_record([&](uint32_t k) { return octet(pdu_bit + 8ull * k); },
+		  [&](uint32_t pdu) { return pdu_bit + 8ull * (pdu + 3) > n_words * 64; },
+		  -1, crc_tab, wh_tab, phys[h.stream], crc_init_reflected, h.lap, h, out[i]);
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
