@@ -1515,7 +1515,8 @@ int64_t btbbx_le_resolve_host(const uint64_t *words, uint64_t n_words, uint64_t 
  *     truncated = 1 and crc_ok = 0 iff o + symbols > 64 * n_words.  aa_errors = the hit's ac_errors; offset and stream the hit's.
  *  8. WRITES.  Records [0, min(*d_count, cap)) of both arrays are written whole, the reserved bytes as 0; nothing else is
  *     written; the count stays on the device.
- * LIMITS: not in here are the promiscuous discovery of coded connections (unknown AA), reading ADV_EXT_IND / AuxPtr (extended
+ * LIMITS: the promiscuous discovery of coded connections (unknown AA) is the stage behind this one ("promiscuous LE Coded
+ * connection discovery" below); not in here are reading ADV_EXT_IND / AuxPtr (extended
  * advertising), feeding coded records to the seed, follow or resolve stages, the 2M PHY, soft decisions, and bytes beyond 64
  * octets.  The lell_* entries still abort. */
 #define BTBBX_LE_CODED_PATTERN    336   /* preamble 80 + coded AA 256 symbols */
@@ -1555,6 +1556,71 @@ int btbbx_le_coded_decode_hits_device(const uint64_t *d_words, uint64_t n_words,
 int64_t btbbx_le_coded_scan_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
 				 uint64_t search_bits, const uint16_t *phys_channel, uint32_t aa, uint32_t crc_init,
 				 int max_errors, btbbx_le_pkt *pkts, btbbx_le_coded_info *info, uint64_t cap);
+
+/* ---- promiscuous LE Coded connection discovery: access address and CRCInit ------------------
+ * The coded scan above finds a packet whose access address it is told.  On the 37 data channels every connection has an AA and a
+ * CRCInit of its own; this stage finds both in a capture that names neither, and hands them to the grouping of the 1M discovery
+ * (btbbx_le_discover_group_device) unchanged.  Air format, trellis, tie rule, lag and whitening are rules 2 to 7 of the coded
+ * decoder above ("the decoder's rule n" below); nothing of them is restated.  The contract is exact, without tolerances.
+ * Offset o of stream s is a CANDIDATE iff
+ *  1. CHANNEL.  ch = le_channel_index(phys_channel[s]) < 37 (an advertising channel yields no candidate).
+ *  2. RANGE.  o < search_bits; the argument check is btbbx_le_coded_scan_device's, search_bits + 335 <= 64 * n_words.
+ *  3. BLOCK 1.  The decoder's rule 3 from o + 80: 37 steps, traced back from state 0, give AA' (bits 0..31), ci (bits 32..33) and
+ *     metric1.
+ *  4. MATCH.  The 336 symbols from o differ from preamble + mapped, coded AA' in at most max_errors (0..63) places: rule 1 of the
+ *     coded scan with the DECODED address.  Not "some address exists": addresses that differ in their last bits lie 8 symbols
+ *     apart, so only the decoded one is determinate.  errors = that count.
+ *  5. ADDRESS.  AA' has no data-channel offense (aa_data_channel_offenses, as rule 3 of the 1M discovery).
+ *  6. S.  ci 0: S = 8.  ci 1: S = 2.  An RFU ci (2, 3) is no candidate.
+ *  7. HEADER.  The decoder's rule 5 (block 2 from o + 376, the lag decision behind step 40 from the best state) gives the
+ *     provisional dewhitened header h0, h1: (h0 & 3) != 0, (h0 & 0xe0) == 0 and h1 <= max_len (0..255).  L = h1.
+ *  8. FIT.  The packet lies in the stream: o + 376 + S * (8 * (L + 5) + 3) <= 64 * n_words.
+ *  9. BODY.  The decoder's rule 6: the forward pass goes on to step N = 8 * (L + 5) + 3, the path is traced back from state 0,
+ *     metric2 its metric.  header_moved must be 0: a path that disowns the length it was cut to is no candidate.
+ * 10. CRCINIT.  The one 24-bit preset, in the orientation btbbx_le_decode_hits_device takes, with which the CRC over the 2 + L
+ *     dewhitened octets of rule 9's path equals its 24 received CRC bits: the register run backwards, last octet first.
+ * 11. RECORD.  A btbbx_le_cand: offset = first preamble symbol, access_address = AA', crc_init, stream, header0 = h0, length = h1,
+ *     conn = ch -- what btbbx_le_discover_group_device asks of a list that is not the 1M scan's.  When d_info is not NULL a
+ *     btbbx_le_coded_cand_info is written at the same index.  The info records are parallel to THIS list only: the grouping
+ *     reorders the candidates in place and knows nothing of them.
+ * 12. WRITES.  Records [0, min(*d_cand_count, cand_cap)) are written whole, the reserved bytes as 0, and nothing else is written;
+ *     *d_cand_count counts every candidate, also those past cand_cap.  The records leave in no order.
+ * A true packet is a candidate when block 1 decodes to the address sent; symbol errors that make it decode to another address
+ * give a candidate of that other address or none (rule 4 decides), never one of the address sent.  Noise: a window passes rule
+ * 4 at max_errors 63 at about 1e-8 of the offsets before rules 5..9 apply.
+ * LIMITS, each one out of scope here: tracking coded candidates (btbbx_le_track_device closes an event by the 1M duration 80 + 8
+ * * length and needs the coded duration 376 + S * N first), ADV_EXT_IND / AuxPtr / AUX_CONNECT_REQ (extended advertising), soft
+ * decisions, the 2M PHY, and the lell_* entries, which still abort. */
+typedef struct btbbx_le_coded_cand_info {   /* 16 bytes, parallel to the btbbx_le_cand of the same index of the SCAN's list */
+	uint32_t symbols;      /* 376 + S * N, from the first preamble symbol */
+	uint32_t metric2;      /* symbol mismatches along block 2's path */
+	uint16_t metric1;      /* the same for block 1 */
+	uint8_t  errors;       /* rule 4's count */
+	uint8_t  ci, s;        /* CI as decoded (0, 1); 8 or 2 */
+	uint8_t  reserved[3];
+} btbbx_le_coded_cand_info;
+
+/* Rules 1..12 for offsets [0, search_bits) of every stream, two kernels on hip_stream: an address-free scan leaves pre-records
+ * (offset, stream, a lower bound of rule 4's count) in d_scratch, a decoder turns them into candidates.  d_scratch holds
+ * pre_cap = scratch_bytes / 16 pre-records, btbbx_le_cfind_scratch_bytes(pre_cap) = 16 * pre_cap bytes; *d_pre_count is cleared
+ * by the call and counts every pre-record: when it exceeds pre_cap the surplus was dropped and candidates may be missing -- call
+ * again with room.  *d_cand_count (zeroed by the caller) is added to.  Nothing is read back.  BTBBX_E_ARG: max_errors outside
+ * 0..63, max_len above 255, search_bits + 335 > 64 * n_words, n_streams outside 1..65535, pitch_words < n_words, a null pointer
+ * (d_cands may be NULL when cand_cap is 0, d_info always), scratch_bytes < 16, d_words or d_cands not 8-, d_info or d_scratch not
+ * 16-, a counter not 4-, d_phys_channel not 2-byte aligned.  (The entries are named le_cfind, "coded find".) */
+size_t btbbx_le_cfind_scratch_bytes(uint32_t pre_cap);
+int btbbx_le_cfind_scan_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			       uint64_t search_bits, const uint16_t *d_phys_channel, uint32_t max_len, int max_errors,
+			       btbbx_le_cand *d_cands, btbbx_le_coded_cand_info *d_info, uint32_t cand_cap, uint32_t *d_cand_count,
+			       uint32_t *d_pre_count, void *d_scratch, size_t scratch_bytes, void *hip_stream);
+
+/* Host wrapper, btbbx_le_discover_host's chain with this scan in it: copy in, scan (repeated with room when the pre-record list or
+ * the candidate list was short), btbbx_le_discover_group_device, copy out.  Returns, and fills conns, cands and *n_cands_out, as
+ * btbbx_le_discover_host does.  Safe to call from several host threads at once. */
+int64_t btbbx_le_cfind_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			    uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, int max_errors, uint32_t min_count,
+			    btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
+			    uint64_t *n_cands_out);
 
 /* ---- hop selection and CLK1-27 reversal ------------------------- */
 #define BTBBX_SEQUENCE_LENGTH 134217728u   /* values of CLK1-27, bluetooth_piconet.h:102 */

@@ -96,6 +96,10 @@ LE_CODED_LAG = 24
 LE_CODED_INFO_DTYPE = np.dtype([("symbols", "<u4"), ("metric2", "<u4"), ("metric1", "<u2"), ("ci", "u1"), ("s", "u1"),
                                 ("header_moved", "u1"), ("reserved", "u1", (3,))])
 assert LE_CODED_INFO_DTYPE.itemsize == 16
+# promiscuous LE Coded connection discovery (include/btbbx.h btbbx_le_cfind_*; le_cfind.h checks the C layout with a static_assert)
+LE_CODED_CAND_INFO_DTYPE = np.dtype([("symbols", "<u4"), ("metric2", "<u4"), ("metric1", "<u2"), ("errors", "u1"), ("ci", "u1"),
+                                     ("s", "u1"), ("reserved", "u1", (3,))])
+assert LE_CODED_CAND_INFO_DTYPE.itemsize == 16
 
 # LE connection discovery (include/btbbx.h btbbx_le_cand / btbbx_le_conn; le_discover.h checks the C layout with static_asserts)
 LE_CAND_DTYPE = np.dtype([("offset", "<u8"), ("access_address", "<u4"), ("crc_init", "<u4"), ("stream", "<u2"),
@@ -285,6 +289,9 @@ SIGNATURES = {
     "btbbx_le_coded_scratch_bytes": (C.c_size_t, [_u32]),
     "btbbx_le_coded_decode_hits_device": (C.c_int, [_vp, _u64, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, C.c_size_t, _vp]),
     "btbbx_le_coded_scan_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _u32, C.c_int, _vp, _vp, _u64]),
+    "btbbx_le_cfind_scratch_bytes": (C.c_size_t, [_u32]),
+    "btbbx_le_cfind_scan_device": (C.c_int, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, C.c_int, _vp, _vp, _u32, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "btbbx_le_cfind_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, C.c_int, _u32, _vp, _u64, _vp, _u64, _vp]),
     "btbbx_le_discover_scan_device": (C.c_int, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _vp, _u32, _vp, _vp]),
     "btbbx_le_discover_scratch_bytes": (C.c_size_t, [_u32]),
     "btbbx_le_discover_group_device": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _vp, C.c_size_t, _vp]),
@@ -583,6 +590,30 @@ def le_discover(words, search_bits, phys_channels, max_len=27, min_count=2, n_st
     n_cands = C.c_uint64(0)
     n = check(lib().btbbx_le_discover_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, _ptr(phys), max_len, min_count,
                                            _ptr(conns), conn_cap, _ptr(cands), cand_cap, C.byref(n_cands)), "btbbx_le_discover_host")
+    if (n > conn_cap or n_cands.value > cand_cap) and not truncate:
+        raise BtbbError("buffers too small: %d connections > %d or %d candidates > %d" % (n, conn_cap, n_cands.value, cand_cap))
+    return conns[:min(n, conn_cap)].copy(), cands[:min(n_cands.value, cand_cap)].copy()
+
+
+def le_coded_discover(words, search_bits, phys_channels, max_len=27, max_errors=16, min_count=2, n_streams=1, pitch_words=None,
+                      n_words=None, conn_cap=1 << 16, cand_cap=1 << 20, truncate=False):
+    """The LE Coded PHY connections of a data-channel capture, neither access address nor CRCInit given (include/btbbx.h,
+    promiscuous LE Coded connection discovery, rules 1..12): every offset whose block 1 decodes to an access address without
+    offense that the 336 symbols match within max_errors <= 63, with a plausible header of length <= max_len, a packet that fits and
+    the CRCInit that makes its CRC come out, grouped by (access address, CRCInit) by le_discover's grouping.  Arguments and the
+    returned (conns, cands) -- LE_CONN_DTYPE and LE_CAND_DTYPE -- as le_discover."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if pitch_words is None:
+        pitch_words = len(words) // n_streams
+    if n_words is None:
+        n_words = pitch_words
+    assert n_words <= pitch_words and (n_streams - 1) * pitch_words + n_words <= len(words)
+    phys = np.ascontiguousarray(np.broadcast_to(np.asarray(phys_channels, dtype=np.uint16), (n_streams,)))
+    conns = np.empty(max(conn_cap, 1), dtype=LE_CONN_DTYPE)          # (not zeroed: only the records returned are ever touched)
+    cands = np.empty(max(cand_cap, 1), dtype=LE_CAND_DTYPE)
+    n_cands = C.c_uint64(0)
+    n = check(lib().btbbx_le_cfind_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, _ptr(phys), max_len, max_errors,
+                                        min_count, _ptr(conns), conn_cap, _ptr(cands), cand_cap, C.byref(n_cands)), "btbbx_le_cfind_host")
     if (n > conn_cap or n_cands.value > cand_cap) and not truncate:
         raise BtbbError("buffers too small: %d connections > %d or %d candidates > %d" % (n, conn_cap, n_cands.value, cand_cap))
     return conns[:min(n, conn_cap)].copy(), cands[:min(n_cands.value, cand_cap)].copy()
