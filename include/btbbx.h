@@ -1590,7 +1590,8 @@ int64_t btbbx_le_coded_scan_host(const uint64_t *words, uint64_t n_words, uint64
  * 4 at max_errors 63 at about 1e-8 of the offsets before rules 5..9 apply.
  * LIMITS, each one out of scope here: tracking coded candidates (btbbx_le_track_device closes an event by the 1M duration 80 + 8
  * * length and needs the coded duration 376 + S * N first), ADV_EXT_IND / AuxPtr / AUX_CONNECT_REQ (extended advertising), soft
- * decisions, the 2M PHY, and the lell_* entries, which still abort. */
+ * decisions, the 2M PHY, and the lell_* entries, which still abort.  (The first of these is lifted by the stage behind this one,
+ * "LE Coded connection tracking" below: btbbx_le_ctrack_symbols_device and btbbx_le_ctrack_device.) */
 typedef struct btbbx_le_coded_cand_info {   /* 16 bytes, parallel to the btbbx_le_cand of the same index of the SCAN's list */
 	uint32_t symbols;      /* 376 + S * N, from the first preamble symbol */
 	uint32_t metric2;      /* symbol mismatches along block 2's path */
@@ -1621,6 +1622,60 @@ int64_t btbbx_le_cfind_host(const uint64_t *words, uint64_t n_words, uint64_t pi
 			    uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, int max_errors, uint32_t min_count,
 			    btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands, uint64_t cand_cap,
 			    uint64_t *n_cands_out);
+
+/* ---- LE Coded connection tracking: coded durations, events, hop check ------------------------
+ * btbbx_le_track_device closes a connection event by the 1M duration 80 + 8 * length.  A coded packet lasts 376 + S * N symbols,
+ * 8 to 70 times as long (an empty PDU: 720 symbols at S = 8; 255 octets: 17040), so on coded candidates every reply opens an
+ * event of its own, the event spacings leave the 1.25 ms grid, the connection is not TIMED and btbbx_le_csa2_device evaluates
+ * nothing.  Only the tracking's rule 3 reads a duration.  This stage computes the duration of every candidate of a list AS IT
+ * STANDS -- behind the grouping, which reorders the list in place and leaves the discovery's info records behind -- and runs the
+ * tracking with rule 3 taking it.  Trellis and tie rule are the coded decoder's rules 2 and 3 ("LE Coded PHY scan" above); nothing
+ * of them is restated.  With N = min(*d_cand_count, cand_cap), for every i < N:
+ *  1. STREAM.  cands[i].stream >= n_streams: symbols_i = 0.
+ *  2. CI.  Otherwise the decoder's rule 3 at o = cands[i].offset: 37 steps of 8 symbols from o + 80, symbols past the stream's end
+ *     read as 0 (an offset beyond the stream reads nothing but zeros), predecessor x = 0 on equal sums, traced back from state 0;
+ *     ci = bits 32..33.  Block 1 is not whitened: no channel is needed, and an advertising stream is decoded like any other.
+ *  3. S.  ci 0: S = 8.  ci 1: S = 2.  With L = cands[i].length, symbols_i = 376 + S * (8 * (L + 5) + 3).  An RFU ci (2, 3):
+ *     symbols_i = 376, the decoder's rule 4.
+ *  4. WRITES.  d_symbols[0 .. N) is written and nothing else; the count stays on the device, nothing is read back.
+ * For a candidate that btbbx_le_cfind_scan_device produced, symbols_i equals the symbols of its btbbx_le_coded_cand_info.
+ * Offsets lie below 2^48 (the grouping's promise); all address arithmetic is 64 bits wide.
+ * TRACKING.  btbbx_le_ctrack_device is btbbx_le_track_device -- its rules 1, 2 and 4 to 7 word for word, its records, its flags,
+ * btbbx_le_track_scratch_bytes, its launch count -- with rule 3 changed to end_m = offset_m + d_symbols[m] (a 64-bit sum; m = the
+ * candidate's index in the list).  With d_symbols[i] = 80 + 8 * cands[i].length every output byte equals btbbx_le_track_device's.
+ * LIMITS, each one out of scope here: feeding coded connections to the seed, follow, span, data, decryption or pairing stages
+ * (they read payloads as 1M bits from the streams); LL_PHY_UPDATE_IND and connections that change PHY inside the capture (one
+ * list, one kind of duration); ADV_EXT_IND, AuxPtr and AUX_CONNECT_REQ; soft decisions; the 2M PHY; the lell_* entries, which
+ * still abort.  (The entries are named le_ctrack, "coded track".) */
+
+/* Rules 1..4, one kernel on hip_stream.  BTBBX_E_ARG, before any launch: a null pointer with cand_cap != 0, d_words or d_cands
+ * not 8-, d_symbols or the counter not 4-byte aligned, n_streams outside 1..65535, pitch_words < n_words, n_words > 2^40.
+ * cand_cap == 0 succeeds and writes nothing. */
+int btbbx_le_ctrack_symbols_device(const uint64_t *d_words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+				   const btbbx_le_cand *d_cands, const uint32_t *d_cand_count, uint32_t cand_cap,
+				   uint32_t *d_symbols, void *hip_stream);
+
+/* The tracking with per-candidate durations.  Arguments, promises, writes and BTBBX_E_ARG as btbbx_le_track_device; in addition
+ * d_symbols (N dwords, parallel to d_cands) must not be NULL and must be 4-byte aligned. */
+int btbbx_le_ctrack_device(const btbbx_le_cand *d_cands, const uint32_t *d_cand_count, uint32_t cand_cap,
+			   const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
+			   const uint16_t *d_phys_channel, uint32_t n_streams, const uint32_t *d_symbols,
+			   uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+			   btbbx_le_track *d_tracks, btbbx_le_track_pkt *d_pkts,
+			   void *d_scratch, size_t scratch_bytes, void *hip_stream);
+
+/* Host wrapper, btbbx_le_cfind_host's chain -- copy in, the coded scan repeated with room, the grouping -- with the durations of
+ * the sorted list, the tracking that takes them and btbbx_le_csa2_device behind it on the same stream, then the copy-out.  Returns,
+ * and fills conns, cands and *n_cands_out, as btbbx_le_cfind_host does; tracks and sel are parallel to conns, pkts, sel_pkts and
+ * symbols to cands, as in btbbx_le_csa2_host.  pkts, sel_pkts and symbols may be NULL; when sel is NULL channel selection #2 is
+ * not queued (and sel_pkts not touched).  When no connection was stored, pkts and sel_pkts get the 0xff fill of the 1M wrappers
+ * (no candidate is a member); symbols holds the durations all the same.  Safe to call from several host threads at once. */
+int64_t btbbx_le_ctrack_host(const uint64_t *words, uint64_t n_words, uint64_t pitch_words, uint32_t n_streams,
+			     uint64_t search_bits, const uint16_t *phys_channel, uint32_t max_len, int max_errors,
+			     uint32_t min_count, btbbx_le_conn *conns, uint64_t conn_cap, btbbx_le_cand *cands,
+			     uint64_t cand_cap, uint64_t *n_cands_out, uint32_t unit_bits, uint32_t ifs_bits,
+			     uint32_t jitter_bits, uint32_t flags, btbbx_le_track *tracks, btbbx_le_track_pkt *pkts,
+			     btbbx_le_csa2 *sel, btbbx_le_csa2_pkt *sel_pkts, uint32_t *symbols);
 
 /* ---- hop selection and CLK1-27 reversal ------------------------- */
 #define BTBBX_SEQUENCE_LENGTH 134217728u   /* values of CLK1-27, bluetooth_piconet.h:102 */

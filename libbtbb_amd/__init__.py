@@ -292,6 +292,10 @@ SIGNATURES = {
     "btbbx_le_cfind_scratch_bytes": (C.c_size_t, [_u32]),
     "btbbx_le_cfind_scan_device": (C.c_int, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, C.c_int, _vp, _vp, _u32, _vp, _vp, _vp, C.c_size_t, _vp]),
     "btbbx_le_cfind_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, C.c_int, _u32, _vp, _u64, _vp, _u64, _vp]),
+    "btbbx_le_ctrack_symbols_device": (C.c_int, [_vp, _u64, _u64, _u32, _vp, _vp, _u32, _vp, _vp]),
+    "btbbx_le_ctrack_device": (C.c_int, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "btbbx_le_ctrack_host": (C.c_int64, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, C.c_int, _u32, _vp, _u64, _vp, _u64, _vp, _u32, _u32, _u32, _u32,
+                                         _vp, _vp, _vp, _vp, _vp]),
     "btbbx_le_discover_scan_device": (C.c_int, [_vp, _u64, _u64, _u32, _u64, _vp, _u32, _vp, _u32, _vp, _vp]),
     "btbbx_le_discover_scratch_bytes": (C.c_size_t, [_u32]),
     "btbbx_le_discover_group_device": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _vp, C.c_size_t, _vp]),
@@ -674,6 +678,36 @@ def le_csa2(words, search_bits, phys_channels, max_len=27, min_count=2, n_stream
         raise BtbbError("buffers too small: %d connections > %d or %d candidates > %d" % (n, conn_cap, n_cands.value, cand_cap))
     nc, nk = min(n, conn_cap), min(n_cands.value, cand_cap)
     return conns[:nc].copy(), cands[:nk].copy(), tracks[:nc].copy(), pkts[:nk].copy(), sel[:nc].copy(), sel_pkts[:nk].copy()
+
+
+def le_coded_track(words, search_bits, phys_channels, max_len=27, max_errors=16, min_count=2, n_streams=1, pitch_words=None, n_words=None,
+                   unit_bits=1250, ifs_bits=200, jitter_bits=50, flags=LE_CSA2_REMAP, conn_cap=1 << 12, cand_cap=1 << 20, truncate=False):
+    """le_coded_discover, then the duration of every coded candidate, the tracking with rule 3 taking it and channel selection
+    algorithm #2 (include/btbbx.h, LE Coded connection tracking: btbbx_le_ctrack_host).  le_coded_discover's and le_csa2's parameters.
+    Returns what le_csa2 returns, plus symbols: (conns, cands, tracks, pkts, sel, sel_pkts, symbols), symbols a uint32 array
+    parallel to cands -- 376 + S * (8 * (length + 5) + 3) symbols from the first preamble symbol."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    if pitch_words is None:
+        pitch_words = len(words) // n_streams
+    if n_words is None:
+        n_words = pitch_words
+    assert n_words <= pitch_words and (n_streams - 1) * pitch_words + n_words <= len(words)
+    phys = np.ascontiguousarray(np.broadcast_to(np.asarray(phys_channels, dtype=np.uint16), (n_streams,)))
+    conns = np.empty(max(conn_cap, 1), dtype=LE_CONN_DTYPE)
+    tracks = np.empty(max(conn_cap, 1), dtype=LE_TRACK_DTYPE)
+    sel = np.empty(max(conn_cap, 1), dtype=LE_CSA2_DTYPE)
+    cands = np.empty(max(cand_cap, 1), dtype=LE_CAND_DTYPE)
+    pkts = np.empty(max(cand_cap, 1), dtype=LE_TRACK_PKT_DTYPE)
+    sel_pkts = np.empty(max(cand_cap, 1), dtype=LE_CSA2_PKT_DTYPE)
+    symbols = np.empty(max(cand_cap, 1), dtype=np.uint32)
+    n_cands = C.c_uint64(0)
+    n = check(lib().btbbx_le_ctrack_host(_ptr(words), n_words, pitch_words, n_streams, search_bits, _ptr(phys), max_len, max_errors, min_count,
+                                         _ptr(conns), conn_cap, _ptr(cands), cand_cap, C.byref(n_cands), unit_bits, ifs_bits, jitter_bits,
+                                         flags, _ptr(tracks), _ptr(pkts), _ptr(sel), _ptr(sel_pkts), _ptr(symbols)), "btbbx_le_ctrack_host")
+    if (n > conn_cap or n_cands.value > cand_cap) and not truncate:
+        raise BtbbError("buffers too small: %d connections > %d or %d candidates > %d" % (n, conn_cap, n_cands.value, cand_cap))
+    nc, nk = min(n, conn_cap), min(n_cands.value, cand_cap)
+    return conns[:nc].copy(), cands[:nk].copy(), tracks[:nc].copy(), pkts[:nk].copy(), sel[:nc].copy(), sel_pkts[:nk].copy(), symbols[:nk].copy()
 
 
 def le_follow(words, search_bits, phys_channels, max_len=27, min_count=2, n_streams=1, pitch_words=None, n_words=None,

@@ -17,6 +17,7 @@
 #pragma once
 #include "radix_sort.h"
 #include "wave_scan.h"
+#include "le_slots.h"
 
 #define LD_RING      128                   // per-wave ring of header-tested survivors (entries)
 #define LD_GRP_TILE  2048u                 // records (or groups) a workgroup flags per launch (8 rounds of 256)
@@ -356,17 +357,7 @@ static LeDiscLayout le_disc_layout(uint32_t cap)
 	return L;
 }
 
-struct LdCand { uint2 a, b, c; };           // a btbbx_le_cand as the three 8-byte words it is moved in
-
-__device__ __forceinline__ LdCand ld_load(const btbbx_le_cand *c, uint32_t i)
-{
-	const uint2 *p = reinterpret_cast<const uint2 *>(c + i);
-	LdCand r;
-	r.a = p[0];
-	r.b = p[1];
-	r.c = p[2];
-	return r;
-}
+// (LdCand and ld_load: le_slots.h, which the coded tracking's unit includes as well)
 
 __device__ __forceinline__ void ld_store(btbbx_le_cand *c, uint32_t i, const LdCand &r)
 {

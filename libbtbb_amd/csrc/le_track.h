@@ -21,9 +21,13 @@
 #pragma once
 #include "radix_sort.h"
 #include "wave_scan.h"
+#include "le_slots.h"
 #include <string.h>
 
+static_assert(LT_THREADS == LE_THREADS, "a slot pass's workgroup");
 #define LT_TILE        2048u               // slots (or events) a workgroup scans per launch (8 rounds of 256)
+static_assert(LT_TILE % LT_THREADS == 0, "whole rounds");
+// (LT_INFO_EVENT and lt_member_of: le_slots.h)
 #define LT_SCORE_TILE  1024u               // events a workgroup of the scoring pass votes for (4 rounds of 256)
 #define LT_PAIRS       444u                // 12 hop increments x 37 first unmapped channels
 #define LT_WAVES       (LE_THREADS / 64)
@@ -185,17 +189,6 @@ __global__ __launch_bounds__(LE_THREADS) void le_track_key_kernel(const btbbx_le
 	vals[i] = i;
 }
 
-// rule 1: the connection a candidate is a member of, K for none
-__device__ __forceinline__ uint32_t lt_member_of(uint2 c, const uint16_t *phys, uint32_t n_streams, uint32_t k, uint32_t &ch)
-{
-	const uint32_t stream = c.x & 0xffffu;
-	ch = 0xff;
-	if (c.y >= k || stream >= n_streams)
-		return k;
-	ch = le_channel_index(phys[stream]);
-	return ch < 37 ? c.y : k;
-}
-
 // second sort key, of the slots in (offset, stream) order: the connection index, K for a candidate that is no member
 __global__ __launch_bounds__(LE_THREADS) void le_track_rekey_kernel(const btbbx_le_cand *cands, const uint32_t *params, const uint32_t *vals,
 								    const uint16_t *phys, uint32_t n_streams, uint64_t *keys)
@@ -208,8 +201,6 @@ __global__ __launch_bounds__(LE_THREADS) void le_track_rekey_kernel(const btbbx_
 }
 
 // ---- 2. events --------------------------------------------------------------------------------------------------------
-
-#define LT_INFO_EVENT 0x100u               // info[j]: the channel index in the low byte, this bit where slot j opens an event
 
 // rule 3 for every slot against the slot in front of it; events that begin in every tile of LT_TILE slots
 __global__ __launch_bounds__(LE_THREADS) void le_track_flag_kernel(const btbbx_le_cand *cands, const uint64_t *keys, const uint32_t *vals,
@@ -618,10 +609,12 @@ static int le_conn_passes(uint32_t conn_cap)
 	return passes;
 }
 
-// the launches of one tracking run: 24 + 3 per eight bits of conn_cap for the two sorts, 13 of its own
+// the launches of one tracking run: 24 + 3 per eight bits of conn_cap for the two sorts, 13 of its own.  stand_in (null: the
+// flag pass above) enqueues the flag pass in its place, as the coded tracking does, whose rule 3 reads a duration per candidate
 static int le_track_launch(const btbbx_le_cand *d_cands, const uint32_t *d_count, uint32_t cap, const uint32_t *d_conn_count, uint32_t conn_cap,
 			   const uint16_t *d_phys, uint32_t n_streams, uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
-			   btbbx_le_track *d_tracks, btbbx_le_track_pkt *d_pkts, void *d_scratch, hipStream_t q)
+			   btbbx_le_track *d_tracks, btbbx_le_track_pkt *d_pkts, void *d_scratch, hipStream_t q,
+			   const LtFlagStandIn *stand_in = nullptr)
 {
 	const LtLayout L = le_track_layout(cap, conn_cap);
 	char *s = (char *)d_scratch;
@@ -641,7 +634,12 @@ static int le_track_launch(const btbbx_le_cand *d_cands, const uint32_t *d_count
 	cur = le_sort_bytes(b, le_conn_passes(conn_cap), cur, q);
 	const uint64_t *keys = b.keys[cur];
 	const uint32_t *vals = b.vals[cur];
-	hipLaunchKernelGGL(le_track_flag_kernel, per_tile, wg, 0, q, d_cands, keys, vals, params, d_phys, n_streams, ifs_bits, info, tiles);
+	if (stand_in) {
+		const LtFlagPass pass = {d_cands, keys, vals, params, d_phys, n_streams, ifs_bits, info, tiles, L.tiles_n, LT_TILE, q};
+		stand_in->enqueue(pass, stand_in->user);
+	} else {
+		hipLaunchKernelGGL(le_track_flag_kernel, per_tile, wg, 0, q, d_cands, keys, vals, params, d_phys, n_streams, ifs_bits, info, tiles);
+	}
 	hipLaunchKernelGGL(le_track_prefix_kernel, dim3(1), wg, 0, q, tiles, L.tiles_n, params);
 	hipLaunchKernelGGL(le_track_event_kernel, per_tile, wg, 0, q, d_cands, keys, vals, params, info, tiles, evidx, ekey, econn, work);
 	hipLaunchKernelGGL(le_track_interval_kernel, per_cand, wg, 0, q, ekey, econn, params, unit_bits, jitter_bits, work);
@@ -655,14 +653,15 @@ static int le_track_launch(const btbbx_le_cand *d_cands, const uint32_t *d_count
 	return BTBBX_OK;
 }
 
-extern "C" int btbbx_le_track_device(const btbbx_le_cand *d_cands, const uint32_t *d_cand_count, uint32_t cand_cap,
-				     const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
-				     const uint16_t *d_phys_channel, uint32_t n_streams,
-				     uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
-				     btbbx_le_track *d_tracks, btbbx_le_track_pkt *d_pkts,
-				     void *d_scratch, size_t scratch_bytes, void *hip_stream)
+// btbbx_le_track_device's checks and launches under the name `who`, with a stand-in for the flag pass or none.  Not exported:
+// the coded tracking's unit (le_ctrack.h) reaches le_track_launch through it
+int le_track_run(const char *who, const btbbx_le_cand *d_cands, const uint32_t *d_cand_count, uint32_t cand_cap,
+		 const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
+		 const uint16_t *d_phys_channel, uint32_t n_streams,
+		 uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+		 btbbx_le_track *d_tracks, btbbx_le_track_pkt *d_pkts,
+		 void *d_scratch, size_t scratch_bytes, void *hip_stream, const LtFlagStandIn *stand_in)
 {
-	const char *who = "btbbx_le_track_device";
 	int rc = le_track_check_args(who, n_streams, unit_bits, jitter_bits);
 	if (rc)
 		return rc;
@@ -683,5 +682,16 @@ extern "C" int btbbx_le_track_device(const btbbx_le_cand *d_cands, const uint32_
 	if (!cand_cap || !conn_cap)
 		return BTBBX_OK;
 	return le_track_launch(d_cands, d_cand_count, cand_cap, d_conn_count, conn_cap, d_phys_channel, n_streams, unit_bits, ifs_bits,
-			       jitter_bits, flags, d_tracks, d_pkts, d_scratch, (hipStream_t)hip_stream);
+			       jitter_bits, flags, d_tracks, d_pkts, d_scratch, (hipStream_t)hip_stream, stand_in);
+}
+
+extern "C" int btbbx_le_track_device(const btbbx_le_cand *d_cands, const uint32_t *d_cand_count, uint32_t cand_cap,
+				     const btbbx_le_conn *d_conns, const uint32_t *d_conn_count, uint32_t conn_cap,
+				     const uint16_t *d_phys_channel, uint32_t n_streams,
+				     uint32_t unit_bits, uint32_t ifs_bits, uint32_t jitter_bits, uint32_t flags,
+				     btbbx_le_track *d_tracks, btbbx_le_track_pkt *d_pkts,
+				     void *d_scratch, size_t scratch_bytes, void *hip_stream)
+{
+	return le_track_run("btbbx_le_track_device", d_cands, d_cand_count, cand_cap, d_conns, d_conn_count, conn_cap, d_phys_channel, n_streams,
+			    unit_bits, ifs_bits, jitter_bits, flags, d_tracks, d_pkts, d_scratch, scratch_bytes, hip_stream, nullptr);
 }

@@ -1,0 +1,290 @@
+"""The LE Coded connection tracking (libbtbb_amd/csrc/le_ctrack.h) on the GPU against the model (tests/_le_ctrack.py): every
+duration, every byte of the tracking's records with rule 3 taking durations, the equivalence with btbbx_le_track_device under 1M
+durations, and the chain -- the test that fails on the tracking as it stood: on coded connections it reports twice the events and
+times nothing.  Output buffers start as 0xA5 and are longer than their caps, so a byte a kernel leaves unwritten, or writes where
+it should not, shows.  tests/test_le_ctrack_model.py shows what the lists hold and that they tell every wrong variant from the
+model."""
+import functools
+
+import numpy as np
+import pytest
+
+import _le_csa2 as c2
+import _le_ctrack as m
+import _le_discover as ld
+import _le_track as lt
+import libbtbb_amd as bt
+from test_gpu_le_track import _dev, _filled, _track_device
+
+pytestmark = pytest.mark.gpu
+
+CAND, CONN, TRACK, PKT, SEL, SEL_PKT = (bt.LE_CAND_DTYPE, bt.LE_CONN_DTYPE, bt.LE_TRACK_DTYPE, bt.LE_TRACK_PKT_DTYPE, bt.LE_CSA2_DTYPE,
+                                        bt.LE_CSA2_PKT_DTYPE)
+GUARD = 5                                                  # dwords behind the durations that must stay as they were
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _init():
+    torch = pytest.importorskip("torch")
+    assert torch.cuda.is_available()
+    torch.cuda.set_device(0)
+    bt.init(2)
+
+
+def _cand_arr(cands):
+    arr = np.zeros(len(cands), CAND)
+    if len(cands):
+        fields = np.array(cands, dtype=np.int64)
+        for k, name in enumerate(("offset", "access_address", "crc_init", "stream", "header0", "length", "conn")):
+            arr[name] = fields[:, k]
+    return arr
+
+
+def _symbols_device(d_words, n_words, pitch_words, n_streams, cands, count=None, cand_cap=None):
+    """btbbx_le_ctrack_symbols_device -> the durations buffer, GUARD dwords longer than cand_cap; it was 0xA5."""
+    import torch
+    n = len(cands)
+    count = n if count is None else count
+    cand_cap = n if cand_cap is None else cand_cap
+    d_cands = _dev(_cand_arr(cands))
+    d_cnt = torch.from_numpy(np.array([count, 0xA5A5A5A5], np.int64).astype(np.uint32).view(np.int32)).cuda()
+    d_sym = torch.full((4 * (cand_cap + GUARD),), 0xA5, dtype=torch.uint8, device="cuda")
+    bt.check(bt.lib().btbbx_le_ctrack_symbols_device(d_words.data_ptr(), n_words, pitch_words, n_streams, d_cands.data_ptr(), d_cnt.data_ptr(), cand_cap,
+                                                     d_sym.data_ptr(), None), "btbbx_le_ctrack_symbols_device")
+    torch.cuda.synchronize()
+    assert d_cnt.cpu().numpy().view(np.uint32).tolist() == [count, 0xA5A5A5A5]
+    return d_sym.cpu().numpy().view(np.uint32)
+
+
+def _check_symbols(d_words, n_words, pitch_words, n_streams, cands, want, count=None, cand_cap=None):
+    got = _symbols_device(d_words, n_words, pitch_words, n_streams, cands, count, cand_cap)
+    work = min(len(cands) if count is None else count, len(cands) if cand_cap is None else cand_cap)
+    if got[:work].tolist() != list(want[:work]):
+        bad = [i for i in range(work) if got[i] != want[i]]
+        raise AssertionError("candidate %d %s: %d, model %d (%d differ)" % (bad[0], cands[bad[0]], got[bad[0]], want[bad[0]], len(bad)))
+    assert (got[work:] == 0xA5A5A5A5).all() and len(got) == (len(cands) if cand_cap is None else cand_cap) + GUARD
+
+
+# ---- the duration --------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _lattice():
+    words, cands, notes = m.symbols_lattice()
+    return words, cands, notes, m.symbols(words, m.SYM_WORDS, cands, 1)
+
+
+def test_durations_on_the_lattice():
+    """All 64 offset residues, S = 8 and S = 2, L in {0, 1, 27, 255}, ci 2 and 3, symbol errors in the CI, offsets beyond the stream,
+    streams out of range; pitch_words above n_words with noise behind the stream's end."""
+    words, cands, notes, want = _lattice()
+    assert words.shape[1] > m.SYM_WORDS and len(cands) >= 90
+    d_words = _dev(words)
+    _check_symbols(d_words, m.SYM_WORDS, words.shape[1], 1, cands, want)
+    # two streams of half the words each: stream 1 is in range now and begins at pitch_words
+    half = m.SYM_WORDS // 2
+    want2 = m.symbols(words.reshape(-1)[:2 * half].reshape(2, half), half, cands, 2)
+    assert want2 != want
+    _check_symbols(d_words, half, half, 2, cands, want2)
+    print("%d candidates, durations %s" % (len(cands), sorted(set(want))))
+
+
+@pytest.mark.parametrize("size", [0, 1, 63, 64, 65, 257])
+def test_list_sizes_and_caps(size):
+    words, cands, notes, want = _lattice()
+    many = (cands * 3)[:size]
+    wanted = (want * 3)[:size]
+    d_words = _dev(words)
+    _check_symbols(d_words, m.SYM_WORDS, words.shape[1], 1, many, wanted)
+    if size:
+        _check_symbols(d_words, m.SYM_WORDS, words.shape[1], 1, many, wanted, count=size + 1000, cand_cap=size - 1)     # a count above cand_cap
+        _check_symbols(d_words, m.SYM_WORDS, words.shape[1], 1, many, wanted, count=size // 2)
+    else:
+        import torch
+        d_sym = torch.full((32,), 0xA5, dtype=torch.uint8, device="cuda")
+        assert bt.lib().btbbx_le_ctrack_symbols_device(None, 64, 64, 1, None, None, 0, None, None) == 0          # cand_cap 0: nothing is needed
+        assert bt.lib().btbbx_le_ctrack_symbols_device(d_words.data_ptr(), 64, 64, 1, d_words.data_ptr(), d_words.data_ptr(), 0, d_sym.data_ptr(), None) == 0
+        torch.cuda.synchronize()
+        assert (d_sym.cpu().numpy() == 0xA5).all()
+
+
+def test_block_1_on_and_past_the_streams_end():
+    for words, n_words, cands in m.end_cases():
+        want = m.symbols(words, n_words, cands, 1)
+        _check_symbols(_dev(words), n_words, words.shape[1], 1, cands, want)
+
+
+def test_offsets_beyond_2_to_the_32():
+    """Two streams, pitch_words just above 2^26 (1 GiB of zeros in HBM), one packet copied into stream 1 at bit 2^32 + 37: the stream
+    offset lies beyond 2^32 bits and the byte address beyond 2^32 bytes."""
+    import torch
+    words, cands, notes, _ = _lattice()
+    src = next(cd for cd, n in zip(cands, notes) if n == "residue 1")         # S = 2
+    pitch, n_words = (1 << 26) + 64, (1 << 26) + 32
+    at = (1 << 32) + 37
+    first, last = src.offset >> 6, (src.offset + 400 + 63) >> 6
+    sym = np.unpackbits(np.ascontiguousarray(words[0, first:last + 1]).view(np.uint8), bitorder="little")[src.offset - 64 * first:][:400]
+    line = np.zeros(64 * 9, np.uint8)
+    line[at % 64:at % 64 + 400] = sym
+    piece = m._le.pack(line)
+    d_words = torch.zeros(2 * pitch, dtype=torch.int64, device="cuda")
+    w0 = pitch + (at >> 6)
+    d_words[w0:w0 + len(piece)] = torch.from_numpy(piece.view(np.int64)).cuda()
+
+    class Sparse:                                                           # the two streams as the model reads them
+        def __getitem__(self, key):
+            s, sl = key
+            out = np.zeros(sl.stop - sl.start, np.uint64)
+            if s == 1:
+                for k in range(len(piece)):
+                    if sl.start <= (at >> 6) + k < sl.stop:
+                        out[(at >> 6) + k - sl.start] = piece[k]
+            return out
+
+    moved = [src._replace(offset=at, stream=1), src._replace(offset=at, stream=0), src._replace(offset=at - 64, stream=1),
+             src._replace(offset=64 * n_words - 200, stream=1), src._replace(offset=at, stream=2)]
+    want = m.symbols(Sparse(), n_words, moved, 2)
+    assert want[0] == m.coded_duration(2, src.length) and want[1] == 720 and want[4] == 0
+    _check_symbols(d_words, n_words, pitch, 2, moved, want)
+
+
+# ---- the flag pass with durations ----------------------------------------------------------------------------------------
+def _ctrack_device(cand_arr, conn_arr, mhz, n_streams, flags, durations, unit=m.UNIT, ifs=m.IFS, jitter=m.JITTER):
+    """btbbx_le_ctrack_device over a grouped list -> (tracks buffer, pkts buffer), whole, one record longer than their caps."""
+    import torch
+    lib = bt.lib()
+    n, k = len(cand_arr), len(conn_arr)
+    d_cands, d_conns, d_phys = _dev(cand_arr), _dev(conn_arr), _dev(np.asarray(mhz, np.uint16))
+    d_sym = _dev(np.asarray(durations, np.uint32))
+    d_tracks, d_pkts = _filled((k + 1) * TRACK.itemsize), _filled((n + 1) * PKT.itemsize)
+    d_cnt = torch.from_numpy(np.array([n, k], np.int64).astype(np.uint32).view(np.int32)).cuda()
+    scratch = lib.btbbx_le_track_scratch_bytes(n, k)
+    d_scr = _filled(scratch)
+    bt.check(lib.btbbx_le_ctrack_device(d_cands.data_ptr(), d_cnt.data_ptr(), n, d_conns.data_ptr(), d_cnt.data_ptr() + 4, k, d_phys.data_ptr(),
+                                        n_streams, d_sym.data_ptr(), unit, ifs, jitter, flags, d_tracks.data_ptr(), d_pkts.data_ptr(),
+                                        d_scr.data_ptr(), scratch, None), "btbbx_le_ctrack_device")
+    torch.cuda.synchronize()
+    assert d_sym.cpu().numpy().view(np.uint32)[:n].tolist() == list(durations)
+    return d_tracks.cpu().numpy()[:(k + 1) * TRACK.itemsize].view(TRACK), d_pkts.cpu().numpy()[:(n + 1) * PKT.itemsize].view(PKT)
+
+
+def _check_track(conns, cands, durations, flags=lt.REMAP, names=None):
+    want = m.track(cands, len(conns), lt.LATTICE_MHZ, lt.N_STREAMS, m.UNIT, m.IFS, m.JITTER, flags, durations)
+    tracks, pkts = _ctrack_device(_cand_arr(cands), ld.conn_array(conns, CONN), lt.LATTICE_MHZ, lt.N_STREAMS, flags, durations)
+    n, k = len(cands), len(conns)
+    want_t, want_p = lt.track_array(want[0], TRACK), lt.pkt_array(want[1], PKT)
+    if tracks[:k].tobytes() != want_t.tobytes():
+        bad = [g for g in range(k) if tracks[g].tobytes() != want_t[g].tobytes()]
+        raise AssertionError("connection %d (%s): %s, model %s (%d differ)" % (bad[0], names[bad[0]] if names else "", tracks[bad[0]], want_t[bad[0]], len(bad)))
+    if pkts[:n].tobytes() != want_p.tobytes():
+        bad = [i for i in range(n) if pkts[i].tobytes() != want_p[i].tobytes()]
+        raise AssertionError("candidate %d %s: %s, model %s (%d differ)" % (bad[0], cands[bad[0]], pkts[bad[0]], want_p[bad[0]], len(bad)))
+    assert tracks[k:].tobytes() == b"\xa5" * TRACK.itemsize and pkts[n:].tobytes() == b"\xa5" * PKT.itemsize
+    return want
+
+
+@pytest.mark.parametrize("flags", [0, lt.REMAP])
+def test_rule_3_with_durations_on_the_flag_list(flags):
+    """Request and reply on each side of a wave seam (slots 63 | 64, 127 | 128) and a tile seam (2047 | 2048, 4095 | 4096), a gap of
+    exactly end + ifs and one more, duration 0, 17 040 symbols reaching past the next start, a channel change inside the gap, a
+    non-member between two members, offsets just below 2^48 whose end carries across 2^32."""
+    conns, cands, durations, names = m.flag_list()
+    want = _check_track(conns, cands, durations, flags, names)
+    assert [t.n_events for t in want[0][:4]] == [40, 30, 1100, 1000]
+
+
+@pytest.mark.parametrize("name", ["align A", "crowd", "long events"])
+def test_coded_durations_on_the_tracking_lists(name):
+    """The tracking's own alignment, crowd and long-event lists with coded durations (S by the offset's parity)."""
+    conns, cands = {"align A": lambda: lt.align_list("A"), "crowd": lt.crowd_list, "long events": lt.long_event_list}[name]()[:2]
+    durations = m.coded_durations_of(cands)
+    want = _check_track(conns, cands, durations)
+    print("%s: %d candidates, %d events" % (name, len(cands), sum(t.n_events for t in want[0])))
+
+
+@pytest.mark.parametrize("name", ["lattice", "seam"])
+def test_one_m_durations_give_the_trackings_bytes(name):
+    """With d_symbols[i] = 80 + 8 * length the output of btbbx_le_ctrack_device equals that of btbbx_le_track_device, byte for byte."""
+    conns, cands = (lt.lattice_list(2) if name == "lattice" else lt.seam_list())[:2]
+    cand_arr, conn_arr = _cand_arr(cands), ld.conn_array(conns, CONN)
+    for flags in (0, lt.REMAP):
+        t1, p1 = _track_device(cand_arr, conn_arr, lt.LATTICE_MHZ, lt.N_STREAMS, flags)
+        t2, p2 = _ctrack_device(cand_arr, conn_arr, lt.LATTICE_MHZ, lt.N_STREAMS, flags, m.one_m_durations(cands))
+        assert t1.tobytes() == t2.tobytes() and p1.tobytes() == p2.tobytes()
+        assert any(t["flags"] & lt.HOPPING for t in t2[:len(conns)])
+
+
+# ---- the chain -------------------------------------------------------------------------------------------------------------
+def test_chain_coded_discovery_then_tracking_then_selection():
+    """Two coded connections over eight streams, one hopping by algorithm #1 and one by #2: the device chain and the wrapper give the
+    model's bytes; btbbx_le_track_device on the same sorted list reports twice the events and no TIMED flag."""
+    import torch
+    lib = bt.lib()
+    cap, planted = m.chain_capture()
+    conns, cands, info, durations, tracks, pkts, sels, sel_pkts = m.chain_model()
+    n, k = len(cands), len(conns)
+    want = dict(conns=ld.conn_array(conns, CONN), cands=_cand_arr(cands), tracks=lt.track_array(tracks, TRACK), pkts=lt.pkt_array(pkts, PKT),
+                sel=c2.sel_array(sels, SEL), sel_pkts=c2.sel_pkt_array(sel_pkts, SEL_PKT), symbols=np.array(durations, np.uint32))
+    assert want["cands"].tobytes() == ld.cand_array(cands, CAND).tobytes()
+    # device-resident: scan with info records, group, durations, tracking, selection
+    alloc, pre_cap, n_streams = n + 4, 4096, len(cap.mhz)
+    d_words, d_phys = _dev(cap.words), _dev(cap.mhz)
+    d_cands, d_info, d_conns = _filled(alloc * CAND.itemsize), _filled(alloc * 16), _filled(alloc * CONN.itemsize)
+    d_cnt = torch.zeros(8, dtype=torch.int32, device="cuda")
+    d_pre = torch.zeros(16 * pre_cap, dtype=torch.uint8, device="cuda")
+    bt.check(lib.btbbx_le_cfind_scan_device(d_words.data_ptr(), cap.n_words, cap.pitch_words, n_streams, cap.search_bits, d_phys.data_ptr(), 27, 16,
+                                            d_cands.data_ptr(), d_info.data_ptr(), alloc, d_cnt.data_ptr(), d_cnt.data_ptr() + 4, d_pre.data_ptr(),
+                                            16 * pre_cap, None))
+    torch.cuda.synchronize()
+    assert int(d_cnt[0]) == n
+    scan_cands = d_cands.cpu().numpy()[:n * CAND.itemsize].view(CAND)
+    scan_info = d_info.cpu().numpy()[:n * 16].view(bt.LE_CODED_CAND_INFO_DTYPE)
+    found = {(int(x["stream"]), int(x["offset"])): int(i["symbols"]) for x, i in zip(scan_cands, scan_info)}
+    d_scr = _filled(lib.btbbx_le_discover_scratch_bytes(alloc))
+    bt.check(lib.btbbx_le_discover_group_device(d_cands.data_ptr(), d_cnt.data_ptr(), alloc, 2, d_conns.data_ptr(), alloc, d_cnt.data_ptr() + 8,
+                                                d_scr.data_ptr(), d_scr.numel(), None))
+    d_sym = _filled(4 * alloc)
+    bt.check(lib.btbbx_le_ctrack_symbols_device(d_words.data_ptr(), cap.n_words, cap.pitch_words, n_streams, d_cands.data_ptr(), d_cnt.data_ptr(), alloc,
+                                                d_sym.data_ptr(), None))
+    d_tracks, d_pkts, d_sel, d_sel_pkts = (_filled(alloc * TRACK.itemsize), _filled(alloc * PKT.itemsize), _filled(alloc * SEL.itemsize),
+                                           _filled(alloc * SEL_PKT.itemsize))
+    d_tscr = _filled(lib.btbbx_le_track_scratch_bytes(alloc, alloc))
+    args = (d_cands.data_ptr(), d_cnt.data_ptr(), alloc, d_conns.data_ptr(), d_cnt.data_ptr() + 8, alloc, d_phys.data_ptr(), n_streams)
+    tail = (m.UNIT, m.IFS, m.JITTER, lt.REMAP, d_tracks.data_ptr(), d_pkts.data_ptr(), d_tscr.data_ptr(), d_tscr.numel(), None)
+    bt.check(lib.btbbx_le_ctrack_device(*args, d_sym.data_ptr(), *tail))
+    d_cscr = _filled(lib.btbbx_le_csa2_scratch_bytes(alloc, alloc))
+    bt.check(lib.btbbx_le_csa2_device(d_cands.data_ptr(), d_cnt.data_ptr(), alloc, d_conns.data_ptr(), d_cnt.data_ptr() + 8, alloc, d_tracks.data_ptr(),
+                                      d_pkts.data_ptr(), lt.REMAP, d_sel.data_ptr(), d_sel_pkts.data_ptr(), d_cscr.data_ptr(), d_cscr.numel(), None))
+    torch.cuda.synchronize()
+    assert d_cnt.cpu().numpy()[[0, 2]].tolist() == [n, k]
+
+    def rows(buf, dtype, count):
+        raw = buf.cpu().numpy()
+        assert (raw[count * dtype.itemsize:alloc * dtype.itemsize] == 0xA5).all()
+        return raw[:count * dtype.itemsize].view(dtype)
+
+    got = dict(conns=rows(d_conns, CONN, k), cands=rows(d_cands, CAND, n), tracks=rows(d_tracks, TRACK, k), pkts=rows(d_pkts, PKT, n),
+               sel=rows(d_sel, SEL, k), sel_pkts=rows(d_sel_pkts, SEL_PKT, n), symbols=rows(d_sym, np.dtype("<u4"), n))
+    for name in want:
+        assert got[name].tobytes() == want[name].tobytes(), name
+    # the durations are the discovery's info, joined by (stream, offset)
+    assert [found[(int(x["stream"]), int(x["offset"]))] for x in got["cands"]] == got["symbols"].tolist() and len(found) == n
+    # the statement of the feature: the tracking as it stood, on the same sorted list
+    bt.check(lib.btbbx_le_track_device(*args, *tail))
+    torch.cuda.synchronize()
+    old = rows(d_tracks, TRACK, k)
+    assert old["n_events"].tolist() == (2 * got["tracks"]["n_events"]).tolist() and not old["flags"].any() and got["tracks"]["flags"].all()
+    assert got["tracks"]["n_events"].tolist() == [m.CHAIN_EVENTS] * 2 and got["tracks"]["interval"].tolist() == [6, 6]
+    # through the wrapper
+    kw = dict(max_len=27, max_errors=16, min_count=2, n_streams=n_streams, pitch_words=cap.pitch_words, n_words=cap.n_words)
+    out = bt.le_coded_track(cap.words, cap.search_bits, cap.mhz, **kw)
+    for name, arr in zip(("conns", "cands", "tracks", "pkts", "sel", "sel_pkts", "symbols"), out):
+        assert arr.tobytes() == want[name].tobytes(), name
+    # cand_cap below the candidate count: the first cand_cap sorted candidates and their parallel records
+    out = bt.le_coded_track(cap.words, cap.search_bits, cap.mhz, conn_cap=1, cand_cap=7, truncate=True, **kw)
+    for name, arr in zip(("conns", "cands", "tracks", "pkts", "sel", "sel_pkts", "symbols"), out):
+        assert arr.tobytes() == want[name][:1 if name in ("conns", "tracks", "sel") else 7].tobytes(), name
+    with pytest.raises(bt.BtbbError):
+        bt.le_coded_track(cap.words, cap.search_bits, cap.mhz, cand_cap=7, **kw)
+    # no connection stored (min_count above every group): the per-candidate records are 0xff, the durations stand
+    out = bt.le_coded_track(cap.words, cap.search_bits, cap.mhz, **dict(kw, min_count=1000))
+    assert len(out[0]) == 0 and out[3].tobytes() == b"\xff" * (PKT.itemsize * n) and out[5].tobytes() == b"\xff" * (SEL_PKT.itemsize * n)
+    assert sorted(out[6].tolist()) == sorted(durations)
