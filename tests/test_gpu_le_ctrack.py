@@ -114,7 +114,7 @@ def test_block_1_on_and_past_the_streams_end():
 
 def test_offsets_beyond_2_to_the_32():
     """Two streams, pitch_words just above 2^26 (1 GiB of zeros in HBM), one packet copied into stream 1 at bit 2^32 + 37: the stream
-    offset lies beyond 2^32 bits and the byte address beyond 2^32 bytes."""
+    offset lies beyond 2^32 bits, at about byte 2^30 of the buffer.  (Byte addresses beyond 2^32: tests/test_gpu_le_coded_frames.py.)"""
     import torch
     words, cands, notes, _ = _lattice()
     src = next(cd for cd, n in zip(cands, notes) if n == "residue 1")         # S = 2
